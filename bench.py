@@ -6,6 +6,11 @@ synthetic galaxy init, N = 2^20 bodies, on 1/2/4/8 MI355X.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W            (the driver's form: runs as one of the ranks)
 
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what takes time of its own after the clock
+has stopped: GPU clock / power telemetry during the timed steps, BASELINE.json configs[0..3] and the CPU baselines.
+--dump-outputs DIR writes x, v and a after the last timed step as DIR/{x,v,a}.npy (float64; a fixed, seeded sample of rows,
+listed in DIR/rows.npy, when the run has more than DUMP_MAX_ROWS bodies), so that two builds can be compared output for output.
+
 One process per GPU.  A "step" is one pass of the hot path over all bodies: K1 all-pairs force on the
 rank's shard of targets (all N sources), K3 leapfrog on the shard, then one RCCL all-gather of the
 updated positions over xGMI (nbody_allgather_positions of the C ABI; torch.distributed, backend "nccl", carries the
@@ -14,7 +19,7 @@ rendezvous, the barriers and the max-over-ranks of the time).  Total work is fix
 
 PyTorch is plumbing here (device memory, streams, the process group); all arithmetic is in
 stdpar-nbody_amd/libnbody_hip.so through its C ABI.  The CPU baseline leg times the oracle's
-restatement of the reference loop on this box's host cores (reported, not the target).
+restatement of the reference loop on this box's host cores (reported, not the target; --full only).
 """
 import os
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # before any HIP runtime is loaded: dmabuf IPC only on this driver
@@ -32,6 +37,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 FP64_VECTOR_PEAK_TFLOPS = 78.6   # 256 CU x 4 SIMD x 16 lanes x 2 flop x 2.4 GHz
 FP32_VECTOR_PEAK_TFLOPS = 157.3  # the same lanes at 2 x 32 bits
 FLOP_PER_INTERACTION = 20        # D=3: 3 sub + 5 r2 + 2 (sqrt, *r2) + 1 (+eps) + 3 (m*d) + 3 (/) + 3 (acc)
+DUMP_MAX_ROWS = 1 << 19          # --dump-outputs: x, v, a of at most this many bodies, 36 MiB in float64
 
 
 def load_package():
@@ -401,6 +407,20 @@ def other_configs(nb, torch):
     return out
 
 
+def dump_outputs(dirname, x, v, a):
+    """What the timed path leaves to its caller after the last timed step — positions, velocities, accelerations of every body —
+    as <dirname>/{x,v,a}.npy in float64, and the row numbers they hold as rows.npy.  Above DUMP_MAX_ROWS bodies the rows are a
+    fixed sample (numpy seed 0, ascending), the same for every run of the same --bodies."""
+    import numpy as np
+    n = x.shape[0]
+    rows = np.arange(n)
+    if n > DUMP_MAX_ROWS:
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_ROWS, replace=False))
+    os.makedirs(dirname, exist_ok=True)
+    for name, arr in (("x", x[rows]), ("v", v[rows]), ("a", a[rows]), ("rows", rows)):
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
+
+
 def visible_gpus():
     """Number of HIP devices this process could use, without creating a HIP context (torch.cuda.device_count() reads the
     driver's device list only)."""
@@ -426,6 +446,10 @@ def launch_ranks(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__), "--gpus", str(args.gpus), "--steps", str(args.steps),
            "--warmup", str(args.warmup), "--bodies", str(args.n)]
+    if args.full:
+        cmd.append("--full")
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     if args.no_cpu_baseline:
         cmd.append("--no-cpu-baseline")
     if args.exchange != "nbody":
@@ -479,8 +503,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--bodies", dest="n", type=int, default=1 << 20,
                     help="bodies (default 2^20, the BASELINE.json metric config); `--n` would collide with torchrun option prefixes")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip BASELINE.json configs[1..3] (the `configs` list of the line)")
+    ap.add_argument("--full", action="store_true",
+                    help="also sample GPU clock / power during the timed steps, then time BASELINE.json configs[0..3] and the CPU "
+                         "baselines (the `gpu_telemetry`, `configs` and `cpu_baseline` entries of the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write x, v, a after the last timed step as DIR/{x,v,a}.npy (float64) and the rows they hold as DIR/rows.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip BASELINE.json configs[0..3] (the `configs` list of the line)")
     ap.add_argument("--exchange", choices=("nbody", "torch"), default="nbody",
                     help="the per-step all-gather of positions: nbody = the library's own collective (nbody_allgather_positions, "
                          "RCCL behind the C ABI; what the metric is about, and the only form that earns a normal line); torch = "
@@ -488,6 +517,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     force_dist = os.environ.get("NBODY_BENCH_FORCE_DIST") == "1"
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or force_dist):
@@ -637,7 +668,7 @@ def main():
     if fault == "stale_late":
         sim.exchange_positions = stale_exchange
     torch.cuda.synchronize()
-    telemetry = Telemetry(local_rank) if rank == 0 else None
+    telemetry = Telemetry(local_rank) if rank == 0 and args.full else None
     if telemetry:
         telemetry.__enter__()
     t0 = time.perf_counter()
@@ -657,6 +688,10 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:   # before the multi-rank checks below, which recompute a
+        x, v, a = sim.gather_state()   # collective for world > 1
+        if rank == 0:
+            dump_outputs(args.dump_outputs, x, v, a)
 
     # dominant kernel: K1.  Algorithmic flops per launch = 20 x (targets of this rank) x (n - 1).  HIP events on the stream
     # the kernels are launched on (torch's current stream is handed to the C ABI).
@@ -794,12 +829,12 @@ def main():
                                  "(20 algorithmic flop per ordered pair, SURVEY 8d); traffic/rocprof are null unless a "
                                  "committed PMC summary carries this run's kernel description and source hash"},
         }
-        if world == 1 and not args.no_other_configs:
+        if world == 1 and args.full and not args.no_other_configs:
             try:   # BASELINE.json configs[1..3], after the headline's clock has stopped: reported extras, never lose the line over them
                 out["configs"] = other_configs(nb, torch)
             except Exception as ex:
                 out["configs"] = [{"workload": "configs[1..3]", "failed": str(ex)}]
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(n, hs)
             except Exception as ex:  # the baseline is a reported extra; never lose the GPU line over it

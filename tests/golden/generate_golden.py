@@ -9,6 +9,7 @@ Fixtures:
   print_state.json   --print-state text rows (start + final) per case          
   positions.npz      positions.bin frames (+ energy.bin pairs) per case        
   hilbert.json       hilbert<2>/<3>, interleave_bits known-answer vectors      
+  help_d3.txt        the --help text of the D=3 binary
 """
 import json
 import os
@@ -108,6 +109,8 @@ def main():
     out = subprocess.run([os.path.join(O.REF_DIR, "ref_units")], input=inp, capture_output=True, text=True, check=True).stdout
     vecs = [[int(t) for t in line.split()] for line in out.splitlines()]  # dim c0 c1 c2 hilbert interleave
     json.dump(vecs, open(os.path.join(OUT, "hilbert.json"), "w"))
+    with open(os.path.join(OUT, "help_d3.txt"), "w") as f:
+        f.write(O.ref_run(3, ["--help"]))
     print(f"wrote {len(ps)} print-state cases, {len(meta)} position cases, {len(vecs)} hilbert vectors")
 
 

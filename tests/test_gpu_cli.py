@@ -239,7 +239,8 @@ def test_gpus_flag_multi_device_path_on_one_gpu():
     assert r.returncode != 0 and "HIP devices visible" in r.stderr
     r = cli(3, ["-n", 1000, "--algorithm", "bvh", "--gpus", 2])
     assert r.returncode != 0 and "all-pairs only" in r.stderr
-    r = cli(3, ["-n", 1000, "-s", 2, "--algorithm", "all-pairs", "--gpus", 1, "--save", "energy", "--csv-detailed"])
+    with tempfile.TemporaryDirectory() as d:   # the CLI opens energy.bin in its working directory before it refuses
+        r = cli(3, ["-n", 1000, "-s", 2, "--algorithm", "all-pairs", "--gpus", 1, "--save", "energy", "--csv-detailed"], cwd=d)
     assert r.returncode != 0 and "one GPU only" in r.stderr
 
 

@@ -61,7 +61,7 @@ def test_bench_line_carries_configs_1_to_4_and_the_handoff_status():
     dominant kernel, its average launch time from HIP events, and achieved / peak = frac against the roofline that bounds it (one
     meaning of `frac` in the whole list); config 1 — the one that names the CPU path — carries both legs, the CPU port timed over
     the whole config; and K1's chunk hand-off status over the run (no failure; how many waves had to wait)."""
-    line = _bench({}, "--gpus", "1", "--steps", "1", "--warmup", "1", "--bodies", str(1 << 16), "--no-cpu-baseline")
+    line = _bench({}, "--gpus", "1", "--steps", "1", "--warmup", "1", "--bodies", str(1 << 16), "--no-cpu-baseline", "--full")
     assert line["roofline"]["handoff"]["failed"] is False and line["roofline"]["handoff"]["polls"] >= 0
     cfg = line["configs"]
     assert len(cfg) == 4 and not any("failed" in c for c in cfg), cfg
@@ -84,6 +84,30 @@ def test_bench_line_carries_configs_1_to_4_and_the_handoff_status():
     assert c4["not_the_bound"]["hbm_cold_bytes_per_s"] > c4["not_the_bound"]["hbm_peak_bytes_per_s"]   # why 8(d)'s HBM model is not the bound
     for c in cfg:
         assert c["ms_per_step"] > 0 and c["body_steps_per_s"] > 0 and abs(c["frac"] - c["achieved"] / c["peak"]) < 1e-12
+
+
+@pytest.mark.parametrize("n,steps,warmup", [(1 << 14, 2, 1), ((1 << 19) + 3, 1, 0)])
+def test_bench_dump_outputs_are_the_state_after_the_timed_steps(nb, tmp_path, n, steps, warmup):
+    """--dump-outputs DIR: x, v, a after the last timed step (float64), bit for bit the state the library's all-pairs driver
+    reaches in warm-up + timed steps from the same galaxy init; above 2^19 bodies a fixed sample of rows, listed in rows.npy.
+    A plain run leaves out what --full adds."""
+    line = _bench({}, "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--bodies", str(n), "--dump-outputs", str(tmp_path))
+    assert line["steps"] == steps and line["ms_per_step"] > 0
+    assert "configs" not in line and "cpu_baseline" not in line and line["gpu_telemetry"] is None
+    got = {k: np.load(tmp_path / f"{k}.npy") for k in ("x", "v", "a", "rows")}
+    assert all(g.dtype == np.float64 for g in got.values())
+    rows = got["rows"].astype(np.int64)
+    if n <= 1 << 19:
+        assert np.array_equal(rows, np.arange(n))
+    else:
+        assert len(rows) == 1 << 19 and np.all(np.diff(rows) > 0) and rows[-1] < n
+    assert sum(g.nbytes for g in got.values()) <= 64 << 20
+    dev = nb.DeviceSystem.from_host(nb.build_model(nb.F64, 3, "galaxy", n))
+    nb.run(dev, "all-pairs", steps + warmup)
+    ref = dev.download()
+    dev.close()
+    for k in ("x", "v", "a"):
+        assert np.array_equal(got[k], getattr(ref, k)[rows]), k
 
 
 def test_bench_refuses_more_gpus_than_visible():

@@ -8,7 +8,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd $R
-echo "== bench"; timeout -k 10 300 python3 bench.py --steps 5 --warmup 1 > $O/bench_n1.json 2> $O/bench_n1.err; tail -c 600 $O/bench_n1.json
+echo "== bench"; timeout -k 10 300 python3 bench.py --steps 5 --warmup 1 --full > $O/bench_n1.json 2> $O/bench_n1.err; tail -c 600 $O/bench_n1.json
 echo "== profile bench"; timeout -k 10 500 bash tools/profile_bench.sh $TAG > $O/profile_bench.txt 2>&1; tail -5 $O/profile_bench.txt
 echo "== configs"; timeout -k 10 300 python3 tools/measure_configs.py > $O/configs_all.json 2> $O/configs_all.err; grep -c config $O/configs_all.json
 echo "== K1 sizes"; timeout -k 10 200 python3 tools/time_all_pairs.py 10 > $O/k1_times.json 2> $O/k1_times.err
