@@ -76,8 +76,9 @@ typedef struct nbody_state {
  * 2.2: nbody_bvh_read what = 6 and nbody_bvh_opening_thresholds (the opening test as one compare), nbody_all_pairs_pair_rule;
  *      the measured forms that are not shipped (traversal 3 / 4 / 6, octree build 2 / 4) are refused by this library.
  * 2.3: nbody_all_pairs_status; nbody_stream_sync / nbody_download return NBODY_ERR_STATE after a failed K1 chunk hand-off;
- *      nbody_all_pairs_pair_rule decides from the positions' variances, not from their bounding box. */
-#define NBODY_HIP_ABI_VERSION 2003
+ *      nbody_all_pairs_pair_rule decides from the positions' variances, not from their bounding box.
+ * 2.4: Plummer softening: nbody_all_pairs_softened_force, nbody_calc_energies_softened, nbody_octree_compute_softened_force. */
+#define NBODY_HIP_ABI_VERSION 2004
 int nbody_abi_version(void);
 
 /* Last error message of the calling thread ("" if none). */
@@ -244,6 +245,31 @@ int nbody_octree_info(nbody_octree* t, uint32_t* tree_size, void* root_mass, voi
 /* Test/diagnostic: per-body {nodes examined, terms accumulated} u32[n][2] of the last compute_force. */
 int nbody_octree_enable_counters(nbody_octree* t, int on);
 int nbody_octree_read_counters(nbody_octree* t, uint32_t* host_out, size_t bytes, void* stream);
+
+/* ---- softening (no reference counterpart: its eps(T) is machine epsilon, a guard against 0 / 0) ------------------------
+ * Plummer softening with length eps.  e2 = fl_T(T(eps) * T(eps)); eps must be finite and > 0 and e2 a normal number of T with
+ * e2^(-3/2) finite: e2 >= 2^-84 in float (eps >= ~1.5e-13), 2^-680 in double (eps >= ~1.4e-103).  Anything else returns
+ * NBODY_ERR_ARG before the device is touched.  "No softening" is the unsoftened entry points, unchanged.
+ *   force      a[i] = c * sum_{j != i} m[j] * (x[j] - x[i]) / (|x[j] - x[i]|^2 + e2)^(3/2)
+ *              The self term is 0 because its difference is 0; coincident distinct bodies add 0 too.  No branch, no pair rule:
+ *              |x[j] - x[i]|^2 + e2 is the FMA chain of the unsoftened K1 seeded with e2, the weight (m y^3)(1 + e(3/2 + 15/8 e)) from
+ *              v_rsq_f64 (<= 2.5 ulp) in double, m y^3 from v_rsq_f32 in float.
+ *   potential  -0.5 * c * sum_i m_i sum_{j != i} m_j / sqrt(|x_i - x_j|^2 + e2): the self term (m_i / eps, not 0) is excluded by
+ *              index; coincident distinct bodies contribute m_i m_j / eps.  The kinetic energy is the unsoftened call's, bit for bit.
+ *   octree     opening decisions unchanged (the reference's side / (sqrt(d2) + eps(T)) < theta on the unsoftened distance); only
+ *              the accepted term changes, to m_node * d / (|d|^2 + e2)^(3/2).
+ * Rounding structure: the unsoftened K1's.  A target's sum follows from sz alone (slices, chunks, chunk-order hand-off or collect),
+ * so any shard window sums bitwise like the whole system, and both K1 source paths give the same bits. */
+
+/* K1 softened; honours the shard window and nbody_state.tuning like nbody_all_pairs_force, and uses the stream's packed-source
+ * scratch the same way (a context's stream: it may be recorded into a step graph). */
+int nbody_all_pairs_softened_force(const nbody_state* s, double eps, void* stream);
+/* nbody_calc_energies with the softened potential (whole system; blocking; host outputs, one T each). */
+int nbody_calc_energies_softened(const nbody_state* s, double eps, void* kinetic_out, void* potential_out, void* stream);
+/* nbody_octree_compute_force with the softened accepted term: the compiler-scheduled walk (form 1) whatever the walk setting
+ * says on auto; NBODY_ERR_ARG if nbody_octree_set_walk(t, 2) asked for the ISA visit round, which has no softened form.
+ * Counters (nbody_octree_read_counters) are the unsoftened walk's bit for bit. */
+int nbody_octree_compute_softened_force(nbody_octree* t, const nbody_state* s, double theta, double eps, void* stream);
 
 /* ---- owning context (device mirrors of a host System), used by the C++ CLI host ------------------ */
 

@@ -56,6 +56,7 @@ ABI_SYMBOLS = [
     "nbody_comm_get_unique_id", "nbody_comm_create", "nbody_comm_create_all", "nbody_comm_destroy", "nbody_comm_world",
     "nbody_comm_rank", "nbody_comm_rccl_version", "nbody_shard_range", "nbody_comm_group_begin", "nbody_comm_group_end",
     "nbody_allgather_positions", "nbody_bvh_opening_thresholds", "nbody_all_pairs_pair_rule", "nbody_all_pairs_status",
+    "nbody_all_pairs_softened_force", "nbody_calc_energies_softened", "nbody_octree_compute_softened_force",
 ]
 ABI_MAJOR = 2
 COMM_ID_BYTES = 128
@@ -352,6 +353,11 @@ class Octree:
     def compute_force(self, st, theta, stream=None):
         _check(lib().nbody_octree_compute_force(self.h, C.byref(st), C.c_double(theta), C.c_void_p(stream)))
 
+    def compute_softened_force(self, st, theta, eps, stream=None):
+        """compute_force with Plummer softening eps > 0 (nbody_octree_compute_softened_force): the same opening decisions, the
+        accepted term m d / (|d|^2 + eps^2)^(3/2); the compiler-scheduled walk (refused after set_walk(2))."""
+        _check(lib().nbody_octree_compute_softened_force(self.h, C.byref(st), C.c_double(theta), C.c_double(eps), C.c_void_p(stream)))
+
     def info(self, stream=None):
         """(tree size = next_free_child_group, root mass); raises if the build hit the depth limit / node pool."""
         size = C.c_uint32()
@@ -442,6 +448,11 @@ class DeviceSystem:
         st = self.state(first, count)
         _check(lib().nbody_all_pairs_force(C.byref(st), C.c_void_p(self.stream)))
 
+    def all_pairs_softened_force(self, eps, first=0, count=None):
+        """K1 with Plummer softening eps > 0 (nbody_all_pairs_softened_force); (first, count) is a shard window as in all_pairs_force."""
+        st = self.state(first, count)
+        _check(lib().nbody_all_pairs_softened_force(C.byref(st), C.c_double(eps), C.c_void_p(self.stream)))
+
     def all_pairs_collapsed_force(self):
         st = self.state()
         _check(lib().nbody_all_pairs_collapsed_force(C.byref(st), C.c_void_p(self.stream)))
@@ -450,12 +461,16 @@ class DeviceSystem:
         st = self.state(first, count)
         _check(lib().nbody_accelerate_step(C.byref(st), C.c_void_p(self.stream)))
 
-    def calc_energies(self):
-        """(kinetic, potential) as in System::calc_energies (src/system.h:62-79); blocking."""
+    def calc_energies(self, softening=0.0):
+        """(kinetic, potential) as in System::calc_energies (src/system.h:62-79); blocking.  softening > 0: the potential of the
+        softened force, -c/2 sum_i m_i sum_{j != i} m_j / sqrt(|x_i - x_j|^2 + softening^2) (nbody_calc_energies_softened)."""
         t = np_dtype(self.dtype)
         ke, pe = np.zeros(1, t), np.zeros(1, t)
         st = self.state()
-        _check(lib().nbody_calc_energies(C.byref(st), _p(ke), _p(pe), C.c_void_p(self.stream)))
+        if softening:
+            _check(lib().nbody_calc_energies_softened(C.byref(st), C.c_double(softening), _p(ke), _p(pe), C.c_void_p(self.stream)))
+        else:
+            _check(lib().nbody_calc_energies(C.byref(st), _p(ke), _p(pe), C.c_void_p(self.stream)))
         return ke[0], pe[0]
 
     # K4..K9
@@ -471,14 +486,17 @@ class DeviceSystem:
             self._octree = Octree(self.dtype, self.dim, self.n, self.device)
         return self._octree
 
-    def octree_force(self, theta):
-        """One force phase of run_octree (src/octree.h:321-326)."""
+    def octree_force(self, theta, softening=0.0):
+        """One force phase of run_octree (src/octree.h:321-326); softening > 0 takes the softened walk."""
         st, t = self.state(), self.octree
         t.clear(self.stream)
         t.compute_bounds(st, self.stream)
         t.insert(st, self.stream)
         t.compute_tree(self.stream)
-        t.compute_force(st, theta, self.stream)
+        if softening:
+            t.compute_softened_force(st, theta, softening, self.stream)
+        else:
+            t.compute_force(st, theta, self.stream)
 
     def bvh_force(self, theta):
         """One force phase of run_bvh (src/bvh.h:382-393)."""

@@ -70,110 +70,19 @@ template <typename T, int D, int R, int JS>
 __global__ __launch_bounds__(kBlock) void all_pairs_force_kernel(const T* __restrict__ m, const T* __restrict__ x,
                                                                  T* __restrict__ a, T c, uint32_t sz, uint32_t first,
                                                                  uint32_t count, const k1_rule* __restrict__ rule) {
-  using rec_t = src_rec<T, D>;
-  constexpr int TG  = kWaves / JS;    // target groups per block
-  constexpr int TB  = TG * 64 * R;    // targets per block
-  constexpr int LPT = kTileJ / kBlock;  // source records each lane stages per tile
-  constexpr int SUB = kTileJ / JS;    // sources of a tile handled by one wave
-
-  __shared__ rec_t tile[kTileJ];
-  __shared__ T partial[(JS > 1) ? (JS - 1) * TG * 64 * R * D : 1];
-
-  const int lane   = threadIdx.x & 63;
-  const int wave   = threadIdx.x >> 6;
-  const int tgroup = wave / JS;
-  const int jpart  = wave % JS;
-
-  // targets of this lane
-  T xi[R][D], acc[R][D];
-  uint32_t ti[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    uint32_t local = blockIdx.x * TB + tgroup * (64 * R) + r * 64 + lane;
-    ti[r]          = local;
-    uint64_t i     = uint64_t(first) + (local < count ? local : 0u);  // clamp: out-of-range lanes compute, never store
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-      xi[r][k]  = x[i * D + k];
-      acc[r][k] = T(0);
-    }
-  }
-
-  const uint32_t ntiles = (sz + kTileJ - 1) / kTileJ;
-  const pair_consts<T> pc;
-  const bool ffar = ap_far_mode(rule);
-
-  // register staging of one tile: LPT records per lane
-  rec_t stage[LPT];
-  auto stage_load = [&](uint32_t t) {
-#pragma unroll
-    for (int q = 0; q < LPT; ++q) {
-      uint64_t j = uint64_t(t) * kTileJ + q * kBlock + threadIdx.x;
-      if (j < sz) {
-#pragma unroll
-        for (int k = 0; k < D; ++k) stage[q].p[k] = x[j * D + k];
-        stage[q].m = m[j];
-      } else {  // padding: zero mass contributes exactly 0
-#pragma unroll
-        for (int k = 0; k < D; ++k) stage[q].p[k] = T(0);
-        stage[q].m = T(0);
-      }
-      if (D == 2) stage[q].p[2] = T(0);
-    }
-  };
-
-  stage_load(0);
-  auto run = [&](auto ff) {  // the tile loop, once per pair rule (pair_batch)
-    constexpr bool FF = decltype(ff)::value;
-    for (uint32_t t = 0; t < ntiles; ++t) {
-      __syncthreads();  // every wave is done reading the previous tile
-#pragma unroll
-      for (int q = 0; q < LPT; ++q) tile[q * kBlock + threadIdx.x] = stage[q];
-      __syncthreads();
-      if (t + 1 < ntiles) stage_load(t + 1);  // in flight while this tile is consumed
-
-      const rec_t* src = &tile[jpart * SUB];
-      constexpr int U  = 64 / int(sizeof(rec_t));  // the scalar-stream form's batch: 2 records in f64, 4 in f32
-#pragma unroll 2
-      for (int jj = 0; jj < SUB; jj += U) {
-        rec_t s[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) s[u] = src[jj + u];  // wave-uniform address: LDS broadcast
-        pair_batch<T, D, R, U, FF>(acc, xi, s, pc);
-      }
-    }
-  };
-  if (ffar) run(std::true_type{});
-  else run(std::false_type{});
-
-  // combine the JS source-split partials in wave order, then a = c * sum
-  if constexpr (JS > 1) {
-    __syncthreads();
-    if (jpart > 0) {
-#pragma unroll
-      for (int r = 0; r < R; ++r)
-#pragma unroll
-        for (int k = 0; k < D; ++k) partial[((((jpart - 1) * TG + tgroup) * R + r) * D + k) * 64 + lane] = acc[r][k];
-    }
-    __syncthreads();
-    if (jpart == 0) {
-#pragma unroll
-      for (int p = 1; p < JS; ++p)
-#pragma unroll
-        for (int r = 0; r < R; ++r)
-#pragma unroll
-          for (int k = 0; k < D; ++k) acc[r][k] += partial[((((p - 1) * TG + tgroup) * R + r) * D + k) * 64 + lane];
-    }
-  }
-  if (jpart == 0) {
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      if (ti[r] < count) {
-#pragma unroll
-        for (int k = 0; k < D; ++k) a[uint64_t(ti[r]) * D + k] = c * acc[r][k];
-      }
-    }
-  }
+  [[maybe_unused]] constexpr T e2 = T(0);
+#define K1_SOFT false
+#include "k1_tile_body.inc"
+#undef K1_SOFT
+}
+template <typename T, int D, int R, int JS>
+__global__ __launch_bounds__(kBlock) void all_pairs_softened_kernel(const T* __restrict__ m, const T* __restrict__ x,
+                                                                    T* __restrict__ a, T c, uint32_t sz, uint32_t first,
+                                                                    uint32_t count, T e2) {
+  const k1_rule* const rule = nullptr;
+#define K1_SOFT true
+#include "k1_tile_body.inc"
+#undef K1_SOFT
 }
 
 // Scalar-stream form: pre-pass that packs (x, m) into aligned records, zero-mass padding up to a whole tile.
@@ -354,212 +263,23 @@ __global__ __launch_bounds__(64 * kSgprWaves<JS>) void all_pairs_force_sgpr_kern
                                                                                    uint32_t first, uint32_t count,
                                                                                    uint32_t tiles_per_chunk, k1_handoff h,
                                                                                    const k1_rule* __restrict__ rule) {
-  using rec_t = src_rec<T, D>;
-  constexpr int TG  = kSgprWaves<JS> / JS;
-  constexpr int TB  = TG * 64 * R;
-  constexpr int SUB = kTileJ / JS;
-  __shared__ T partial[(JS > 1) ? (JS - 1) * TG * 64 * R * D : 1];
-  const int lane   = threadIdx.x & 63;
-  const int wave   = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int tgroup = wave / JS;
-  const int jpart  = wave % JS;
-  T xi[R][D], acc[R][D];
-  uint32_t ti[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    uint32_t local = blockIdx.x * TB + tgroup * (64 * R) + r * 64 + lane;
-    ti[r]          = local;
-    uint64_t i     = uint64_t(first) + (local < count ? local : 0u);
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-      xi[r][k]  = x[i * D + k];
-      acc[r][k] = T(0);
-    }
-  }
-  // source chunk of this block (grid.y): tiles [t0, t1) of the padded source set; one chunk = everything when grid.y == 1
-  const uint32_t ntiles = (sz + kTileJ - 1) / kTileJ;
-  const uint32_t t0     = blockIdx.y * tiles_per_chunk;
-  const uint32_t t1     = min(ntiles, t0 + tiles_per_chunk);
-  const pair_consts<T> pc;
-  const bool ffar       = ap_far_mode(rule);
-  const uint32_t nsteps = (t1 - t0) * SUB;  // sources this wave visits: its SUB-record slice of every tile, in tile order
-  constexpr int U = 64 / int(sizeof(rec_t));  // records per 64-byte batch (2 in f64, 4 in f32); SUB % (2 * U) == 0
-  struct batch_t {
-    rec_t r[U];
-  };
-  auto batch = [&](uint32_t k) { return packed + (uint64_t(t0 + k / SUB) * kTileJ + uint32_t(jpart) * SUB + (k % SUB)); };
-  // Two SGPR buffers, each requested (s_load_dwordx16) one compute phase before it is consumed.  Written with inline
-  // asm: hipcc folds a loop-carried load from read-only memory back into a load at the loop top and waits for it there.
-  // SMEM returns out of order, so the only usable wait is lgkmcnt(0): wait for X, request Y, consume X.
-  auto run = [&](auto ff) {  // the source stream, once per pair rule (pair_batch)
-    constexpr bool FF = decltype(ff)::value;
-    sgpr16 A = sload16(batch(0), xi[0][0]), B;
-    for (uint32_t k = 0; k < nsteps; k += 2 * U) {
-      swait(A, acc[0][0]);
-      B = sload16(batch(k + U), xi[0][0]);
-      {
-        const batch_t ba = __builtin_bit_cast(batch_t, A);
-        pair_batch<T, D, R, U, FF>(acc, xi, ba.r, pc);
-      }
-      swait(B, acc[0][0]);
-      A = sload16(batch(k + 2 * U < nsteps ? k + 2 * U : k), xi[0][0]);  // the last iteration re-requests its own batch
-      {
-        const batch_t bb = __builtin_bit_cast(batch_t, B);
-        pair_batch<T, D, R, U, FF>(acc, xi, bb.r, pc);
-      }
-    }
-    swait(A, acc[0][0]);  // nothing in flight when the wave goes on
-  };
-  if constexpr (RULE == 1) run(std::false_type{});      // (experiments: one rule per instantiation, forced from the host)
-  else if constexpr (RULE == 2) run(std::true_type{});
-  else if (ffar) run(std::true_type{});  // two copies of the loop: inside ONE loop hipcc hoists the rules' common head above the branch
-  else run(std::false_type{});
-  if constexpr (JS > 1) {
-    if (jpart > 0) {
-#pragma unroll
-      for (int r = 0; r < R; ++r)
-#pragma unroll
-        for (int k = 0; k < D; ++k) partial[((((jpart - 1) * TG + tgroup) * R + r) * D + k) * 64 + lane] = acc[r][k];
-    }
-    __syncthreads();
-    if (jpart == 0) {
-#pragma unroll
-      for (int p = 1; p < JS; ++p)
-#pragma unroll
-        for (int r = 0; r < R; ++r)
-#pragma unroll
-          for (int k = 0; k < D; ++k) acc[r][k] += partial[((((p - 1) * TG + tgroup) * R + r) * D + k) * 64 + lane];
-    }
-  }
-  if (jpart != 0) return;
-  const uint32_t y = blockIdx.y, last = gridDim.y - 1u;
-  uint32_t* const tw = h.turn + blockIdx.x * TG + tgroup;  // nullptr + ... when there is one chunk: never dereferenced (y == last == 0)
-  if (h.sums != nullptr) {
-    // Small launches (all blocks resident within a few rounds: the blocks of one target group's sixteen chunks finish TOGETHER, and
-    // a chain of turns is fifteen dependent round trips through memory — 18 of 41 us at N = 4096, 42 of 76 us in float at 8192):
-    // every chunk's wave stores its sum, then draws a ticket; whoever draws the last one — whichever chunk it is — adds the
-    // sums IN CHUNK ORDER, ((s_0 + s_1) + s_2) + ..., applies c and writes `a`: the same bits as the turns give, no waiting, no
-    // failure mode.  The sums are agent-scope stores acknowledged (s_waitcnt 0) before the ticket is drawn.
-    const size_t group_scalars = size_t(R) * D * 64;
-    T* const all  = static_cast<T*>(h.sums);
-    T* const mine = all + ((size_t(y) * gridDim.x + blockIdx.x) * TG + tgroup) * group_scalars;
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-      for (int k = 0; k < D; ++k) __hip_atomic_store(mine + (r * D + k) * 64 + lane, acc[r][k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __builtin_amdgcn_s_waitcnt(0);
-    __builtin_amdgcn_wave_barrier();
-    uint32_t drawn = 0;
-    if (lane == 0) drawn = __hip_atomic_fetch_add(tw, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (uint32_t(__builtin_amdgcn_readfirstlane(int(drawn))) != last) return;
-    T tot[R][D];
-    for (uint32_t yy = 0; yy <= last; ++yy) {
-      const T* src = all + ((size_t(yy) * gridDim.x + blockIdx.x) * TG + tgroup) * group_scalars;
-#pragma unroll
-      for (int r = 0; r < R; ++r)
-#pragma unroll
-        for (int k = 0; k < D; ++k) {
-          const T v = __hip_atomic_load(src + (r * D + k) * 64 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          tot[r][k] = yy == 0 ? v : tot[r][k] + v;
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-      if (ti[r] < count) {
-#pragma unroll
-        for (int k = 0; k < D; ++k) a[uint64_t(ti[r]) * D + k] = c * tot[r][k];
-      }
-    return;
-  }
-  bool poisoned = false;
-  if (y > 0 && h.turn != nullptr) {  // my turn?  (wave-uniform address: every lane reads the same value)
-    uint32_t spins = 0, seen;
-    if (y == 1)
-      for (uint32_t d = 0; d < h.late; ++d) __builtin_amdgcn_s_sleep(127);  // 0 rounds, except in the hand-off tests of the experiments build
-    while ((seen = __hip_atomic_load(tw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != y) {
-      if (seen == kTurnPoison) {  // somebody gave up on this group: nobody will add to its total again, NaN goes over it
-        poisoned = true;
-        break;
-      }
-      if (++spins > h.spins) {  // give up (see above)
-        if (lane == 0) {
-          __hip_atomic_exchange(tw, kTurnPoison, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if (atomicCAS(&h.status->err, 0u, 1u) == 0u) {
-            h.status->block = blockIdx.x;
-            h.status->group = uint32_t(tgroup);
-            h.status->chunk = y;
-          }
-        }
-        poisoned = true;  // whatever the word held — this wave's own number (the turn came between the last poll and the swap), a
-        break;            // predecessor's that has yet to come, or poison already — the group's total is overwritten with NaN
-      }
-      __builtin_amdgcn_s_sleep(8);
-    }
-    // The loads of the running total below must be ISSUED after the poll that saw the turn.  The accesses are relaxed agent-scope
-    // atomics (sc1: they bypass this XCD's L2), so nothing has to be invalidated; what is needed is that the compiler keeps them
-    // behind the loop — a wavefront-scope acquire fence says so and emits no instruction (tools/check_k1_handoff.py verifies in the
-    // built code object that every load of the total carries sc1 and follows the last poll).
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (spins && lane == 0) {
-      atomicAdd(&h.status->polls, (unsigned long long)spins);
-      atomicAdd(&h.status->waits, 1ull);
-    }
-  }
-  // The total's R * D * 64 scalars of this target group are contiguous in `a`: through LDS (the slices' partials are spent) every
-  // lane takes scalars e = q * 64 + lane, so each access is one full-width coalesced instruction — per component the lanes would
-  // touch every line three times (measured: 3.2 GB of traffic per launch at N = 2^20 instead of 1.3).
-  const uint32_t gbase = blockIdx.x * TB + tgroup * (64 * R);  // first target of the group
-  auto add_sum = [&](bool nan) {  // nan: overwrite the group's total with NaN instead
-    if constexpr (JS > 1) {
-      T* stage = partial + size_t(tgroup) * R * D * 64;  // [(jpart - 1 = 0) * TG + tgroup] block of the partials: read above, free now
-      if (!nan) {
-#pragma unroll
-        for (int r = 0; r < R; ++r)
-#pragma unroll
-          for (int k = 0; k < D; ++k) stage[(r * 64 + lane) * D + k] = acc[r][k];
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-      }
-#pragma unroll
-      for (int q = 0; q < R * D; ++q) {
-        const uint32_t e = uint32_t(q) * 64u + uint32_t(lane);
-        if (gbase + e / D < count) {
-          T* slot = a + uint64_t(gbase) * D + e;
-          T t     = nan ? T(__builtin_nan("")) : stage[e];
-          if (!nan && y > 0) t = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + t;  // ((s_0 + s_1) + ...) + s_y
-          if (!nan && y == last) t = c * t;
-          __hip_atomic_store(slot, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-      }
-    } else {
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        if (ti[r] < count) {
-#pragma unroll
-          for (int k = 0; k < D; ++k) {
-            T* slot = a + uint64_t(ti[r]) * D + k;
-            T t     = nan ? T(__builtin_nan("")) : acc[r][k];
-            if (!nan && y > 0) t = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + t;
-            if (!nan && y == last) t = c * t;
-            __hip_atomic_store(slot, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-        }
-      }
-    }
-  };
-  add_sum(poisoned);
-  if (y < last && !poisoned && h.turn != nullptr) {  // pass the turn on once the stores above have been acknowledged
-    for (uint32_t d = 0; d < h.delay; ++d) __builtin_amdgcn_s_sleep(127);  // 0 rounds, except in the hand-off tests of the experiments build
-    __builtin_amdgcn_s_waitcnt(0);  // vmcnt(0) expcnt(0) lgkmcnt(0): this wave's stores are at the agent's coherence point
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // and the compiler keeps them above the hand-over (no instruction)
-    __builtin_amdgcn_wave_barrier();
-    uint32_t held = y;
-    if (lane == 0) {
-      __hip_atomic_compare_exchange_strong(tw, &held, y + 1u, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    held = __builtin_amdgcn_readfirstlane(held);  // what the word held: y, or kTurnPoison left by a successor that gave up
-    if (held != y) add_sum(true);
-  }
+  [[maybe_unused]] constexpr T e2 = T(0);
+#define K1_SOFT false
+#include "k1_sgpr_body.inc"
+#undef K1_SOFT
+}
+// Softened K1 (nbody_all_pairs_softened_force): a name of its own, so that the instantiations of the unsoftened kernel stay what
+// they were (tools/check_k1_handoff.py holds this one to the same hand-off rules with KERNEL set to its name).
+template <typename T, int D, int R, int JS>
+__global__ __launch_bounds__(64 * kSgprWaves<JS>) void all_pairs_softened_sgpr_kernel(const src_rec<T, D>* __restrict__ packed,
+                                                                                      const T* __restrict__ x, T* a, T c, uint32_t sz,
+                                                                                      uint32_t first, uint32_t count,
+                                                                                      uint32_t tiles_per_chunk, k1_handoff h, T e2) {
+  constexpr int RULE = 0;
+  const k1_rule* const rule = nullptr;
+#define K1_SOFT true
+#include "k1_sgpr_body.inc"
+#undef K1_SOFT
 }
 
 // Scratch (packed sources; per-chunk sums), one slot per (device, stream) that has called the scalar-stream form (grow-only).  A context
@@ -737,11 +457,12 @@ static size_t ap_rule_bytes(uint32_t sz, int dim) {
 
 // Everything a K1 launch needs done first, queued as ONE launch (k1_prepare_kernel): the packed records (pack: the scalar-stream
 // form), the pair rule of the whole system (sz >= kFarMinBodies; nullptr = "dense" below) and the turn words handed back to chunk 0.
+// The softened K1 has no pair rule (with_rule false): no moments are summed.
 template <typename T, int D>
 static int ap_prepare(const nbody_state* s, hipStream_t st, bool pack, src_rec<T, D>** packed_out, const k1_rule** rule_out,
-                      uint32_t* turn, size_t turn_words) {
+                      uint32_t* turn, size_t turn_words, bool with_rule = true) {
   const uint32_t padded = (s->sz + kTileJ - 1) / kTileJ * kTileJ;
-  const bool moments    = s->sz >= kFarMinBodies;
+  const bool moments    = with_rule && s->sz >= kFarMinBodies;
   void* scratch         = nullptr;
   if (pack)
     if (int r = ap_scratch_get(st, 0, 4 * sizeof(T) * size_t(padded), &scratch)) return r;
@@ -785,8 +506,8 @@ static size_t sgpr_turn_words(uint32_t count) {
   return size_t((count + TB - 1) / TB) * TG;
 }
 
-template <typename T, int D, int R, int JS>
-static int launch_all_pairs_sgpr(const nbody_state* s, const k1_plan& plan, hipStream_t st) {
+template <typename T, int D, int R, int JS, bool SOFT>
+static int launch_all_pairs_sgpr(const nbody_state* s, const k1_plan& plan, hipStream_t st, T e2) {
   constexpr int TB = (kSgprWaves<JS> / JS) * 64 * R;
   uint32_t blocks  = (s->count + TB - 1) / TB;
   if (blocks == 0) return NBODY_OK;
@@ -811,7 +532,15 @@ static int launch_all_pairs_sgpr(const nbody_state* s, const k1_plan& plan, hipS
   }
   src_rec<T, D>* packed = nullptr;
   const k1_rule* rule   = nullptr;
-  if (int r = ap_prepare<T, D>(s, st, true, &packed, &rule, h.turn, h.turn ? sgpr_turn_words<R, JS>(s->count) : 0)) return r;
+  if (int r = ap_prepare<T, D>(s, st, true, &packed, &rule, h.turn, h.turn ? sgpr_turn_words<R, JS>(s->count) : 0, !SOFT)) return r;
+  if constexpr (SOFT) {
+    hipLaunchKernelGGL((all_pairs_softened_sgpr_kernel<T, D, R, JS>), dim3(blocks, plan.chunks), dim3(64 * kSgprWaves<JS>), 0, st,
+                       packed, static_cast<const T*>(s->x), static_cast<T*>(s->a), static_cast<T>(s->c), s->sz, s->first, s->count,
+                       plan.tiles_per_chunk, h, e2);
+    NB_HIP(hipGetLastError());
+    if (h.turn != nullptr && h.sums == nullptr) ap_status_mark(st);
+    return NBODY_OK;
+  }
 #ifdef NBODY_EXPERIMENTS
   if (const char* e = getenv("NBODY_K1_RULE_FORCE"); e && JS == 8 && D == 3) {  // timing experiment: one rule per instantiation
     if (e[0] == '1')
@@ -834,11 +563,17 @@ static int launch_all_pairs_sgpr(const nbody_state* s, const k1_plan& plan, hipS
   return NBODY_OK;
 }
 
-template <typename T, int D, int R, int JS>
-static int launch_all_pairs(const nbody_state* s, hipStream_t st) {
+template <typename T, int D, int R, int JS, bool SOFT>
+static int launch_all_pairs(const nbody_state* s, hipStream_t st, T e2) {
   constexpr int TB = (kWaves / JS) * 64 * R;
   uint32_t blocks  = (s->count + TB - 1) / TB;
   if (blocks == 0) return NBODY_OK;
+  if constexpr (SOFT) {  // nothing to prepare: no packed records, no pair rule
+    hipLaunchKernelGGL((all_pairs_softened_kernel<T, D, R, JS>), dim3(blocks), dim3(kBlock), 0, st, static_cast<const T*>(s->m),
+                       static_cast<const T*>(s->x), static_cast<T*>(s->a), static_cast<T>(s->c), s->sz, s->first, s->count, e2);
+    NB_HIP(hipGetLastError());
+    return NBODY_OK;
+  }
   const k1_rule* rule = nullptr;  // the same per-pair rule as the scalar-stream form (bitwise the same result)
   if (int r = ap_prepare<T, D>(s, st, false, nullptr, &rule, nullptr, 0)) return r;
   hipLaunchKernelGGL((all_pairs_force_kernel<T, D, R, JS>), dim3(blocks), dim3(kBlock), 0, st, static_cast<const T*>(s->m),
@@ -869,14 +604,16 @@ static bool with_k1_instance(const k1_plan& p, F&& fn) {
   return false;
 }
 
-template <typename T, int D>
-static int all_pairs_dispatch(const nbody_state* s, hipStream_t st) {
+// SOFT: the softened K1 (e2 > 0) on the same launch plan — the same slices, chunks and hand-off, so the same rounding structure
+template <typename T, int D, bool SOFT = false>
+static int all_pairs_dispatch(const nbody_state* s, hipStream_t st, T e2 = T(0)) {
   k1_plan p;
   if (int rc = plan_all_pairs<T>(s, &p)) return rc;
   int rc = NBODY_OK;
   const bool found = with_k1_instance(p, [&](auto r, auto js) {
     constexpr int R = decltype(r)::value, JS = decltype(js)::value;
-    rc = p.scalar ? launch_all_pairs_sgpr<T, D, R, JS>(s, p, st) : (JS <= kWaves ? launch_all_pairs<T, D, R, (JS <= kWaves ? JS : 1)>(s, st) : int(NBODY_ERR_ARG));
+    rc = p.scalar ? launch_all_pairs_sgpr<T, D, R, JS, SOFT>(s, p, st, e2)
+                  : (JS <= kWaves ? launch_all_pairs<T, D, R, (JS <= kWaves ? JS : 1), SOFT>(s, st, e2) : int(NBODY_ERR_ARG));
   });
   if (!found) {
     set_error("all-pairs: unsupported config split=%d targets_per_thread=%d", p.js, p.r);
@@ -1651,6 +1388,18 @@ extern "C" int nbody_all_pairs_force(const nbody_state* s, void* stream) {
   return dispatch(s->dtype, s->dim, [&](auto tg) {
     using TG = decltype(tg);
     return all_pairs_dispatch<typename TG::type, TG::dim>(s, as_stream(stream));
+  });
+}
+
+extern "C" int nbody_all_pairs_softened_force(const nbody_state* s, double eps, void* stream) {
+  if (int r = check_state(s)) return r;
+  return dispatch(s->dtype, s->dim, [&](auto tg) {
+    using TG = decltype(tg);
+    using T  = typename TG::type;
+    T e2;
+    if (int r = check_softening<T>(eps, &e2)) return r;
+    device_guard guard(stream_device(as_stream(stream)));
+    return all_pairs_dispatch<T, TG::dim, true>(s, as_stream(stream), e2);
   });
 }
 

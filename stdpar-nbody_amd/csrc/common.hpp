@@ -458,6 +458,70 @@ __device__ __forceinline__ void pair_batch(T (&acc)[R][D], const T (&xi)[R][D], 
   }
 }
 
+// ---- softened pairs (ABI 2.4: nbody_all_pairs_softened_force, the softened octree walk and energies) -----------------------
+// Plummer softening: the pair term is  m_j * (x_j - x_i) / (r2 + e2)^(3/2),  e2 = fl_T(eps * eps) > 0, with r2 + e2 built by the
+// same FMA chain the unsoftened kernels use, seeded with e2 where they seed `tiny`.  q = r2 + e2 >= e2 never reaches 0, so there is
+// no eps term, no near-pair branch and no pair rule: the self pair and coincident bodies add w * 0 = 0 because their difference is 0.
+//   f64: weight_far<false> above, (m y^3)(1 + e(3/2 + 15/8 e)), y = v_rsq_f64(q): 7 full-rate ops + 1 transcendental, <= 2.5 ulp.
+//   f32: m y^3 from the 1-ulp v_rsq_f32: 3 ops + 1 transcendental, <= ~3 ulp.
+// y^3 = q^(-3/2) must stay finite for q = e2, which bounds e2 from below (check_softening: kSoftMinE2).
+template <typename T>
+__device__ __forceinline__ T soft_weight(T q, T mj, const pair_consts<T>& pc) {
+  if constexpr (sizeof(T) == 8) {
+    return pair_math<double>::template weight_far<false>(q, mj, pc.k15, pc.k1875);
+  } else {
+    const T y = __builtin_amdgcn_rsqf(q);
+    return mj * ((y * y) * y);
+  }
+}
+
+// K1's unit of work in the softened form: U source records against the R targets of a lane, stage by stage like pair_batch.
+template <typename T, int D, int R, int U>
+__device__ __forceinline__ void pair_batch_soft(T (&acc)[R][D], const T (&xi)[R][D], const src_rec<T, D> (&s)[U],
+                                                const pair_consts<T>& pc, T e2) {
+  T d[U][R][D], q[U][R], w[U][R];
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+#pragma unroll
+      for (int k = 0; k < D; ++k) d[u][r][k] = s[u].p[k] - xi[r][k];
+      T t = e2;
+#pragma unroll
+      for (int k = 0; k < D; ++k) t = __builtin_elementwise_fma(d[u][r][k], d[u][r][k], t);
+      q[u][r] = t;
+    }
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+#pragma unroll
+    for (int r = 0; r < R; ++r) w[u][r] = soft_weight<T>(q[u][r], s[u].m, pc);
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+      for (int k = 0; k < D; ++k) acc[r][k] = __builtin_elementwise_fma(w[u][r], d[u][r][k], acc[r][k]);
+}
+
+// The smallest e2 a softened call accepts: e2^(-3/2) <= 2^126 (f32) / 2^1020 (f64), so that y^3 (and the potential's y) of the
+// closest possible pair is finite and a coincident pair adds 0 * finite = 0.  eps >= 1.5e-13 in float, >= 1.4e-103 in double.
+template <typename T>
+constexpr T kSoftMinE2 = sizeof(T) == 4 ? T(0x1p-84f) : T(0x1p-680);
+
+// eps of a softened call -> e2 = fl_T(T(eps) * T(eps)); NBODY_ERR_ARG (no GPU needed) unless eps is finite and > 0 and e2 is a
+// normal number of T no smaller than kSoftMinE2<T>.
+template <typename T>
+inline int check_softening(double eps, T* e2_out) {
+  NB_ARG(eps > 0.0 && eps <= DBL_MAX, "softening length eps = %g must be finite and > 0", eps);
+  const T te = T(eps);
+  const T e2 = te * te;
+  NB_ARG(e2 >= kSoftMinE2<T> && e2 <= (sizeof(T) == 4 ? T(FLT_MAX) : T(DBL_MAX)),
+         "softening length eps = %g: eps^2 = %g in %s is outside [%g, max]: its square must be a normal number whose ^(-3/2) is finite",
+         eps, double(e2), sizeof(T) == 4 ? "float" : "double", double(kSoftMinE2<T>));
+  *e2_out = e2;
+  return NBODY_OK;
+}
+
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 // ---- which per-pair rule a launch takes: ap_far_mode ---------------------------------------------------------------------

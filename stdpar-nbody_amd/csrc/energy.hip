@@ -14,6 +14,10 @@
 //        (m_i^2 / eps): it always lands in the near path (r2 = 0), where it is removed by comparing the body indices.
 //        Coincident DISTINCT bodies keep the reference's m_i m_j / eps.
 // Against the reference's sequential sums the result agrees to rounding (tolerance parity).  Bound: FP64/FP32 VALU issue.
+// Softened (nbody_calc_energies_softened, e2 = eps^2 > 0): potential = -0.5 * c * sum_i m_i * sum_{j != i} m_j / sqrt(|x_i - x_j|^2 + e2),
+// the potential whose gradient is the softened force.  q = r2 + e2 (the FMA chain seeded with e2) is never small, so every pair
+// takes one form — m_j y (1 + e/2 + 3/8 e^2) in f64 (6 ops + rsq), m_j y in f32 — and the self pair, which is m_i / eps here
+// and not 0, is removed by comparing the body indices in every pair (one compare and select).  The kinetic part is unchanged.
 #include "common.hpp"
 
 namespace nbody {
@@ -114,68 +118,62 @@ __device__ __forceinline__ void pot_batch(T (&acc)[R], const T (&xi)[R][D], cons
     for (int r = 0; r < R; ++r) acc[r] += w[u][r];
 }
 
-// sums[chunk][i] = sum over the chunk's sources j != i of m_j / (|x_i - x_j| + eps)
+// The softened pair: U source records against the R targets of a lane, acc[r] += m_j / sqrt(q), q = |x_i - x_j|^2 + e2, j != i
+template <typename T, int D, int R, int U>
+__device__ __forceinline__ void pot_batch_soft(T (&acc)[R], const T (&xi)[R][D], const uint32_t (&tg)[R], const src_rec<T, D> (&s)[U],
+                                               uint32_t j0, const pot_consts<T>& pc, T e2) {
+  T q[U][R], w[U][R];
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      T t = e2;
+#pragma unroll
+      for (int k = 0; k < D; ++k) {
+        const T d = s[u].p[k] - xi[r][k];
+        t         = __builtin_elementwise_fma(d, d, t);
+      }
+      q[u][r] = t;
+    }
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      T v;
+      if constexpr (sizeof(T) == 8) {  // y (1 + e/2 + 3/8 e^2), e = 1 - q y^2: the 2^-24 seed to third order
+        const T y  = __builtin_amdgcn_rsq(q[u][r]);
+        const T e  = __builtin_fma(-q[u][r], y * y, 1.0);
+        const T p  = __builtin_fma(e, pc.k0375, 0.5);
+        const T my = s[u].m * y;
+        v          = __builtin_fma(my, p * e, my);
+      } else {
+        v = s[u].m * __builtin_amdgcn_rsqf(q[u][r]);
+      }
+      w[u][r] = (j0 + uint32_t(u) == tg[r]) ? T(0) : v;  // the self pair, by index
+    }
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+#pragma unroll
+    for (int r = 0; r < R; ++r) acc[r] += w[u][r];
+}
+
+// sums[chunk][i] = sum over the chunk's sources j != i of m_j / (|x_i - x_j| + eps); softened: of m_j / sqrt(|x_i - x_j|^2 + e2)
 template <typename T, int D, int R>
 __global__ __launch_bounds__(64 * kPotJS) void potential_sgpr_kernel(const src_rec<T, D>* __restrict__ packed, const T* __restrict__ x,
                                                                      T* __restrict__ sums, uint32_t sz, uint32_t tiles_per_chunk) {
-  using rec_t       = src_rec<T, D>;
-  constexpr int TB  = 64 * R;
-  constexpr int SUB = kTileJ / kPotJS;
-  __shared__ T partial[(kPotJS - 1) * 64 * R];
-  const int lane  = threadIdx.x & 63;
-  const int jpart = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  T xi[R][D], acc[R];
-  uint32_t tg[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    tg[r]            = blockIdx.x * TB + r * 64 + lane;
-    const uint64_t i = tg[r] < sz ? tg[r] : 0u;  // clamp: out-of-range lanes compute, never store
-#pragma unroll
-    for (int k = 0; k < D; ++k) xi[r][k] = x[i * D + k];
-    acc[r] = T(0);
-  }
-  const uint32_t ntiles = (sz + kTileJ - 1) / kTileJ;
-  const uint32_t t0     = blockIdx.y * tiles_per_chunk;
-  const uint32_t t1     = min(ntiles, t0 + tiles_per_chunk);
-  const pot_consts<T> pc;
-  const uint32_t nsteps = (t1 - t0) * SUB;
-  constexpr int U       = 64 / int(sizeof(rec_t));
-  struct batch_t {
-    rec_t r[U];
-  };
-  auto index = [&](uint32_t k) { return (t0 + k / SUB) * uint32_t(kTileJ) + uint32_t(jpart) * SUB + (k % SUB); };
-  auto batch = [&](uint32_t k) { return packed + uint64_t(index(k)); };
-  // the same two-deep SMEM pipeline as all_pairs_force_sgpr_kernel (see there)
-  sgpr16 A = sload16(batch(0), xi[0][0]), B;
-  for (uint32_t k = 0; k < nsteps; k += 2 * U) {
-    swait(A, acc[0]);
-    B = sload16(batch(k + U), xi[0][0]);
-    {
-      const batch_t ba = __builtin_bit_cast(batch_t, A);
-      pot_batch<T, D, R, U>(acc, xi, tg, ba.r, index(k), pc);
-    }
-    swait(B, acc[0]);
-    A = sload16(batch(k + 2 * U < nsteps ? k + 2 * U : k), xi[0][0]);
-    {
-      const batch_t bb = __builtin_bit_cast(batch_t, B);
-      pot_batch<T, D, R, U>(acc, xi, tg, bb.r, index(k + U), pc);
-    }
-  }
-  swait(A, acc[0]);
-  if (jpart > 0) {
-#pragma unroll
-    for (int r = 0; r < R; ++r) partial[((jpart - 1) * R + r) * 64 + lane] = acc[r];
-  }
-  __syncthreads();
-  if (jpart == 0) {
-#pragma unroll
-    for (int p = 1; p < kPotJS; ++p)
-#pragma unroll
-      for (int r = 0; r < R; ++r) acc[r] += partial[((p - 1) * R + r) * 64 + lane];
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-      if (tg[r] < sz) sums[uint64_t(blockIdx.y) * sz + tg[r]] = acc[r];
-  }
+  [[maybe_unused]] constexpr T e2 = T(0);
+#define POT_SOFT false
+#include "potential_body.inc"
+#undef POT_SOFT
+}
+// (its name contains potential_sgpr_kernel: tools/check_smem_pipeline.py holds it to the hand-written block's rules)
+template <typename T, int D, int R>
+__global__ __launch_bounds__(64 * kPotJS) void softened_potential_sgpr_kernel(const src_rec<T, D>* __restrict__ packed,
+                                                                              const T* __restrict__ x, T* __restrict__ sums, uint32_t sz,
+                                                                              uint32_t tiles_per_chunk, T e2) {
+#define POT_SOFT true
+#include "potential_body.inc"
+#undef POT_SOFT
 }
 
 template <typename T>
@@ -231,8 +229,8 @@ __global__ __launch_bounds__(kEB) void energy_final_kernel(const T* __restrict__
   }
 }
 
-template <typename T, int D>
-static int energies_run(const nbody_state* s, void* ke_out, void* pe_out, hipStream_t st) {
+template <typename T, int D, bool SOFT = false>
+static int energies_run(const nbody_state* s, void* ke_out, void* pe_out, hipStream_t st, T e2 = T(0)) {
   constexpr int R       = sizeof(T) == 8 ? 2 : 1;
   const uint32_t n      = s->sz;
   const uint32_t ntiles = (n + kTileJ - 1) / kTileJ;
@@ -248,8 +246,12 @@ static int energies_run(const nbody_state* s, void* ke_out, void* pe_out, hipStr
   T* out     = partial + 2 * size_t(nblk);
   void* packed = nullptr;
   if (int r = ap_pack_sources(s, st, &packed)) return r;
-  hipLaunchKernelGGL((potential_sgpr_kernel<T, D, R>), dim3((n + 64 * R - 1) / (64 * R), chunks), dim3(64 * kPotJS), 0, st,
-                     static_cast<const src_rec<T, D>*>(packed), static_cast<const T*>(s->x), sums, n, tpc);
+  if constexpr (SOFT)
+    hipLaunchKernelGGL((softened_potential_sgpr_kernel<T, D, R>), dim3((n + 64 * R - 1) / (64 * R), chunks), dim3(64 * kPotJS), 0, st,
+                       static_cast<const src_rec<T, D>*>(packed), static_cast<const T*>(s->x), sums, n, tpc, e2);
+  else
+    hipLaunchKernelGGL((potential_sgpr_kernel<T, D, R>), dim3((n + 64 * R - 1) / (64 * R), chunks), dim3(64 * kPotJS), 0, st,
+                       static_cast<const src_rec<T, D>*>(packed), static_cast<const T*>(s->x), sums, n, tpc);
   NB_HIP(hipGetLastError());
   hipLaunchKernelGGL((energy_partial_kernel<T, D>), dim3(nblk), dim3(kEB), 0, st, static_cast<const T*>(s->m),
                      static_cast<const T*>(s->v), sums, chunks, n, partial);
@@ -277,5 +279,20 @@ extern "C" int nbody_calc_energies(const nbody_state* s, void* kinetic_out, void
   return dispatch(s->dtype, s->dim, [&](auto tg) {
     using TG = decltype(tg);
     return energies_run<typename TG::type, TG::dim>(s, kinetic_out, potential_out, as_stream(stream));
+  });
+}
+
+extern "C" int nbody_calc_energies_softened(const nbody_state* s, double eps, void* kinetic_out, void* potential_out, void* stream) {
+  if (int r = check_state(s)) return r;
+  NB_ARG(kinetic_out && potential_out, "NULL output pointer");
+  NB_ARG(s->first == 0 && s->count == s->sz, "nbody_calc_energies_softened needs the whole system (first=0, count=sz)");
+  NB_ARG(s->sz >= 1, "empty system");
+  return dispatch(s->dtype, s->dim, [&](auto tg) {
+    using TG = decltype(tg);
+    using T  = typename TG::type;
+    T e2;
+    if (int r = check_softening<T>(eps, &e2)) return r;
+    device_guard guard(stream_device(as_stream(stream)));
+    return energies_run<T, TG::dim, true>(s, kinetic_out, potential_out, as_stream(stream), e2);
   });
 }

@@ -1737,6 +1737,21 @@ __device__ __forceinline__ void ot_accumulate(bool on, uint64_t on_mask, T (&acc
   for (int k = 0; k < D; ++k) acc[k] = __builtin_elementwise_fma(w, dj[k], acc[k]);
 }
 
+// The softened accepted term (nbody_octree_compute_softened_force): a += mj * (xj - x) / (d2 + e2)^(3/2), for the lanes in `on`.
+// q = d2 + e2 is its own FMA chain seeded with e2 (the opening test keeps the unsoftened d2f and its seed y0, bit for bit the
+// reference's decision), so the term pays one more rsq and D FMAs; in exchange there is no eps term and no near path — q >= e2 —
+// and the body's own leaf and empty leaves still add exactly 0 (dj == 0 or mj == 0).  Weight: common.hpp soft_weight (K1's).
+template <typename T, int D>
+__device__ __forceinline__ void ot_accumulate_soft(bool on, T (&acc)[D], const T (&dj)[D], T mj, T e2, const pair_consts<T>& pc) {
+  T q = e2;
+#pragma unroll
+  for (int k = 0; k < D; ++k) q = __builtin_elementwise_fma(dj[k], dj[k], q);
+  T w = soft_weight<T>(q, mj, pc);
+  w   = on ? w : T(0);
+#pragma unroll
+  for (int k = 0; k < D; ++k) acc[k] = __builtin_elementwise_fma(w, dj[k], acc[k]);
+}
+
 // Shard windows.  The walk takes bodies in key order, the window [first, first + count) is a range of BODY indices, so the
 // owned bodies are scattered over the key order: they are compacted (order kept) into a dense list first, otherwise every
 // wave would carry one owned body among 2^(6-D) and a 1/G shard would cost as much as the whole system.
@@ -1807,101 +1822,28 @@ __global__ __launch_bounds__(kOC) void ot_owned_scatter_kernel(const uint32_t* _
 // the 2^D partial sums are combined at the end in a fixed order: the summation order differs from the reference's
 // (tolerance parity), the set of tests, accepted terms and therefore the counters do not, and the result of a body
 // depends on nothing but the tree and that body (so it is independent of the shard window).
+// ot_force_softened_kernel: the walk of nbody_octree_compute_softened_force — the same tests in the same order, the accepted term
+// ot_accumulate_soft.
 template <typename T, int D, bool COUNT>
 __global__ __launch_bounds__(64) void ot_force_kernel(const ot_node<T>* __restrict__ rootrec, const ot_group<T, D>* __restrict__ groups,
                                                       const uint32_t* __restrict__ list,
                                                       uint32_t nlist, const T* __restrict__ x, T* __restrict__ a, T c,
                                                       uint32_t first, T theta, uint32_t capacity, const T* __restrict__ root,
                                                       uint32_t* __restrict__ flags, uint32_t* __restrict__ counters) {
-  constexpr uint32_t NCH   = 1u << D;
-  constexpr uint32_t GPW   = 64u / NCH;                         // bodies per wave
-  constexpr uint32_t DEPTH = (NCH - 1u) * kMaxLevels<D> + NCH;  // a pop frees one slot, an open adds <= 2^D
-  __shared__ uint32_t stack[GPW][DEPTH];
-  const uint32_t g = threadIdx.x / NCH, cc = threadIdx.x % NCH;
-  // `list`: the owned bodies in key order (neighbours share most of their walk: cache); XCD-contiguous blocks
-  const uint32_t t    = ot_xcd_contiguous_block(blockIdx.x, gridDim.x) * GPW + g;
-  const bool valid    = t < nlist;
-  const uint32_t body = valid ? list[t] : first;
-  const ot_theta<T> th(theta);
-  const pair_consts<T> pc;
-  const T root_side = root[D];
-  T xi[D], acc[D];
-#pragma unroll
-  for (int k = 0; k < D; ++k) {
-    xi[k]  = valid ? x[uint64_t(body) * D + k] : T(0);
-    acc[k] = T(0);
-  }
-  uint32_t c_nodes = 0, c_terms = 0;
-  uint32_t cur = 0, sp = 0;
-  bool more = false;
-  if (valid) {  // the root is examined alone (by every lane of the group; lane 0 keeps the result)
-    const ot_node<T> nd = *rootrec;
-    T di[D];
-#pragma unroll
-    for (int k = 0; k < D; ++k) di[k] = nd.p[k] - xi[k];
-    const T d2f     = ot_dist2_fused<T, D>(di);
-    const T y0      = ot_rsq(d2f);
-    const bool leaf = nd.fc >= kOtBody;  // kOtBody or kOtEmpty
-    const bool take = leaf || ot_accept<T, D>(!leaf, root_side, di, y0, th);
-    {
-      const bool on0 = take && cc == 0;  // the root is examined by every lane of the group; lane 0 keeps the result
-      const uint64_t m0 = __builtin_amdgcn_ballot_w64(on0);
-      if (m0 != 0ull) ot_accumulate<T, D>(on0, m0, acc, di, nd.m, d2f, y0, pc);
-    }
-    if (COUNT && cc == 0) {
-      c_nodes = 1;
-      c_terms = take;
-    }
-    more = !take;
-    cur  = nd.fc;  // the root's stored fc is already a sibling-group number, like every fl[][0] below
-  }
-  uint32_t guard = capacity;  // a well-formed tree is left after < capacity steps; never spin on a damaged one
-  while (more && guard-- != 0u) {  // the lanes of a group leave together
-    const ot_node<T> nd = groups[cur].load(cc);  // this lane's child: two or three 16-/8-byte loads
-    T di[D];
-#pragma unroll
-    for (int k = 0; k < D; ++k) di[k] = nd.p[k] - xi[k];
-    const T d2f     = ot_dist2_fused<T, D>(di);
-    const T y0      = ot_rsq(d2f);
-    const bool leaf = nd.fc >= kOtBody;
-    const bool take = leaf || ot_accept<T, D>(!leaf, ot_ldexp(root_side, -int(nd.lvl)), di, y0, th);
-    if (COUNT) {
-      ++c_nodes;
-      c_terms += take;
-    }
-    const uint64_t take_mask = __builtin_amdgcn_ballot_w64(take);
-    if (take_mask != 0ull) ot_accumulate<T, D>(take, take_mask, acc, di, nd.m, d2f, y0, pc);
-    const uint32_t open_mask = uint32_t((__ballot(!take) >> (g * NCH)) & ((1ull << NCH) - 1ull));
-    if (sp + uint32_t(__builtin_popcount(open_mask)) > DEPTH) {  // only below the key depth can a walk hold this many
-      if (cc == 0) atomicOr(flags, kFlagStack);                  // pending nodes; reported by nbody_octree_info
-      break;
-    }
-    if (!take) stack[g][sp + uint32_t(__builtin_popcount(open_mask >> (cc + 1u)))] = nd.fc;  // reverse child order
-    sp += uint32_t(__builtin_popcount(open_mask));
-    if (sp == 0u) break;
-    __builtin_amdgcn_wave_barrier();  // one lane pushed, all lanes of the group pop: keep the LDS write before the read
-    cur = stack[g][--sp];
-    __builtin_amdgcn_wave_barrier();  // ... and this read before the next round's push into the same slot
-  }
-  if (more && guard == 0xffffffffu && cc == 0) atomicOr(flags, kFlagWalk);  // step budget spent: the tree is damaged
-  // combine the 2^D partial sums of a body (fixed order)
-#pragma unroll
-  for (uint32_t off = NCH / 2; off > 0; off >>= 1) {
-#pragma unroll
-    for (int k = 0; k < D; ++k) acc[k] += __shfl_xor(acc[k], int(off), 64);
-    if (COUNT) {
-      c_nodes += __shfl_xor(c_nodes, int(off), 64);
-      c_terms += __shfl_xor(c_terms, int(off), 64);
-    }
-  }
-  if (valid && cc == 0) {
-#pragma unroll
-    for (int k = 0; k < D; ++k) a[uint64_t(body - first) * D + k] = c * acc[k];
-    if (COUNT) {
-      counters[uint64_t(body) * 2 + 0] = c_nodes;
-      counters[uint64_t(body) * 2 + 1] = c_terms;
-    }
-  }
+  [[maybe_unused]] constexpr T e2 = T(0);
+#define OT_SOFT false
+#include "ot_walk_body.inc"
+#undef OT_SOFT
+}
+template <typename T, int D, bool COUNT>
+__global__ __launch_bounds__(64) void ot_force_softened_kernel(const ot_node<T>* __restrict__ rootrec,
+                                                               const ot_group<T, D>* __restrict__ groups, const uint32_t* __restrict__ list,
+                                                               uint32_t nlist, const T* __restrict__ x, T* __restrict__ a, T c,
+                                                               uint32_t first, T theta, uint32_t capacity, const T* __restrict__ root,
+                                                               uint32_t* __restrict__ flags, uint32_t* __restrict__ counters, T e2) {
+#define OT_SOFT true
+#include "ot_walk_body.inc"
+#undef OT_SOFT
 }
 
 // the accepted term's weight for d2 >= 2^-46 (ot_accumulate's far form, same operations in the same order); v[60:61] = mass
@@ -2646,8 +2588,14 @@ static int ot_tree_run(nbody_octree* t, hipStream_t st) {
   return NBODY_OK;
 }
 
+// soft: the softened walk (e2 > 0), which exists in the compiler-scheduled form only
 template <typename T, int D>
-static int ot_force_run(nbody_octree* t, const nbody_state* s, double theta, hipStream_t st) {
+static int ot_force_run(nbody_octree* t, const nbody_state* s, double theta, hipStream_t st, bool soft = false, T e2 = T(0)) {
+  if (soft && t->walk == 2) {
+    set_error("octree walk: the softened walk exists in the compiler-scheduled form only (walk form 1 or 0 = auto), not as the ISA "
+              "visit round set by nbody_octree_set_walk(t, 2)");
+    return NBODY_ERR_ARG;
+  }
   if (s->count == 0) return NBODY_OK;
   const uint32_t* list = t->idx[t->sorted_buf];  // whole system: the sorted body indices themselves
   if (s->count < s->sz) {                        // shard window: compact the owned ones (scratch: the sort's other buffers)
@@ -2671,6 +2619,19 @@ static int ot_force_run(nbody_octree* t, const nbody_state* s, double theta, hip
                      static_cast<const T*>(s->x), static_cast<T*>(s->a), static_cast<T>(s->c), s->first,                     \
                      static_cast<T>(theta), budget, static_cast<const T*>(t->root),                                        \
                      t->lvl_count + ((D == 3 ? kMaxLevels<3> : kMaxLevels<2>) + 2), t->counters)
+  if (soft) {
+#define NB_OT_SOFT(CNT)                                                                                                      \
+  hipLaunchKernelGGL((ot_force_softened_kernel<T, D, CNT>), dim3(blocks), dim3(64), 0, st, rootrec,                          \
+                     static_cast<const ot_group<T, D>*>(t->groups), list, s->count,                                          \
+                     static_cast<const T*>(s->x), static_cast<T*>(s->a), static_cast<T>(s->c), s->first,                     \
+                     static_cast<T>(theta), budget, static_cast<const T*>(t->root),                                        \
+                     t->lvl_count + ((D == 3 ? kMaxLevels<3> : kMaxLevels<2>) + 2), t->counters, e2)
+    if (t->counters_on) NB_OT_SOFT(true);
+    else NB_OT_SOFT(false);
+#undef NB_OT_SOFT
+    NB_HIP(hipGetLastError());
+    return NBODY_OK;
+  }
   // the visit round written as ISA (ot_force_isa_kernel, ot_force_isa_f32_kernel; 2D and 3D), while 24-bit group numbers times the group
   // size stay inside 32-bit offsets; nbody_octree_set_walk(t, 1) keeps the compiler-scheduled kernel (tests compare the two bitwise)
   bool isa = false;
@@ -2913,6 +2874,30 @@ extern "C" int nbody_octree_compute_force(nbody_octree* t, const nbody_state* s,
   return dispatch(s->dtype, s->dim, [&](auto tg) {
     using TG = decltype(tg);
     return ot_force_run<typename TG::type, TG::dim>(t, s, theta, as_stream(stream));
+  });
+}
+
+extern "C" int nbody_octree_compute_softened_force(nbody_octree* t, const nbody_state* s, double theta, double eps, void* stream) {
+  NB_ARG(t != nullptr, "nbody_octree is NULL");
+  if (int r = check_state(s)) return r;
+  int r = dispatch(s->dtype, s->dim, [&](auto tg) {
+    using T = typename decltype(tg)::type;
+    T e2;
+    return check_softening<T>(eps, &e2);
+  });
+  if (r) return r;
+  if (int r2 = ot_check(t, s, stream)) return r2;
+  device_guard guard(t->device);
+  if (!t->have_tree) {
+    set_error("nbody_octree_compute_softened_force before nbody_octree_compute_tree");
+    return NBODY_ERR_STATE;
+  }
+  return dispatch(s->dtype, s->dim, [&](auto tg) {
+    using TG = decltype(tg);
+    using T  = typename TG::type;
+    T e2;
+    (void)check_softening<T>(eps, &e2);
+    return ot_force_run<T, TG::dim>(t, s, theta, as_stream(stream), true, e2);
   });
 }
 

@@ -84,6 +84,10 @@ class Device {
   void all_pairs_force() {
     for (std::size_t g = 0; g < ctx_.size(); ++g) backend_check(nbody_all_pairs_force(&view_[g], stream(g)), "nbody_all_pairs_force");
   }
+  void all_pairs_softened_force(double eps) {
+    for (std::size_t g = 0; g < ctx_.size(); ++g)
+      backend_check(nbody_all_pairs_softened_force(&view_[g], eps, stream(g)), "nbody_all_pairs_softened_force");
+  }
   void all_pairs_collapsed_force() {
     single("all-pairs-collapsed");
     backend_check(nbody_all_pairs_collapsed_force(&view_[0], stream()), "nbody_all_pairs_collapsed_force");
@@ -99,10 +103,12 @@ class Device {
   }
 
   // System::calc_energies (src/system.h:62-79) on the device: {kinetic, potential}
-  std::pair<T, T> calc_energies() {
+  // softening > 0: the potential of the softened force (nbody_calc_energies_softened)
+  std::pair<T, T> calc_energies(double softening = 0.0) {
     single("--save energy");
     T ke{}, pe{};
-    backend_check(nbody_calc_energies(&view_[0], &ke, &pe, stream()), "nbody_calc_energies");
+    if (softening > 0.0) backend_check(nbody_calc_energies_softened(&view_[0], softening, &ke, &pe, stream()), "nbody_calc_energies_softened");
+    else backend_check(nbody_calc_energies(&view_[0], &ke, &pe, stream()), "nbody_calc_energies");
     return {ke, pe};
   }
 
@@ -137,8 +143,11 @@ class Device {
   void octree_compute_bounds() { backend_check(nbody_octree_compute_bounds(octree_, &view_[0], stream()), "nbody_octree_compute_bounds"); }
   void octree_insert() { backend_check(nbody_octree_insert(octree_, &view_[0], stream()), "nbody_octree_insert"); }
   void octree_compute_tree() { backend_check(nbody_octree_compute_tree(octree_, stream()), "nbody_octree_compute_tree"); }
-  void octree_compute_force(double theta) {
-    backend_check(nbody_octree_compute_force(octree_, &view_[0], theta, stream()), "nbody_octree_compute_force");
+  void octree_compute_force(double theta, double softening = 0.0) {
+    if (softening > 0.0)
+      backend_check(nbody_octree_compute_softened_force(octree_, &view_[0], theta, softening, stream()),
+                    "nbody_octree_compute_softened_force");
+    else backend_check(nbody_octree_compute_force(octree_, &view_[0], theta, stream()), "nbody_octree_compute_force");
   }
   // {tree size, total mass}; also where device-side build errors (depth limit, node pool) surface
   std::pair<std::uint32_t, T> octree_info() {

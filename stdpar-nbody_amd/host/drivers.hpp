@@ -43,7 +43,11 @@ void run_all_pairs(System<T, D>& sys, Device<T, D>& dev, Options o, char const* 
   csv_total_guard(o);
   if (o.csv_total) std::cout << "algorithm,dim,precision,nsteps,nbodies,total [s]\n";  // detailed prints no header here
 
-  auto force = [&] { collapsed ? dev.all_pairs_collapsed_force() : dev.all_pairs_force(); };
+  auto force = [&] {
+    if (collapsed) dev.all_pairs_collapsed_force();
+    else if (o.softening > 0.0) dev.all_pairs_softened_force(o.softening);
+    else dev.all_pairs_force();
+  };
   seconds_t t_force(0), t_accel(0), t_total(0);
   if (o.csv_detailed) {
     t_total = timed([&] {
@@ -163,7 +167,7 @@ void run_octree(System<T, D>& sys, Device<T, D>& dev, Options o) {
           t_bbox += timed([&] { dev.octree_compute_bounds(); dev.sync(); });
           t_insert += timed([&] { dev.octree_insert(); dev.sync(); });
           t_tree += timed([&] { dev.octree_compute_tree(); dev.sync(); });
-          t_walk += timed([&] { dev.octree_compute_force(theta); dev.sync(); });
+          t_walk += timed([&] { dev.octree_compute_force(theta, o.softening); dev.sync(); });
         });
         t_accel += timed([&] { dev.accelerate_step(); dev.sync(); });
         auto [size, mass] = dev.octree_info();  // also reports a build that hit the depth limit / node pool
@@ -181,7 +185,7 @@ void run_octree(System<T, D>& sys, Device<T, D>& dev, Options o) {
       dev.octree_compute_bounds();
       dev.octree_insert();
       dev.octree_compute_tree();
-      dev.octree_compute_force(theta);
+      dev.octree_compute_force(theta, o.softening);
       dev.accelerate_step();
     };
     one_step();  // the phase-order checks of the ABI need one direct pass before the sequence is recorded

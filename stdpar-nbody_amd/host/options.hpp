@@ -1,5 +1,6 @@
 // Command line of the reference binary (src/arguments.h): same flags, defaults, help and error text.
 #pragma once
+#include <cmath>
 #include <cstdlib>
 #include <iostream>
 #include <optional>
@@ -30,6 +31,9 @@ struct Options {
   // the bodies of --algorithm all-pairs over N devices of this node, one RCCL all-gather of positions per step
   int gpus = 1;
   bool gpus_given = false;  // an explicit --gpus N (any N, also 1) takes the sharded path: communicator, shard windows, exchange
+  // not in the reference either (nor in --help): --softening EPS, Plummer softening length for all-pairs (also under --gpus N),
+  // octree and --save energy; 0 = off, the same run as without the flag
+  double softening = 0.0;
 };
 
 namespace detail {
@@ -96,6 +100,15 @@ inline Options parse_options(std::vector<std::string> const& argv) {
         std::cerr << "--gpus needs a positive device count." << std::endl;
         std::exit(EXIT_FAILURE);
       }
+    } else if (f == "--softening") {
+      auto const& e = value();
+      char* end     = nullptr;
+      double const v = std::strtod(e.c_str(), &end);
+      if (e.empty() || end != e.c_str() + e.size() || !std::isfinite(v) || v < 0.0) {
+        std::cerr << "--softening needs a finite length >= 0 (0 = off), got \"" << e << "\"." << std::endl;
+        std::exit(EXIT_FAILURE);
+      }
+      o.softening = v;
     } else if (f == "--print-state") {
       o.print_state = true;
     } else if (f == "--print-info") {
@@ -117,6 +130,11 @@ inline Options parse_options(std::vector<std::string> const& argv) {
   }
   if (o.csv_detailed && o.csv_total) {
     std::cerr << "Cannot capture a CSV detailed and coarse trace in the same run. Specify one or the other." << std::endl;
+    std::exit(EXIT_FAILURE);
+  }
+  if (o.softening > 0.0 && (o.algorithm == Algorithm::Bvh || o.algorithm == Algorithm::AllPairsCollapsed)) {
+    std::cerr << "--softening is supported by --algorithm all-pairs and octree only, not by "
+              << (o.algorithm == Algorithm::Bvh ? "bvh" : "all-pairs-collapsed") << "." << std::endl;
     std::exit(EXIT_FAILURE);
   }
   return o;
