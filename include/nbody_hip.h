@@ -77,7 +77,9 @@ typedef struct nbody_state {
  *      the measured forms that are not shipped (traversal 3 / 4 / 6, octree build 2 / 4) are refused by this library.
  * 2.3: nbody_all_pairs_status; nbody_stream_sync / nbody_download return NBODY_ERR_STATE after a failed K1 chunk hand-off;
  *      nbody_all_pairs_pair_rule decides from the positions' variances, not from their bounding box.
- * 2.4: Plummer softening: nbody_all_pairs_softened_force, nbody_calc_energies_softened, nbody_octree_compute_softened_force. */
+ * 2.4: Plummer softening: nbody_all_pairs_softened_force, nbody_calc_energies_softened, nbody_octree_compute_softened_force.
+ *      Additive, same version: octree quadrupole moments, nbody_octree_compute_quadrupoles, nbody_octree_compute_quadrupole_force,
+ *      nbody_octree_read_root_quadrupole. */
 #define NBODY_HIP_ABI_VERSION 2004
 int nbody_abi_version(void);
 
@@ -245,6 +247,22 @@ int nbody_octree_info(nbody_octree* t, uint32_t* tree_size, void* root_mass, voi
 /* Test/diagnostic: per-body {nodes examined, terms accumulated} u32[n][2] of the last compute_force. */
 int nbody_octree_enable_counters(nbody_octree* t, int on);
 int nbody_octree_read_counters(nbody_octree* t, uint32_t* host_out, size_t bytes, void* stream);
+/* Quadrupole moments (no reference counterpart): the next term of the expansion of an accepted cell.  For a cell with centre of mass
+ * p, Q = sum over its children c (child order, empty ones skipped) of Q_c + m_c (3 d d^T - |d|^2 I), d = p_c - p; a body leaf has
+ * Q = 0.  NQ = 6 values in 3D (xx, xy, xz, yy, yz, zz), 3 in 2D (xx, xy, yy: the 3D tensor restricted to the plane, not traceless).
+ * Both build forms give the same Q bit for bit.
+ * compute_quadrupoles: after compute_tree; children before parents, on the stream.  The first call allocates the array (NQ values
+ *   of T per node of the pool: 384 B per body in double 3D), so it must not be recorded: under stream capture it returns
+ *   NBODY_ERR_STATE.
+ * compute_quadrupole_force: compute_force whose accepted cells also add -c (Q d) y^5 + (5/2) c (d^T Q d) d y^7, d = p - x[i],
+ *   y = 1/|d|.  The opening tests, their order, the monopole terms and the counters are compute_force's bit for bit; honours the
+ *   shard window.  The compiler-scheduled walk (form 1) on auto; NBODY_ERR_ARG after nbody_octree_set_walk(t, 2).
+ * read_root_quadrupole: blocking; NQ values of T into host_out.
+ * The last two return NBODY_ERR_STATE unless compute_quadrupoles ran after the latest clear / insert / compute_tree / set_build
+ * (tracked by the host in call order, which a recorded step replays). */
+int nbody_octree_compute_quadrupoles(nbody_octree* t, void* stream);
+int nbody_octree_compute_quadrupole_force(nbody_octree* t, const nbody_state* s, double theta, void* stream);
+int nbody_octree_read_root_quadrupole(nbody_octree* t, void* host_out, void* stream);
 
 /* ---- softening (no reference counterpart: its eps(T) is machine epsilon, a guard against 0 / 0) ------------------------
  * Plummer softening with length eps.  e2 = fl_T(T(eps) * T(eps)); eps must be finite and > 0 and e2 a normal number of T with

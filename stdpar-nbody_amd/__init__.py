@@ -57,6 +57,7 @@ ABI_SYMBOLS = [
     "nbody_comm_rank", "nbody_comm_rccl_version", "nbody_shard_range", "nbody_comm_group_begin", "nbody_comm_group_end",
     "nbody_allgather_positions", "nbody_bvh_opening_thresholds", "nbody_all_pairs_pair_rule", "nbody_all_pairs_status",
     "nbody_all_pairs_softened_force", "nbody_calc_energies_softened", "nbody_octree_compute_softened_force",
+    "nbody_octree_compute_quadrupoles", "nbody_octree_compute_quadrupole_force", "nbody_octree_read_root_quadrupole",
 ]
 ABI_MAJOR = 2
 COMM_ID_BYTES = 128
@@ -358,6 +359,20 @@ class Octree:
         accepted term m d / (|d|^2 + eps^2)^(3/2); the compiler-scheduled walk (refused after set_walk(2))."""
         _check(lib().nbody_octree_compute_softened_force(self.h, C.byref(st), C.c_double(theta), C.c_double(eps), C.c_void_p(stream)))
 
+    def compute_quadrupoles(self, stream=None):
+        """Quadrupole moments of every cell (nbody_octree_compute_quadrupoles); after compute_tree."""
+        _check(lib().nbody_octree_compute_quadrupoles(self.h, C.c_void_p(stream)))
+
+    def compute_quadrupole_force(self, st, theta, stream=None):
+        """compute_force with the quadrupole term of every accepted cell (nbody_octree_compute_quadrupole_force)."""
+        _check(lib().nbody_octree_compute_quadrupole_force(self.h, C.byref(st), C.c_double(theta), C.c_void_p(stream)))
+
+    def read_root_quadrupole(self, stream=None):
+        """The root's quadrupole: xx, xy, xz, yy, yz, zz in 3D, xx, xy, yy in 2D (blocking)."""
+        out = np.zeros(6 if self.dim == 3 else 3, dtype=np_dtype(self.dtype))
+        _check(lib().nbody_octree_read_root_quadrupole(self.h, _p(out), C.c_void_p(stream)))
+        return out
+
     def info(self, stream=None):
         """(tree size = next_free_child_group, root mass); raises if the build hit the depth limit / node pool."""
         size = C.c_uint32()
@@ -486,14 +501,20 @@ class DeviceSystem:
             self._octree = Octree(self.dtype, self.dim, self.n, self.device)
         return self._octree
 
-    def octree_force(self, theta, softening=0.0):
-        """One force phase of run_octree (src/octree.h:321-326); softening > 0 takes the softened walk."""
+    def octree_force(self, theta, softening=0.0, quadrupole=False):
+        """One force phase of run_octree (src/octree.h:321-326); softening > 0 takes the softened walk, quadrupole=True the
+        quadrupole pass and walk (the two do not combine)."""
+        if softening and quadrupole:
+            raise ValueError("octree_force: softening and quadrupole cannot be combined")
         st, t = self.state(), self.octree
         t.clear(self.stream)
         t.compute_bounds(st, self.stream)
         t.insert(st, self.stream)
         t.compute_tree(self.stream)
-        if softening:
+        if quadrupole:
+            t.compute_quadrupoles(self.stream)
+            t.compute_quadrupole_force(st, theta, self.stream)
+        elif softening:
             t.compute_softened_force(st, theta, softening, self.stream)
         else:
             t.compute_force(st, theta, self.stream)

@@ -1846,6 +1846,178 @@ __global__ __launch_bounds__(64) void ot_force_softened_kernel(const ot_node<T>*
 #undef OT_SOFT
 }
 
+// ---- quadrupole moments (nbody_octree_compute_quadrupoles, nbody_octree_compute_quadrupole_force; no reference counterpart) ----
+// Q(cell) = sum over its children c, in child order, empty ones skipped, of Q_c + m_c (3 d d^T - |d|^2 I), d = p_c - p(cell); a body
+// leaf has Q = 0.  2D takes the same formula in the plane (the 3D tensor restricted to z = 0: not traceless, and it need not be).
+// Stored per node beside the tree, node index order (node 0 = the root, node 1 + g * 2^D + c = slot c of sibling group g), kOtNQ<D>
+// values each: xx, xy, xz, yy, yz, zz in 3D, xx, xy, yy in 2D.  Body leaves and empty slots are never written nor read.
+template <int D>
+constexpr int kOtNQ = D == 3 ? 6 : 3;
+
+// One cell, after its monopole and the quadrupoles of its child cells: the same children, the same order and the same operations
+// whichever build form numbered the cells, so both forms give the same bits.
+template <typename T, int D>
+__device__ __forceinline__ void ot_quadrupole_cell(ot_tree<T, D> tree, T* __restrict__ quad, uint32_t node) {
+#pragma clang fp contract(off)
+  constexpr uint32_t NCH = 1u << D;
+  constexpr int NQ       = kOtNQ<D>;
+  const ot_node<T> pn = tree.get(node);
+  if (pn.fc >= kOtBody) return;  // only after an overflow flag
+  T q[NQ];
+#pragma unroll
+  for (int i = 0; i < NQ; ++i) q[i] = T(0);
+  for (uint32_t c = 0; c < NCH; ++c) {
+    const uint32_t ci   = pn.fc + c;
+    const ot_node<T> ch = tree.get(ci);
+    if (ch.fc == kOtEmpty) continue;
+    if (ch.fc != kOtBody) {
+#pragma unroll
+      for (int i = 0; i < NQ; ++i) q[i] += quad[uint64_t(ci) * NQ + i];
+    }
+    T d[D], r2 = T(0);
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      d[k] = ch.p[k] - pn.p[k];
+      r2   = r2 + d[k] * d[k];
+    }
+    int i = 0;
+#pragma unroll
+    for (int u = 0; u < D; ++u) {
+#pragma unroll
+      for (int v = u; v < D; ++v, ++i) {
+        T e = T(3) * d[u] * d[v];
+        if (u == v) e = e - r2;
+        q[i] += ch.m * e;
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NQ; ++i) quad[uint64_t(node) * NQ + i] = q[i];
+}
+
+// build form 1: one launch per level over that level's cell list, deepest first (the lists of ot_multipole_level_kernel)
+template <typename T, int D>
+__global__ __launch_bounds__(kOB) void ot_quadrupole_level_kernel(int level, ot_tree<T, D> tree, T* __restrict__ quad,
+                                                                  const ot_cell* __restrict__ cells, const uint32_t* __restrict__ lvl_count,
+                                                                  uint32_t max_cells) {
+  const uint32_t count = lvl_count[level];
+  const uint32_t k     = blockIdx.x * kOB + threadIdx.x;
+  if (k >= count) return;
+  uint32_t base = 0;
+  for (int j = 0; j < level; ++j) base += lvl_count[j];
+  if (base + k >= max_cells) return;
+  ot_quadrupole_cell<T, D>(tree, quad, cells[base + k].node);
+}
+
+// build form 3: one launch per level over all ranks (the cells of a level are spread over the pre-order ranks)
+template <typename T, int D>
+__global__ __launch_bounds__(kOB) void ot_quadrupole_ranks_level_kernel(int level, ot_tree<T, D> tree, T* __restrict__ quad,
+                                                                        const ot_cell* __restrict__ cells,
+                                                                        const uint32_t* __restrict__ lvl_count, uint32_t capacity,
+                                                                        uint32_t max_cells) {
+  constexpr uint32_t NCH = 1u << D;
+  if (lvl_count[level] == 0) return;
+  uint32_t total = ot_lcp_total<T, D>(lvl_count);
+  if (total > max_cells) total = max_cells;
+  const uint32_t r = blockIdx.x * kOB + threadIdx.x;
+  if (r >= total || 1u + r * NCH + NCH > capacity) return;
+  const ot_cell cl = cells[r];
+  if (int(cl.start) == level) ot_quadrupole_cell<T, D>(tree, quad, cl.node);
+}
+
+// The cells at and below the key depth (ot_build_deep_kernel's), both build forms: one thread per cell of depth kMaxLevels finishes
+// its subtree children first, by a depth-first walk over the stored child links.  The deep build splits no cell of depth
+// kOtDeepLevels or more, so a path holds at most kOtDeepLevels - kMaxLevels cells.
+template <typename T, int D>
+__global__ __launch_bounds__(64) void ot_quadrupole_deep_kernel(ot_tree<T, D> tree, T* __restrict__ quad, const ot_cell* __restrict__ cells,
+                                                                const ot_cell* __restrict__ tops, const uint32_t* __restrict__ lvl_count,
+                                                                uint32_t capacity) {
+  constexpr uint32_t NCH = 1u << D;
+  constexpr int ML       = kMaxLevels<D>;
+  constexpr int kFrames  = kOtDeepLevels - ML + 1;
+  uint32_t base = 0;
+  for (int j = 0; j < ML; ++j) base += lvl_count[j];
+  const uint32_t count = tops ? lvl_count[ML + 5] : lvl_count[ML];
+  if (!tops) tops = cells + base;
+  struct frame {
+    uint32_t node, fc, c;  // the cell, its first child's node index, the next child to look at
+  };
+  frame stack[kFrames];
+  for (uint32_t k = blockIdx.x * 64 + threadIdx.x; k < count; k += gridDim.x * 64) {
+    if (tops == cells + base && base + k >= capacity / NCH + 1u) break;  // as ot_build_deep_body: beyond the list's room
+    const uint32_t top   = tops[k].node;
+    const ot_node<T> tnd = tree.get(top);
+    if (tnd.fc >= kOtBody) continue;  // not split (a flagged build)
+    int sp      = 0;
+    stack[sp++] = frame{top, tnd.fc, 0u};
+    while (sp > 0) {
+      frame& f = stack[sp - 1];
+      if (f.c == NCH) {  // every child cell is finished
+        ot_quadrupole_cell<T, D>(tree, quad, f.node);
+        --sp;
+        continue;
+      }
+      const uint32_t ci   = f.fc + f.c++;
+      const ot_node<T> ch = tree.get(ci);
+      if (ch.fc >= kOtBody) continue;
+      if (sp == kFrames) break;  // cannot happen in a tree the deep build made; never write past the stack
+      stack[sp++] = frame{ci, ch.fc, 0u};
+    }
+  }
+}
+
+// a += -(Q d) y^5 + 5/2 (d^T Q d) d y^7 for the lanes in `on`: the next term of the expansion of an accepted cell about its centre
+// of mass, d = p - x (dj), y = 1 / |d|.  q: the cell's kOtNQ<D> values.  In f64 the seed y0 (2^-24) is polished by one
+// third-order step; in f32 the 1-ulp seed is used as it is.  Evaluated on the unit vector u = d y as
+// ((5/2 (u^T Q u) u - Q u) y^2) y^2: |Q| y^2 is about m theta^2 for an accepted cell, so every intermediate is bounded like the
+// monopole's m y^2 — y^5 or y^7 on their own overflow or underflow f32 at distances where the term itself is finite.
+template <typename T, int D>
+__device__ __forceinline__ void ot_accumulate_quad(bool on, T (&acc)[D], const T (&dj)[D], T d2f, T y0, const T* __restrict__ q) {
+  if (!on) return;
+  T y = y0;
+  if constexpr (sizeof(T) == 8) {
+    const T e = __builtin_elementwise_fma(-d2f, y0 * y0, T(1));
+    y         = __builtin_elementwise_fma(y0 * e, __builtin_elementwise_fma(e, T(0.375), T(0.5)), y0);
+  }
+  T u[D], qu[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) u[k] = dj[k] * y;
+  if constexpr (D == 3) {
+    const T q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = q[4], q5 = q[5];
+    qu[0] = q0 * u[0] + q1 * u[1] + q2 * u[2];
+    qu[1] = q1 * u[0] + q3 * u[1] + q4 * u[2];
+    qu[2] = q2 * u[0] + q4 * u[1] + q5 * u[2];
+  } else {
+    const T q0 = q[0], q1 = q[1], q2 = q[2];
+    qu[0] = q0 * u[0] + q1 * u[1];
+    qu[1] = q1 * u[0] + q2 * u[1];
+  }
+  T uqu = T(0);
+#pragma unroll
+  for (int k = 0; k < D; ++k) uqu += u[k] * qu[k];
+  const T y2 = y * y;
+  const T s  = T(2.5) * uqu;
+#pragma unroll
+  for (int k = 0; k < D; ++k) acc[k] += ((s * u[k] - qu[k]) * y2) * y2;
+}
+
+// ot_force_quadrupole_kernel: the walk of nbody_octree_compute_quadrupole_force — ot_force_kernel's tests, order and monopole terms,
+// and the quadrupole term of every accepted cell.
+template <typename T, int D, bool COUNT>
+__global__ __launch_bounds__(64) void ot_force_quadrupole_kernel(const ot_node<T>* __restrict__ rootrec,
+                                                                 const ot_group<T, D>* __restrict__ groups, const uint32_t* __restrict__ list,
+                                                                 uint32_t nlist, const T* __restrict__ x, T* __restrict__ a, T c,
+                                                                 uint32_t first, T theta, uint32_t capacity, const T* __restrict__ root,
+                                                                 uint32_t* __restrict__ flags, uint32_t* __restrict__ counters,
+                                                                 const T* __restrict__ quad) {
+  [[maybe_unused]] constexpr T e2 = T(0);
+#define OT_SOFT false
+#define OT_QUAD
+#include "ot_walk_body.inc"
+#undef OT_QUAD
+#undef OT_SOFT
+}
+
 // the accepted term's weight for d2 >= 2^-46 (ot_accumulate's far form, same operations in the same order); v[60:61] = mass
 #define OT_FAR                                                                                                            \
   "v_mul_f64 %[y2], %[y], %[y]\n\t"                                                                                       \
@@ -2406,8 +2578,10 @@ struct nbody_octree {
   uint32_t* later2 = nullptr, *later2_mask = nullptr;  //   the same for the blocks of ot_multipole_round_kernel
   uint32_t* lvl_count = nullptr;  // [MAXL + 2] level counts and deep groups, flags, two barrier counters, deep-list cursor, crown count
   uint32_t* counters = nullptr;
+  void* quad         = nullptr;  // T[1 + max_cells * 2^D][NQ]: quadrupoles by node index; allocated by the first nbody_octree_compute_quadrupoles
   int sorted_buf   = 0;
   bool counters_on = false, have_bounds = false, inserted = false, have_tree = false;
+  bool have_quad = false;  // nbody_octree_compute_quadrupoles ran after the latest clear / insert / compute_tree / set_build
 };
 
 using namespace nbody;
@@ -2590,7 +2764,13 @@ static int ot_tree_run(nbody_octree* t, hipStream_t st) {
 
 // soft: the softened walk (e2 > 0), which exists in the compiler-scheduled form only
 template <typename T, int D>
-static int ot_force_run(nbody_octree* t, const nbody_state* s, double theta, hipStream_t st, bool soft = false, T e2 = T(0)) {
+static int ot_force_run(nbody_octree* t, const nbody_state* s, double theta, hipStream_t st, bool soft = false, T e2 = T(0),
+                        bool quadrupole = false) {
+  if (quadrupole && t->walk == 2) {
+    set_error("octree walk: the quadrupole walk exists in the compiler-scheduled form only (walk form 1 or 0 = auto), not as the "
+              "ISA visit round set by nbody_octree_set_walk(t, 2)");
+    return NBODY_ERR_ARG;
+  }
   if (soft && t->walk == 2) {
     set_error("octree walk: the softened walk exists in the compiler-scheduled form only (walk form 1 or 0 = auto), not as the ISA "
               "visit round set by nbody_octree_set_walk(t, 2)");
@@ -2632,6 +2812,19 @@ static int ot_force_run(nbody_octree* t, const nbody_state* s, double theta, hip
     NB_HIP(hipGetLastError());
     return NBODY_OK;
   }
+  if (quadrupole) {
+#define NB_OT_QUAD(CNT)                                                                                                      \
+  hipLaunchKernelGGL((ot_force_quadrupole_kernel<T, D, CNT>), dim3(blocks), dim3(64), 0, st, rootrec,                        \
+                     static_cast<const ot_group<T, D>*>(t->groups), list, s->count,                                          \
+                     static_cast<const T*>(s->x), static_cast<T*>(s->a), static_cast<T>(s->c), s->first,                     \
+                     static_cast<T>(theta), budget, static_cast<const T*>(t->root),                                        \
+                     t->lvl_count + ((D == 3 ? kMaxLevels<3> : kMaxLevels<2>) + 2), t->counters, static_cast<const T*>(t->quad))
+    if (t->counters_on) NB_OT_QUAD(true);
+    else NB_OT_QUAD(false);
+#undef NB_OT_QUAD
+    NB_HIP(hipGetLastError());
+    return NBODY_OK;
+  }
   // the visit round written as ISA (ot_force_isa_kernel, ot_force_isa_f32_kernel; 2D and 3D), while 24-bit group numbers times the group
   // size stay inside 32-bit offsets; nbody_octree_set_walk(t, 1) keeps the compiler-scheduled kernel (tests compare the two bitwise)
   bool isa = false;
@@ -2665,6 +2858,35 @@ static int ot_force_run(nbody_octree* t, const nbody_state* s, double theta, hip
   return NBODY_OK;
 }
 
+// Children before parents: the cells below the key depth (one thread per cell of depth kMaxLevels), then the key levels one launch
+// each, deepest first, over the cell lists the multipole pass of the same build form reads.  The root's slot is cleared first: a
+// root that holds one body (or none) has Q = 0 and no launch writes it.
+template <typename T, int D>
+static int ot_quad_run(nbody_octree* t, hipStream_t st) {
+  constexpr uint32_t NCH = 1u << D;
+  const ot_tree<T, D> tree{static_cast<ot_group<T, D>*>(t->groups), static_cast<ot_node<T>*>(t->rootrec)};
+  T* quad              = static_cast<T*>(t->quad);
+  const bool one_pass  = t->build == 0 || t->build == 3;
+  NB_HIP(hipMemsetAsync(quad, 0, sizeof(T) * kOtNQ<D>, st));
+  hipLaunchKernelGGL((ot_quadrupole_deep_kernel<T, D>), dim3(64), dim3(64), 0, st, tree, quad, t->cells,
+                     one_pass ? t->tops : static_cast<const ot_cell*>(nullptr), t->lvl_count, t->capacity);
+  NB_HIP(hipGetLastError());
+  for (int l = kMaxLevels<D> - 1; l >= 0; --l) {
+    if (one_pass) {
+      hipLaunchKernelGGL((ot_quadrupole_ranks_level_kernel<T, D>), dim3((t->max_cells + kOB - 1) / kOB), dim3(kOB), 0, st, l, tree, quad,
+                         t->cells, t->lvl_count, t->capacity, t->max_cells);
+    } else {
+      uint64_t width = 1;
+      for (int j = 0; j < l && width < (uint64_t(1) << 40); ++j) width *= NCH;
+      const uint64_t cap_l = width < uint64_t(t->n / 2 + 1) ? width : uint64_t(t->n / 2 + 1);
+      hipLaunchKernelGGL((ot_quadrupole_level_kernel<T, D>), dim3(uint32_t((cap_l + kOB - 1) / kOB)), dim3(kOB), 0, st, l, tree, quad,
+                         t->cells, t->lvl_count, t->max_cells);
+    }
+    NB_HIP(hipGetLastError());
+  }
+  return NBODY_OK;
+}
+
 }  // namespace nbody
 
 extern "C" int nbody_octree_create(nbody_octree** out, int dtype, int dim, uint32_t n) {
@@ -2688,7 +2910,7 @@ extern "C" int nbody_octree_set_build(nbody_octree* t, int mode) {
   NB_ARG(mode == 0 || mode == 1 || mode == 3, "build form must be 0 (auto), 1 (breadth-first, one launch per level) or 3 (one pass over the sorted keys), got %d%s",
          mode, mode == 2 || mode == 4 ? " — that form exists only in the -DNBODY_EXPERIMENTS build (make experiments)" : "");
 #endif
-  if (mode != t->build) t->inserted = t->have_tree = false;  // the forms lay the cell list out differently: a tree inserted by one
+  if (mode != t->build) t->inserted = t->have_tree = t->have_quad = false;  // the forms lay the cell list out differently: a tree inserted by one
                                                              // is not the other's to finish (insert again after a change)
   t->build = mode;
   if (mode != 4) t->depth_hint = 64;  // 1: every level its own launch, whatever earlier trees looked like
@@ -2810,6 +3032,7 @@ extern "C" void nbody_octree_destroy(nbody_octree* t) {
   (void)hipFree(t->later2_mask);
   (void)hipFree(t->lvl_count);
   (void)hipFree(t->counters);
+  (void)hipFree(t->quad);
   delete t;
 }
 
@@ -2819,6 +3042,7 @@ extern "C" int nbody_octree_clear(nbody_octree* t, void* stream) {
   // every node the build allocates is fully rewritten by it: nothing to reset but the phase flags
   t->inserted  = false;
   t->have_tree = false;
+  t->have_quad = false;
   return NBODY_OK;
 }
 
@@ -2844,6 +3068,7 @@ extern "C" int nbody_octree_insert(nbody_octree* t, const nbody_state* s, void* 
     using TG = decltype(tg);
     return ot_insert_run<typename TG::type, TG::dim>(t, s, as_stream(stream));
   });
+  t->have_quad = false;  // (also when the insert failed: the tree is no longer the one the quadrupoles describe)
   if (r == NBODY_OK) t->inserted = true;
   return r;
 }
@@ -2860,6 +3085,7 @@ extern "C" int nbody_octree_compute_tree(nbody_octree* t, void* stream) {
     using TG = decltype(tg);
     return ot_tree_run<typename TG::type, TG::dim>(t, as_stream(stream));
   });
+  t->have_quad = false;
   if (r == NBODY_OK) t->have_tree = true;
   return r;
 }
@@ -2967,6 +3193,65 @@ extern "C" int nbody_octree_read_counters(nbody_octree* t, uint32_t* host_out, s
   device_guard guard(t->device);
   NB_ARG(bytes == sizeof(uint32_t) * 2 * size_t(t->n), "expected %zu bytes", sizeof(uint32_t) * 2 * size_t(t->n));
   NB_HIP(hipMemcpyAsync(host_out, t->counters, bytes, hipMemcpyDeviceToHost, as_stream(stream)));
+  NB_HIP(hipStreamSynchronize(as_stream(stream)));
+  return NBODY_OK;
+}
+
+// Host-side phase tracking in call order: a recorded step replays its calls in the order they were recorded, so the checks hold
+// for graphs too.
+static int ot_quad_ready(nbody_octree* t, const char* what) {
+  if (!t->have_quad) {
+    set_error("%s before nbody_octree_compute_quadrupoles (which must follow the latest clear / insert / compute_tree / set_build)", what);
+    return NBODY_ERR_STATE;
+  }
+  return NBODY_OK;
+}
+
+extern "C" int nbody_octree_compute_quadrupoles(nbody_octree* t, void* stream) {
+  NB_ARG(t != nullptr, "nbody_octree is NULL");
+  if (int r = check_same_device(t->device, as_stream(stream), "nbody_octree")) return r;
+  device_guard guard(t->device);
+  if (!t->have_tree) {
+    set_error("nbody_octree_compute_quadrupoles before nbody_octree_compute_tree");
+    return NBODY_ERR_STATE;
+  }
+  hipStream_t st = as_stream(stream);
+  if (!t->quad) {
+    if (capture_id(st) != 0) {
+      set_error("nbody_octree_compute_quadrupoles: the quadrupole array is allocated by the first call; call once before capture "
+                "(outside nbody_graph_begin/end)");
+      return NBODY_ERR_STATE;
+    }
+    const size_t nq = t->dim == 3 ? 6 : 3;  // every node the groups can hold, and the root
+    NB_HIP(hipMalloc(&t->quad, t->tsz * nq * (size_t(t->max_cells) * (size_t(1) << t->dim) + 1)));
+  }
+  int r = dispatch(t->dtype, t->dim, [&](auto tg) {
+    using TG = decltype(tg);
+    return ot_quad_run<typename TG::type, TG::dim>(t, st);
+  });
+  if (r == NBODY_OK) t->have_quad = true;
+  return r;
+}
+
+extern "C" int nbody_octree_compute_quadrupole_force(nbody_octree* t, const nbody_state* s, double theta, void* stream) {
+  if (int r = check_state(s)) return r;  // (before the tree: a bad state is reported as such whatever the tree)
+  if (int r = ot_check(t, s, stream)) return r;
+  device_guard guard(t->device);
+  if (int r = ot_quad_ready(t, "nbody_octree_compute_quadrupole_force")) return r;
+  return dispatch(s->dtype, s->dim, [&](auto tg) {
+    using TG = decltype(tg);
+    using T  = typename TG::type;
+    return ot_force_run<T, TG::dim>(t, s, theta, as_stream(stream), false, T(0), true);
+  });
+}
+
+extern "C" int nbody_octree_read_root_quadrupole(nbody_octree* t, void* host_out, void* stream) {
+  NB_ARG(t != nullptr && host_out != nullptr, "NULL argument");
+  if (int r = check_same_device(t->device, as_stream(stream), "nbody_octree")) return r;
+  device_guard guard(t->device);
+  if (int r = ot_quad_ready(t, "nbody_octree_read_root_quadrupole")) return r;
+  const size_t nq = t->dim == 3 ? 6 : 3;
+  NB_HIP(hipMemcpyAsync(host_out, t->quad, t->tsz * nq, hipMemcpyDeviceToHost, as_stream(stream)));
   NB_HIP(hipStreamSynchronize(as_stream(stream)));
   return NBODY_OK;
 }

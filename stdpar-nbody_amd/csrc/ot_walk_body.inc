@@ -1,7 +1,9 @@
 // Body of the compiler-scheduled octree walk (walk form 1), included by ot_force_kernel (OT_SOFT false) and by
 // ot_force_softened_kernel (OT_SOFT true: the same tests in the same order, the accepted term ot_accumulate_soft).  Included
 // rather than inlined for the reason k1_sgpr_body.inc gives.
-// In scope: T, D, COUNT, rootrec, groups, list, nlist, x, a, c, first, theta, capacity, root, flags, counters, e2.
+// ot_force_quadrupole_kernel defines OT_QUAD as well: every accepted cell also adds its quadrupole term (ot_accumulate_quad); the
+// kernels that leave it undefined are the same text as before it existed.
+// In scope: T, D, COUNT, rootrec, groups, list, nlist, x, a, c, first, theta, capacity, root, flags, counters, e2 (and quad).
   constexpr uint32_t NCH   = 1u << D;
   constexpr uint32_t GPW   = 64u / NCH;                         // bodies per wave
   constexpr uint32_t DEPTH = (NCH - 1u) * kMaxLevels<D> + NCH;  // a pop frees one slot, an open adds <= 2^D
@@ -40,6 +42,10 @@
       } else {
         if (m0 != 0ull) ot_accumulate<T, D>(on0, m0, acc, di, nd.m, d2f, y0, pc);
       }
+#ifdef OT_QUAD
+      const bool q0 = on0 && !leaf;  // an accepted root cell: its quadrupole is node 0's slot
+      if (__builtin_amdgcn_ballot_w64(q0) != 0ull) ot_accumulate_quad<T, D>(q0, acc, di, d2f, y0, quad);
+#endif
     }
     if (COUNT && cc == 0) {
       c_nodes = 1;
@@ -68,6 +74,13 @@
     } else {
       if (take_mask != 0ull) ot_accumulate<T, D>(take, take_mask, acc, di, nd.m, d2f, y0, pc);
     }
+#ifdef OT_QUAD
+    {  // leaves (bodies, empty slots) have no quadrupole: a round that accepts none loads nothing more
+      const bool qon = take && !leaf;
+      if (__builtin_amdgcn_ballot_w64(qon) != 0ull)
+        ot_accumulate_quad<T, D>(qon, acc, di, d2f, y0, quad + (uint64_t(1u + cur * NCH + cc) * uint32_t(kOtNQ<D>)));
+    }
+#endif
     const uint32_t open_mask = uint32_t((__ballot(!take) >> (g * NCH)) & ((1ull << NCH) - 1ull));
     if (sp + uint32_t(__builtin_popcount(open_mask)) > DEPTH) {  // only below the key depth can a walk hold this many
       if (cc == 0) atomicOr(flags, kFlagStack);                  // pending nodes; reported by nbody_octree_info

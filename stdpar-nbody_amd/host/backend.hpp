@@ -143,6 +143,12 @@ class Device {
   void octree_compute_bounds() { backend_check(nbody_octree_compute_bounds(octree_, &view_[0], stream()), "nbody_octree_compute_bounds"); }
   void octree_insert() { backend_check(nbody_octree_insert(octree_, &view_[0], stream()), "nbody_octree_insert"); }
   void octree_compute_tree() { backend_check(nbody_octree_compute_tree(octree_, stream()), "nbody_octree_compute_tree"); }
+  void octree_compute_quadrupoles() {
+    backend_check(nbody_octree_compute_quadrupoles(octree_, stream()), "nbody_octree_compute_quadrupoles");
+  }
+  void octree_compute_quadrupole_force(double theta) {
+    backend_check(nbody_octree_compute_quadrupole_force(octree_, &view_[0], theta, stream()), "nbody_octree_compute_quadrupole_force");
+  }
   void octree_compute_force(double theta, double softening = 0.0) {
     if (softening > 0.0)
       backend_check(nbody_octree_compute_softened_force(octree_, &view_[0], theta, softening, stream()),

@@ -167,7 +167,12 @@ void run_octree(System<T, D>& sys, Device<T, D>& dev, Options o) {
           t_bbox += timed([&] { dev.octree_compute_bounds(); dev.sync(); });
           t_insert += timed([&] { dev.octree_insert(); dev.sync(); });
           t_tree += timed([&] { dev.octree_compute_tree(); dev.sync(); });
-          t_walk += timed([&] { dev.octree_compute_force(theta, o.softening); dev.sync(); });
+          if (o.quadrupole) t_tree += timed([&] { dev.octree_compute_quadrupoles(); dev.sync(); });  // the multipoles column
+          t_walk += timed([&] {
+            if (o.quadrupole) dev.octree_compute_quadrupole_force(theta);
+            else dev.octree_compute_force(theta, o.softening);
+            dev.sync();
+          });
         });
         t_accel += timed([&] { dev.accelerate_step(); dev.sync(); });
         auto [size, mass] = dev.octree_info();  // also reports a build that hit the depth limit / node pool
@@ -185,7 +190,12 @@ void run_octree(System<T, D>& sys, Device<T, D>& dev, Options o) {
       dev.octree_compute_bounds();
       dev.octree_insert();
       dev.octree_compute_tree();
-      dev.octree_compute_force(theta, o.softening);
+      if (o.quadrupole) {
+        dev.octree_compute_quadrupoles();
+        dev.octree_compute_quadrupole_force(theta);
+      } else {
+        dev.octree_compute_force(theta, o.softening);
+      }
       dev.accelerate_step();
     };
     one_step();  // the phase-order checks of the ABI need one direct pass before the sequence is recorded

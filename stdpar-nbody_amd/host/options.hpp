@@ -34,6 +34,8 @@ struct Options {
   // not in the reference either (nor in --help): --softening EPS, Plummer softening length for all-pairs (also under --gpus N),
   // octree and --save energy; 0 = off, the same run as without the flag
   double softening = 0.0;
+  // not in the reference either (nor in --help): --quadrupole, octree cells also add their quadrupole term (octree only, unsoftened)
+  bool quadrupole = false;
 };
 
 namespace detail {
@@ -109,6 +111,8 @@ inline Options parse_options(std::vector<std::string> const& argv) {
         std::exit(EXIT_FAILURE);
       }
       o.softening = v;
+    } else if (f == "--quadrupole") {
+      o.quadrupole = true;
     } else if (f == "--print-state") {
       o.print_state = true;
     } else if (f == "--print-info") {
@@ -135,6 +139,14 @@ inline Options parse_options(std::vector<std::string> const& argv) {
   if (o.softening > 0.0 && (o.algorithm == Algorithm::Bvh || o.algorithm == Algorithm::AllPairsCollapsed)) {
     std::cerr << "--softening is supported by --algorithm all-pairs and octree only, not by "
               << (o.algorithm == Algorithm::Bvh ? "bvh" : "all-pairs-collapsed") << "." << std::endl;
+    std::exit(EXIT_FAILURE);
+  }
+  if (o.quadrupole && o.algorithm != Algorithm::Octree) {
+    std::cerr << "--quadrupole is supported by --algorithm octree only." << std::endl;
+    std::exit(EXIT_FAILURE);
+  }
+  if (o.quadrupole && o.softening > 0.0) {
+    std::cerr << "--quadrupole and --softening cannot be combined." << std::endl;
     std::exit(EXIT_FAILURE);
   }
   return o;
