@@ -79,7 +79,8 @@ typedef struct nbody_state {
  *      nbody_all_pairs_pair_rule decides from the positions' variances, not from their bounding box.
  * 2.4: Plummer softening: nbody_all_pairs_softened_force, nbody_calc_energies_softened, nbody_octree_compute_softened_force.
  *      Additive, same version: octree quadrupole moments, nbody_octree_compute_quadrupoles, nbody_octree_compute_quadrupole_force,
- *      nbody_octree_read_root_quadrupole. */
+ *      nbody_octree_read_root_quadrupole.  Additive, same version: octree potentials and energies, nbody_octree_compute_potential,
+ *      nbody_octree_compute_softened_potential, nbody_octree_compute_quadrupole_potential, nbody_octree_calc_energies. */
 #define NBODY_HIP_ABI_VERSION 2004
 int nbody_abi_version(void);
 
@@ -288,6 +289,33 @@ int nbody_calc_energies_softened(const nbody_state* s, double eps, void* kinetic
  * says on auto; NBODY_ERR_ARG if nbody_octree_set_walk(t, 2) asked for the ISA visit round, which has no softened form.
  * Counters (nbody_octree_read_counters) are the unsoftened walk's bit for bit. */
 int nbody_octree_compute_softened_force(nbody_octree* t, const nbody_state* s, double theta, double eps, void* stream);
+
+/* ---- octree potentials and energies (no reference counterpart) --------------------------------------------------------------
+ * The walk that gives the force gives the potential.  For body i, S_i = the sum over its walk of the accepted terms — the same opening
+ * tests in the same order as the matching force walk, the same per-child-slot partial sums combined in the same fixed order — and
+ *   phi_i = -c * S_i,   PE = -0.5 * c * sum_i m_i * S_i,
+ * which is System::calc_energies (src/system.h:62-79) with the inner sum replaced by the tree's.  Accepted terms, d = p - x[i]:
+ *   monopole    m / (|d| + eps(T)) (src/vec.h:243-246), evaluated as nbody_calc_energies evaluates a pair, so at theta = 0 every
+ *               term is the direct path's to rounding level;
+ *   softened    m / sqrt(|d|^2 + e2) (e2 as for the softened force; the same NBODY_ERR_ARG rules for eps);
+ *   quadrupole  the monopole term, and for accepted CELLS (never leaves) + 0.5 * (d^T Q d) / |d|^5, Q as stored by
+ *               nbody_octree_compute_quadrupoles.
+ * The body's own leaf (m / eps(T) unsoftened, m / eps softened, where the force's self term is 0) is left out: in a well-formed tree it
+ * is the only leaf at d == 0 in every coordinate.  The compiler-scheduled walk (form 1) on auto; NBODY_ERR_ARG after
+ * nbody_octree_set_walk(t, 2).  With counters on, the walks write the matching force walk's counters bit for bit.
+ * compute_*potential: phi (device pointer, T[count]): phi[k] = phi of body first + k; honours the shard window.  Phase order as for
+ *   the force entries (clear, compute_bounds, insert, compute_tree on this state; NBODY_ERR_STATE otherwise); the quadrupole entry also
+ *   needs compute_quadrupoles after the latest build.  They allocate nothing, so a step graph may record them.
+ * calc_energies: the whole system (first = 0, count = sz), on a tree built as above; eps = 0 unsoftened, eps > 0 softened,
+ *   quadrupole != 0 the quadrupole term (refused together with eps > 0).  Blocking, host outputs of one T each; the kinetic energy is
+ *   nbody_calc_energies' bit for bit, the potential goes through the same reduction.  NBODY_ERR_STATE under stream capture.
+ * Argument errors (NULL tree, state or output, a bad eps, quadrupole with eps, a shard window for calc_energies) return NBODY_ERR_ARG
+ * before the device is touched. */
+int nbody_octree_compute_potential(nbody_octree* t, const nbody_state* s, double theta, void* phi, void* stream);
+int nbody_octree_compute_softened_potential(nbody_octree* t, const nbody_state* s, double theta, double eps, void* phi, void* stream);
+int nbody_octree_compute_quadrupole_potential(nbody_octree* t, const nbody_state* s, double theta, void* phi, void* stream);
+int nbody_octree_calc_energies(nbody_octree* t, const nbody_state* s, double theta, double eps, int quadrupole, void* kinetic_out,
+                               void* potential_out, void* stream);
 
 /* ---- owning context (device mirrors of a host System), used by the C++ CLI host ------------------ */
 

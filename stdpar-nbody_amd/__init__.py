@@ -58,6 +58,8 @@ ABI_SYMBOLS = [
     "nbody_allgather_positions", "nbody_bvh_opening_thresholds", "nbody_all_pairs_pair_rule", "nbody_all_pairs_status",
     "nbody_all_pairs_softened_force", "nbody_calc_energies_softened", "nbody_octree_compute_softened_force",
     "nbody_octree_compute_quadrupoles", "nbody_octree_compute_quadrupole_force", "nbody_octree_read_root_quadrupole",
+    "nbody_octree_compute_potential", "nbody_octree_compute_softened_potential", "nbody_octree_compute_quadrupole_potential",
+    "nbody_octree_calc_energies",
 ]
 ABI_MAJOR = 2
 COMM_ID_BYTES = 128
@@ -87,6 +89,11 @@ def lib():
         L.nbody_ctx_stream.restype = C.c_void_p
         L.nbody_bvh_nnodes.restype = C.c_uint32
         L.nbody_shard_range.restype = None
+        vp, d = C.c_void_p, C.c_double
+        L.nbody_octree_compute_potential.argtypes = [vp, vp, d, vp, vp]
+        L.nbody_octree_compute_softened_potential.argtypes = [vp, vp, d, d, vp, vp]
+        L.nbody_octree_compute_quadrupole_potential.argtypes = [vp, vp, d, vp, vp]
+        L.nbody_octree_calc_energies.argtypes = [vp, vp, d, d, C.c_int, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -373,6 +380,28 @@ class Octree:
         _check(lib().nbody_octree_read_root_quadrupole(self.h, _p(out), C.c_void_p(stream)))
         return out
 
+    def compute_potential(self, st, theta, phi, stream=None):
+        """phi[k] = -c S of body st.first + k (nbody_octree_compute_potential): the force walk's tests, the accepted term
+        m / (|d| + eps(T)), the body's own leaf left out.  phi: a device pointer (int) to count values of T, e.g. a torch tensor's
+        data_ptr(); nothing is allocated, so this may be recorded."""
+        _check(lib().nbody_octree_compute_potential(self.h, C.byref(st), theta, phi, stream))
+
+    def compute_softened_potential(self, st, theta, eps, phi, stream=None):
+        """compute_potential with the softened term m / sqrt(|d|^2 + eps^2) (nbody_octree_compute_softened_potential)."""
+        _check(lib().nbody_octree_compute_softened_potential(self.h, C.byref(st), theta, eps, phi, stream))
+
+    def compute_quadrupole_potential(self, st, theta, phi, stream=None):
+        """compute_potential whose accepted cells also add 1/2 (d^T Q d) / |d|^5 (after compute_quadrupoles)."""
+        _check(lib().nbody_octree_compute_quadrupole_potential(self.h, C.byref(st), theta, phi, stream))
+
+    def calc_energies(self, st, theta, eps=0.0, quadrupole=False, stream=None):
+        """(kinetic, potential) with the potential from the tree (nbody_octree_calc_energies; blocking, whole system, on a built
+        tree): -c/2 sum_i m_i S_i.  eps > 0 softened, quadrupole=True the quadrupole term (after compute_quadrupoles)."""
+        t = np_dtype(self.dtype)
+        ke, pe = np.zeros(1, t), np.zeros(1, t)
+        _check(lib().nbody_octree_calc_energies(self.h, C.byref(st), theta, eps, 1 if quadrupole else 0, _p(ke), _p(pe), stream))
+        return ke[0], pe[0]
+
     def info(self, stream=None):
         """(tree size = next_free_child_group, root mass); raises if the build hit the depth limit / node pool."""
         size = C.c_uint32()
@@ -500,6 +529,39 @@ class DeviceSystem:
         if self._octree is None:
             self._octree = Octree(self.dtype, self.dim, self.n, self.device)
         return self._octree
+
+    def _octree_build(self, quadrupole=False):
+        st, t = self.state(), self.octree
+        t.clear(self.stream)
+        t.compute_bounds(st, self.stream)
+        t.insert(st, self.stream)
+        t.compute_tree(self.stream)
+        if quadrupole:
+            t.compute_quadrupoles(self.stream)
+        return st, t
+
+    def octree_potential(self, theta, softening=0.0, quadrupole=False):
+        """Per-body potentials phi_i = -c S_i from the tree, built like octree_force; returns a NumPy array (n,) of T."""
+        if softening and quadrupole:
+            raise ValueError("octree_potential: softening and quadrupole cannot be combined")
+        import torch
+        st, t = self._octree_build(quadrupole)
+        phi = torch.empty(self.n, dtype=torch.float32 if self.dtype == F32 else torch.float64, device=f"cuda:{self.device}")
+        if quadrupole:
+            t.compute_quadrupole_potential(st, theta, phi.data_ptr(), self.stream)
+        elif softening:
+            t.compute_softened_potential(st, theta, softening, phi.data_ptr(), self.stream)
+        else:
+            t.compute_potential(st, theta, phi.data_ptr(), self.stream)
+        self.sync()
+        return phi.cpu().numpy()
+
+    def octree_energies(self, theta, softening=0.0, quadrupole=False):
+        """(kinetic, potential) with the potential from the tree, built like octree_force (nbody_octree_calc_energies)."""
+        if softening and quadrupole:
+            raise ValueError("octree_energies: softening and quadrupole cannot be combined")
+        st, t = self._octree_build(quadrupole)
+        return t.calc_energies(st, theta, softening, quadrupole, self.stream)
 
     def octree_force(self, theta, softening=0.0, quadrupole=False):
         """One force phase of run_octree (src/octree.h:321-326); softening > 0 takes the softened walk, quadrupole=True the

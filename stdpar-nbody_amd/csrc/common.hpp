@@ -584,5 +584,8 @@ void ap_status_mark(hipStream_t st);  // a recorded step is being replayed on st
 int ap_status_read(hipStream_t st, unsigned long long out[6], bool clear);  // waits for the stream; NBODY_ERR_STATE while a K1 hand-off failure is recorded
 int ap_pack_sources(const nbody_state* s, hipStream_t st, void** packed_out);
 void ap_auto_chunks(uint32_t sz, uint32_t* chunks, uint32_t* tiles_per_chunk);
+// energy.hip: nbody_calc_energies' reduction over per-body sums S_i that `fill` writes (T[sz], on st) into the buffer it is handed:
+// kinetic = 1/2 sum_i m_i |v_i|^2 (the same launch: the same bits), potential = -c/2 sum_i m_i S_i.  Blocking; host outputs of one T.
+int energies_from_sums(const nbody_state* s, hipStream_t st, int (*fill)(void* sums, void* ctx), void* ctx, void* ke_out, void* pe_out);
 
 }  // namespace nbody

@@ -229,6 +229,28 @@ __global__ __launch_bounds__(kEB) void energy_final_kernel(const T* __restrict__
   }
 }
 
+// energy_partial_kernel over `nchunks` rows of per-body sums, energy_final_kernel, and the two values to the host (blocking)
+template <typename T, int D>
+static int energies_reduce(const nbody_state* s, hipStream_t st, const T* sums, uint32_t nchunks, T* partial, uint32_t nblk, T* out,
+                           void* ke_out, void* pe_out) {
+  hipLaunchKernelGGL((energy_partial_kernel<T, D>), dim3(nblk), dim3(kEB), 0, st, static_cast<const T*>(s->m),
+                     static_cast<const T*>(s->v), sums, nchunks, s->sz, partial);
+  NB_HIP(hipGetLastError());
+  hipLaunchKernelGGL((energy_final_kernel<T>), dim3(1), dim3(kEB), 0, st, partial, nblk, static_cast<T>(s->c), out);
+  NB_HIP(hipGetLastError());
+  T host[2];
+  NB_HIP(hipMemcpyAsync(host, out, sizeof host, hipMemcpyDeviceToHost, st));
+  NB_HIP(hipStreamSynchronize(st));
+  *static_cast<T*>(ke_out) = host[0];
+  *static_cast<T*>(pe_out) = host[1];
+  return NBODY_OK;
+}
+
+static uint32_t energies_blocks(uint32_t n) {
+  const uint32_t nblk = (n + kEB - 1) / kEB;
+  return nblk > 1024 ? 1024 : nblk;
+}
+
 template <typename T, int D, bool SOFT = false>
 static int energies_run(const nbody_state* s, void* ke_out, void* pe_out, hipStream_t st, T e2 = T(0)) {
   constexpr int R       = sizeof(T) == 8 ? 2 : 1;
@@ -236,8 +258,7 @@ static int energies_run(const nbody_state* s, void* ke_out, void* pe_out, hipStr
   const uint32_t ntiles = (n + kTileJ - 1) / kTileJ;
   uint32_t chunks = 1, tpc = ntiles;
   ap_auto_chunks(n, &chunks, &tpc);
-  uint32_t nblk = (n + kEB - 1) / kEB;
-  if (nblk > 1024) nblk = 1024;
+  const uint32_t nblk = energies_blocks(n);
   // persistent work area of this stream: chunk sums [chunks][n], block partials [2 * nblk], result [2]
   void* w = nullptr;
   if (int r = ap_scratch_get(st, 2, sizeof(T) * (size_t(chunks) * n + 2 * size_t(nblk) + 2), &w)) return r;
@@ -253,17 +274,28 @@ static int energies_run(const nbody_state* s, void* ke_out, void* pe_out, hipStr
     hipLaunchKernelGGL((potential_sgpr_kernel<T, D, R>), dim3((n + 64 * R - 1) / (64 * R), chunks), dim3(64 * kPotJS), 0, st,
                        static_cast<const src_rec<T, D>*>(packed), static_cast<const T*>(s->x), sums, n, tpc);
   NB_HIP(hipGetLastError());
-  hipLaunchKernelGGL((energy_partial_kernel<T, D>), dim3(nblk), dim3(kEB), 0, st, static_cast<const T*>(s->m),
-                     static_cast<const T*>(s->v), sums, chunks, n, partial);
-  NB_HIP(hipGetLastError());
-  hipLaunchKernelGGL((energy_final_kernel<T>), dim3(1), dim3(kEB), 0, st, partial, nblk, static_cast<T>(s->c), out);
-  NB_HIP(hipGetLastError());
-  T host[2];
-  NB_HIP(hipMemcpyAsync(host, out, sizeof host, hipMemcpyDeviceToHost, st));
-  NB_HIP(hipStreamSynchronize(st));
-  *static_cast<T*>(ke_out) = host[0];
-  *static_cast<T*>(pe_out) = host[1];
-  return NBODY_OK;
+  return energies_reduce<T, D>(s, st, sums, chunks, partial, nblk, out, ke_out, pe_out);
+}
+
+// one row of sums (nchunks = 1), in the same per-stream work area
+template <typename T, int D>
+static int energies_from_sums_run(const nbody_state* s, hipStream_t st, int (*fill)(void*, void*), void* ctx, void* ke_out, void* pe_out) {
+  const uint32_t n    = s->sz;
+  const uint32_t nblk = energies_blocks(n);
+  void* w             = nullptr;
+  if (int r = ap_scratch_get(st, 2, sizeof(T) * (size_t(n) + 2 * size_t(nblk) + 2), &w)) return r;
+  T* sums    = static_cast<T*>(w);
+  T* partial = sums + n;
+  T* out     = partial + 2 * size_t(nblk);
+  if (int r = fill(sums, ctx)) return r;
+  return energies_reduce<T, D>(s, st, sums, 1u, partial, nblk, out, ke_out, pe_out);
+}
+
+int energies_from_sums(const nbody_state* s, hipStream_t st, int (*fill)(void* sums, void* ctx), void* ctx, void* ke_out, void* pe_out) {
+  return dispatch(s->dtype, s->dim, [&](auto tg) {
+    using TG = decltype(tg);
+    return energies_from_sums_run<typename TG::type, TG::dim>(s, st, fill, ctx, ke_out, pe_out);
+  });
 }
 
 }  // namespace nbody

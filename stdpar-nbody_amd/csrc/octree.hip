@@ -2018,6 +2018,162 @@ __global__ __launch_bounds__(64) void ot_force_quadrupole_kernel(const ot_node<T
 #undef OT_SOFT
 }
 
+// ---- per-body potentials (nbody_octree_compute_*potential, nbody_octree_calc_energies; no reference counterpart) ----------------
+// S_i = the sum over body i's walk of the accepted terms, phi_i = -c S_i, and PE = -c/2 sum_i m_i S_i: System::calc_energies
+// (src/system.h:62-79) with the inner sum taken from the tree.  Unlike the force, whose self term is 0 * d, the potential's is
+// m / eps: the body's own leaf — in a well-formed tree the only leaf at d == 0 in every coordinate (the build flags coincident
+// bodies) — is left out by a select.  Empty slots have m = 0 and add 0.
+
+// S += mj / (sqrt(d2) + eps) (src/vec.h:243-246) for the lanes in `on`, the body's own leaf left out.  energy.hip's pot_math, on the
+// seed the opening test already paid for: far (d2 >= 2^-48 in f64, 2^-20 in f32) mj y (1 - eps y) with y polished to third order in
+// f64, the 1-ulp seed in f32; near (one compare and one wave-uniform branch) the reference's expression from a polished square root
+// and reciprocal.  At theta = 0 every term is the direct path's to rounding level.
+template <typename T>
+struct ot_pot_near {
+  static constexpr uint32_t bits = sizeof(T) == 8 ? 0x3CF00000u : 0x35800000u;  // high word of 2^-48 / bits of 2^-20
+};
+
+template <typename T, int D>
+__device__ __forceinline__ void ot_potential_term(bool on, uint64_t on_mask, T& s, const T (&dj)[D], T mj, T d2f, T y0) {
+  bool self = true;
+#pragma unroll
+  for (int k = 0; k < D; ++k) self = self && dj[k] == T(0);
+  T w;
+  if constexpr (sizeof(T) == 8) {
+    const T a  = y0 * y0;
+    const T e  = __builtin_fma(-d2f, a, 1.0);
+    const T p  = __builtin_fma(e, 0.375, 0.5);
+    const T ey = DBL_EPSILON * y0;
+    const T g  = __builtin_fma(p, e, -ey);
+    const T my = mj * y0;
+    w          = __builtin_fma(my, g, my);
+  } else {
+    const T my = mj * y0;
+    w          = __builtin_fmaf(my, -FLT_EPSILON * y0, my);
+  }
+  const bool close = ot_near<T>::of(d2f) < ot_pot_near<T>::bits;
+  if (__builtin_expect((__builtin_amdgcn_ballot_w64(close) & on_mask) != 0ull, 0)) {
+    T wn;
+    if constexpr (sizeof(T) == 8) {
+      const T h  = d2f * y0;
+      const T e  = __builtin_fma(-h, y0, 1.0);
+      const T p  = __builtin_fma(e, 0.375, 0.5);
+      const T sq = __builtin_fma(h * e, p, h);
+      const T d  = sq + DBL_EPSILON;
+      const T z0 = __builtin_amdgcn_rcp(d);
+      const T e2 = __builtin_fma(-d, z0, 1.0);
+      const T q  = __builtin_fma(e2, e2, e2);
+      const T zm = z0 * mj;
+      wn         = __builtin_fma(zm, q, zm);
+    } else {
+      const T d = __builtin_fmaf(d2f, y0, FLT_EPSILON);
+      wn        = __builtin_amdgcn_rcpf(d) * mj;
+    }
+    w = close ? wn : w;
+  }
+  s += (on && !self) ? w : T(0);
+}
+
+// The softened term, S += mj / sqrt(d2 + e2), q = d2 + e2 seeded with e2 as in ot_accumulate_soft: mj y (1 + e/2 + 3/8 e^2) in f64,
+// mj y in f32 (energy.hip's pot_batch_soft).  q >= e2, so there is no near path; the own leaf (mj / eps here) is left out by the select.
+template <typename T, int D>
+__device__ __forceinline__ void ot_potential_soft(bool on, T& s, const T (&dj)[D], T mj, T e2) {
+  bool self = true;
+  T q       = e2;
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    self = self && dj[k] == T(0);
+    q    = __builtin_elementwise_fma(dj[k], dj[k], q);
+  }
+  T v;
+  if constexpr (sizeof(T) == 8) {
+    const T y  = __builtin_amdgcn_rsq(q);
+    const T e  = __builtin_fma(-q, y * y, 1.0);
+    const T p  = __builtin_fma(e, 0.375, 0.5);
+    const T my = mj * y;
+    v          = __builtin_fma(my, p * e, my);
+  } else {
+    v = mj * __builtin_amdgcn_rsqf(q);
+  }
+  s += (on && !self) ? v : T(0);
+}
+
+// The quadrupole term of an accepted cell, S += 1/2 (d^T Q d) y^5, evaluated on the unit vector u = d y as ((1/2 u^T Q u) y^2) y —
+// |Q| y^2 is about m theta^2 for an accepted cell, so every intermediate is bounded like the monopole's m y (ot_accumulate_quad).
+template <typename T, int D>
+__device__ __forceinline__ void ot_potential_quad(bool on, T& s, const T (&dj)[D], T d2f, T y0, const T* __restrict__ q) {
+  if (!on) return;
+  T y = y0;
+  if constexpr (sizeof(T) == 8) {
+    const T e = __builtin_elementwise_fma(-d2f, y0 * y0, T(1));
+    y         = __builtin_elementwise_fma(y0 * e, __builtin_elementwise_fma(e, T(0.375), T(0.5)), y0);
+  }
+  T u[D], qu[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) u[k] = dj[k] * y;
+  if constexpr (D == 3) {
+    const T q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = q[4], q5 = q[5];
+    qu[0] = q0 * u[0] + q1 * u[1] + q2 * u[2];
+    qu[1] = q1 * u[0] + q3 * u[1] + q4 * u[2];
+    qu[2] = q2 * u[0] + q4 * u[1] + q5 * u[2];
+  } else {
+    const T q0 = q[0], q1 = q[1], q2 = q[2];
+    qu[0] = q0 * u[0] + q1 * u[1];
+    qu[1] = q1 * u[0] + q2 * u[1];
+  }
+  T uqu = T(0);
+#pragma unroll
+  for (int k = 0; k < D; ++k) uqu += u[k] * qu[k];
+  s += ((T(0.5) * uqu) * (y * y)) * y;
+}
+
+// The potential walks: ot_force_kernel's, ot_force_softened_kernel's and ot_force_quadrupole_kernel's tests in the same order, the
+// same per-slot partial sums combined in the same order; phi[body - first] = scale * S (scale -c for phi, 1 for the energies).
+// With counters on they write the force walk's counters.
+template <typename T, int D, bool COUNT>
+__global__ __launch_bounds__(64) void ot_potential_kernel(const ot_node<T>* __restrict__ rootrec, const ot_group<T, D>* __restrict__ groups,
+                                                          const uint32_t* __restrict__ list, uint32_t nlist, const T* __restrict__ x,
+                                                          T* __restrict__ phi, T scale, uint32_t first, T theta, uint32_t capacity,
+                                                          const T* __restrict__ root, uint32_t* __restrict__ flags,
+                                                          uint32_t* __restrict__ counters) {
+  [[maybe_unused]] constexpr T e2 = T(0);
+#define OT_SOFT false
+#define OT_POT
+#include "ot_walk_body.inc"
+#undef OT_POT
+#undef OT_SOFT
+}
+template <typename T, int D, bool COUNT>
+__global__ __launch_bounds__(64) void ot_potential_softened_kernel(const ot_node<T>* __restrict__ rootrec,
+                                                                   const ot_group<T, D>* __restrict__ groups,
+                                                                   const uint32_t* __restrict__ list, uint32_t nlist,
+                                                                   const T* __restrict__ x, T* __restrict__ phi, T scale, uint32_t first,
+                                                                   T theta, uint32_t capacity, const T* __restrict__ root,
+                                                                   uint32_t* __restrict__ flags, uint32_t* __restrict__ counters, T e2) {
+#define OT_SOFT true
+#define OT_POT
+#include "ot_walk_body.inc"
+#undef OT_POT
+#undef OT_SOFT
+}
+template <typename T, int D, bool COUNT>
+__global__ __launch_bounds__(64) void ot_potential_quadrupole_kernel(const ot_node<T>* __restrict__ rootrec,
+                                                                     const ot_group<T, D>* __restrict__ groups,
+                                                                     const uint32_t* __restrict__ list, uint32_t nlist,
+                                                                     const T* __restrict__ x, T* __restrict__ phi, T scale,
+                                                                     uint32_t first, T theta, uint32_t capacity,
+                                                                     const T* __restrict__ root, uint32_t* __restrict__ flags,
+                                                                     uint32_t* __restrict__ counters, const T* __restrict__ quad) {
+  [[maybe_unused]] constexpr T e2 = T(0);
+#define OT_SOFT false
+#define OT_QUAD
+#define OT_POT
+#include "ot_walk_body.inc"
+#undef OT_POT
+#undef OT_QUAD
+#undef OT_SOFT
+}
+
 // the accepted term's weight for d2 >= 2^-46 (ot_accumulate's far form, same operations in the same order); v[60:61] = mass
 #define OT_FAR                                                                                                            \
   "v_mul_f64 %[y2], %[y], %[y]\n\t"                                                                                       \
@@ -2762,6 +2918,25 @@ static int ot_tree_run(nbody_octree* t, hipStream_t st) {
   return NBODY_OK;
 }
 
+// The bodies a walk takes, in key order: the sorted body indices themselves, or for a shard window the owned ones compacted (order
+// kept; scratch: the sort's other buffers).
+static int ot_walk_list(nbody_octree* t, const nbody_state* s, hipStream_t st, const uint32_t** out) {
+  const uint32_t* list = t->idx[t->sorted_buf];  // whole system: the sorted body indices themselves
+  if (s->count < s->sz) {                        // shard window: compact the owned ones (scratch: the sort's other buffers)
+    uint32_t* owned       = t->idx[1 - t->sorted_buf];
+    const uint32_t nblk   = (s->sz + kOC - 1) / kOC;
+    hipLaunchKernelGGL(ot_owned_count_kernel, dim3(nblk), dim3(kOC), 0, st, list, s->sz, s->first, s->count, t->hist);
+    NB_HIP(hipGetLastError());
+    hipLaunchKernelGGL(ot_owned_scan_kernel, dim3(1), dim3(kOC), 0, st, t->hist, nblk);
+    NB_HIP(hipGetLastError());
+    hipLaunchKernelGGL(ot_owned_scatter_kernel, dim3(nblk), dim3(kOC), 0, st, list, s->sz, s->first, s->count, t->hist, owned);
+    NB_HIP(hipGetLastError());
+    list = owned;
+  }
+  *out = list;
+  return NBODY_OK;
+}
+
 // soft: the softened walk (e2 > 0), which exists in the compiler-scheduled form only
 template <typename T, int D>
 static int ot_force_run(nbody_octree* t, const nbody_state* s, double theta, hipStream_t st, bool soft = false, T e2 = T(0),
@@ -2777,18 +2952,8 @@ static int ot_force_run(nbody_octree* t, const nbody_state* s, double theta, hip
     return NBODY_ERR_ARG;
   }
   if (s->count == 0) return NBODY_OK;
-  const uint32_t* list = t->idx[t->sorted_buf];  // whole system: the sorted body indices themselves
-  if (s->count < s->sz) {                        // shard window: compact the owned ones (scratch: the sort's other buffers)
-    uint32_t* owned       = t->idx[1 - t->sorted_buf];
-    const uint32_t nblk   = (s->sz + kOC - 1) / kOC;
-    hipLaunchKernelGGL(ot_owned_count_kernel, dim3(nblk), dim3(kOC), 0, st, list, s->sz, s->first, s->count, t->hist);
-    NB_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ot_owned_scan_kernel, dim3(1), dim3(kOC), 0, st, t->hist, nblk);
-    NB_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ot_owned_scatter_kernel, dim3(nblk), dim3(kOC), 0, st, list, s->sz, s->first, s->count, t->hist, owned);
-    NB_HIP(hipGetLastError());
-    list = owned;
-  }
+  const uint32_t* list = nullptr;
+  if (int r = ot_walk_list(t, s, st, &list)) return r;
   const uint32_t per_wave = 64u >> D;
   const uint32_t blocks   = (s->count + per_wave - 1) / per_wave;
   const uint32_t budget   = t->step_budget ? t->step_budget : t->capacity;  // a well-formed tree is left after < capacity rounds
@@ -2854,6 +3019,43 @@ static int ot_force_run(nbody_octree* t, const nbody_state* s, double theta, hip
   } else if (t->counters_on) NB_OT_LAUNCH(true);
   else NB_OT_LAUNCH(false);
 #undef NB_OT_LAUNCH
+  NB_HIP(hipGetLastError());
+  return NBODY_OK;
+}
+
+// The potential walks: kind 0 monopole, 1 softened (e2), 2 quadrupole (after nbody_octree_compute_quadrupoles); phi[k] = scale * S of
+// body first + k.  Compiler-scheduled form only; shard windows through the force walk's owned list.
+enum { kOtPotMono = 0, kOtPotSoft = 1, kOtPotQuad = 2 };
+template <typename T, int D>
+static int ot_potential_run(nbody_octree* t, const nbody_state* s, double theta, hipStream_t st, int kind, T e2, T* phi, T scale) {
+  if (t->walk == 2) {
+    set_error("octree walk: the potential walk exists in the compiler-scheduled form only (walk form 1 or 0 = auto), not as the ISA "
+              "visit round set by nbody_octree_set_walk(t, 2)");
+    return NBODY_ERR_ARG;
+  }
+  if (s->count == 0) return NBODY_OK;
+  const uint32_t* list = nullptr;
+  if (int r = ot_walk_list(t, s, st, &list)) return r;
+  const uint32_t per_wave = 64u >> D;
+  const uint32_t blocks   = (s->count + per_wave - 1) / per_wave;
+  const uint32_t budget   = t->step_budget ? t->step_budget : t->capacity;
+  auto* rootrec           = static_cast<const ot_node<T>*>(t->rootrec);
+  uint32_t* flags         = t->lvl_count + ((D == 3 ? kMaxLevels<3> : kMaxLevels<2>) + 2);
+#define NB_OT_POT(KERN, CNT, ...)                                                                                              \
+  hipLaunchKernelGGL((KERN<T, D, CNT>), dim3(blocks), dim3(64), 0, st, rootrec, static_cast<const ot_group<T, D>*>(t->groups), list, \
+                     s->count, static_cast<const T*>(s->x), phi, scale, s->first, static_cast<T>(theta), budget,               \
+                     static_cast<const T*>(t->root), flags, t->counters __VA_OPT__(, ) __VA_ARGS__)
+  if (kind == kOtPotSoft) {
+    if (t->counters_on) NB_OT_POT(ot_potential_softened_kernel, true, e2);
+    else NB_OT_POT(ot_potential_softened_kernel, false, e2);
+  } else if (kind == kOtPotQuad) {
+    if (t->counters_on) NB_OT_POT(ot_potential_quadrupole_kernel, true, static_cast<const T*>(t->quad));
+    else NB_OT_POT(ot_potential_quadrupole_kernel, false, static_cast<const T*>(t->quad));
+  } else {
+    if (t->counters_on) NB_OT_POT(ot_potential_kernel, true);
+    else NB_OT_POT(ot_potential_kernel, false);
+  }
+#undef NB_OT_POT
   NB_HIP(hipGetLastError());
   return NBODY_OK;
 }
@@ -3254,4 +3456,105 @@ extern "C" int nbody_octree_read_root_quadrupole(nbody_octree* t, void* host_out
   NB_HIP(hipMemcpyAsync(host_out, t->quad, t->tsz * nq, hipMemcpyDeviceToHost, as_stream(stream)));
   NB_HIP(hipStreamSynchronize(as_stream(stream)));
   return NBODY_OK;
+}
+
+// The three potential entries: the state and phi first (a bad state is reported as such whatever the tree), then the tree and its
+// phase; they allocate nothing, so a step graph may record them.
+template <typename F>
+static int ot_potential_entry(nbody_octree* t, const nbody_state* s, void* phi, void* stream, const char* what, F&& run) {
+  if (int r = check_state(s)) return r;
+  NB_ARG(phi != nullptr, "%s: phi is NULL", what);
+  if (int r = ot_check(t, s, stream)) return r;
+  device_guard guard(t->device);
+  if (!t->have_tree) {
+    set_error("%s before nbody_octree_compute_tree", what);
+    return NBODY_ERR_STATE;
+  }
+  return dispatch(s->dtype, s->dim, [&](auto tg) {
+    using TG = decltype(tg);
+    return run(tg, static_cast<typename TG::type*>(phi), -static_cast<typename TG::type>(s->c));
+  });
+}
+
+extern "C" int nbody_octree_compute_potential(nbody_octree* t, const nbody_state* s, double theta, void* phi, void* stream) {
+  return ot_potential_entry(t, s, phi, stream, "nbody_octree_compute_potential", [&](auto tg, auto* p, auto scale) {
+    using TG = decltype(tg);
+    using T  = typename TG::type;
+    return ot_potential_run<T, TG::dim>(t, s, theta, as_stream(stream), kOtPotMono, T(0), p, scale);
+  });
+}
+
+extern "C" int nbody_octree_compute_softened_potential(nbody_octree* t, const nbody_state* s, double theta, double eps, void* phi,
+                                                       void* stream) {
+  if (int r = check_state(s)) return r;
+  if (int r = dispatch(s->dtype, s->dim, [&](auto tg) {
+        typename decltype(tg)::type e2;
+        return check_softening(eps, &e2);
+      }))
+    return r;
+  return ot_potential_entry(t, s, phi, stream, "nbody_octree_compute_softened_potential", [&](auto tg, auto* p, auto scale) {
+    using TG = decltype(tg);
+    using T  = typename TG::type;
+    T e2;
+    (void)check_softening<T>(eps, &e2);
+    return ot_potential_run<T, TG::dim>(t, s, theta, as_stream(stream), kOtPotSoft, e2, p, scale);
+  });
+}
+
+extern "C" int nbody_octree_compute_quadrupole_potential(nbody_octree* t, const nbody_state* s, double theta, void* phi, void* stream) {
+  return ot_potential_entry(t, s, phi, stream, "nbody_octree_compute_quadrupole_potential", [&](auto tg, auto* p, auto scale) {
+    using TG = decltype(tg);
+    using T  = typename TG::type;
+    if (int r = ot_quad_ready(t, "nbody_octree_compute_quadrupole_potential")) return r;
+    return ot_potential_run<T, TG::dim>(t, s, theta, as_stream(stream), kOtPotQuad, T(0), p, scale);
+  });
+}
+
+// The energies from the tree: S of every body by the potential walk (scale 1) into the energy path's per-body sums, then that path's
+// reduction (energies_from_sums: the kinetic energy is nbody_calc_energies' launch, so its bits).  Blocking; never under capture.
+extern "C" int nbody_octree_calc_energies(nbody_octree* t, const nbody_state* s, double theta, double eps, int quadrupole,
+                                          void* kinetic_out, void* potential_out, void* stream) {
+  if (int r = check_state(s)) return r;
+  NB_ARG(kinetic_out && potential_out, "NULL output pointer");
+  NB_ARG(s->first == 0 && s->count == s->sz, "nbody_octree_calc_energies needs the whole system (first=0, count=sz)");
+  NB_ARG(eps >= 0.0 && eps <= DBL_MAX, "nbody_octree_calc_energies: eps = %g must be 0 (unsoftened) or a finite softening length > 0", eps);
+  NB_ARG(!(quadrupole && eps > 0.0), "nbody_octree_calc_energies: the quadrupole term and softening cannot be combined");
+  if (eps > 0.0) {
+    if (int r = dispatch(s->dtype, s->dim, [&](auto tg) {
+          typename decltype(tg)::type e2;
+          return check_softening(eps, &e2);
+        }))
+      return r;
+  }
+  if (int r = ot_check(t, s, stream)) return r;
+  device_guard guard(t->device);
+  hipStream_t st = as_stream(stream);
+  if (capture_id(st) != 0) {
+    set_error("nbody_octree_calc_energies is blocking: it cannot be recorded (call it outside nbody_graph_begin/end)");
+    return NBODY_ERR_STATE;
+  }
+  if (!t->have_tree) {
+    set_error("nbody_octree_calc_energies before nbody_octree_compute_tree");
+    return NBODY_ERR_STATE;
+  }
+  if (quadrupole)
+    if (int r = ot_quad_ready(t, "nbody_octree_calc_energies(quadrupole)")) return r;
+  struct fill_ctx {
+    nbody_octree* t;
+    const nbody_state* s;
+    double theta, eps;
+    int kind;
+    hipStream_t st;
+  } ctx{t, s, theta, eps, quadrupole ? int(kOtPotQuad) : eps > 0.0 ? int(kOtPotSoft) : int(kOtPotMono), st};
+  auto fill = [](void* sums, void* p) -> int {
+    const fill_ctx& c = *static_cast<const fill_ctx*>(p);
+    return dispatch(c.s->dtype, c.s->dim, [&](auto tg) {
+      using TG = decltype(tg);
+      using T  = typename TG::type;
+      T e2     = T(0);
+      if (c.kind == kOtPotSoft) (void)check_softening<T>(c.eps, &e2);
+      return ot_potential_run<T, TG::dim>(c.t, c.s, c.theta, c.st, c.kind, e2, static_cast<T*>(sums), T(1));
+    });
+  };
+  return energies_from_sums(s, st, fill, &ctx, kinetic_out, potential_out);
 }

@@ -155,6 +155,20 @@ class Device {
                     "nbody_octree_compute_softened_force");
     else backend_check(nbody_octree_compute_force(octree_, &view_[0], theta, stream()), "nbody_octree_compute_force");
   }
+  // --tree-energy: {kinetic, potential} from a tree built on the current positions (the next step builds its own again), with the
+  // potential of the run's force: monopole, softened or quadrupole (nbody_octree_calc_energies; blocking)
+  std::pair<T, T> octree_energies(double theta, double softening, bool quadrupole) {
+    octree_alloc();
+    octree_clear();
+    octree_compute_bounds();
+    octree_insert();
+    octree_compute_tree();
+    if (quadrupole) octree_compute_quadrupoles();
+    T ke{}, pe{};
+    backend_check(nbody_octree_calc_energies(octree_, &view_[0], theta, softening, quadrupole ? 1 : 0, &ke, &pe, stream()),
+                  "nbody_octree_calc_energies");
+    return {ke, pe};
+  }
   // {tree size, total mass}; also where device-side build errors (depth limit, node pool) surface
   std::pair<std::uint32_t, T> octree_info() {
     std::uint32_t size = 0;

@@ -155,7 +155,7 @@ void run_octree(System<T, D>& sys, Device<T, D>& dev, Options o) {
     if (o.csv_detailed) std::cout << ",force [s],accel [s],clear [s],bbox [s],insert [s],multipoles [s],force approx [s]";
     std::cout << "\n";
   }
-  dev.octree_alloc();
+  dev.octree_alloc();  // (with --tree-energy the first save_all has already made the tree: this is then a no-op)
   if (o.print_info) std::cout << "Tree init complete\n";
   T const theta = T(o.theta);
   seconds_t t_force(0), t_accel(0), t_clear(0), t_bbox(0), t_insert(0), t_tree(0), t_walk(0), t_total(0);

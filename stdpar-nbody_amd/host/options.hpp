@@ -36,6 +36,9 @@ struct Options {
   double softening = 0.0;
   // not in the reference either (nor in --help): --quadrupole, octree cells also add their quadrupole term (octree only, unsoftened)
   bool quadrupole = false;
+  // not in the reference either (nor in --help): --tree-energy, --save energy|all records the octree's energies at the run's --theta,
+  // with the potential that matches the run's force (monopole, --softening or --quadrupole), instead of the exact O(N^2) sum
+  bool tree_energy = false;
 };
 
 namespace detail {
@@ -113,6 +116,8 @@ inline Options parse_options(std::vector<std::string> const& argv) {
       o.softening = v;
     } else if (f == "--quadrupole") {
       o.quadrupole = true;
+    } else if (f == "--tree-energy") {
+      o.tree_energy = true;
     } else if (f == "--print-state") {
       o.print_state = true;
     } else if (f == "--print-info") {
@@ -147,6 +152,14 @@ inline Options parse_options(std::vector<std::string> const& argv) {
   }
   if (o.quadrupole && o.softening > 0.0) {
     std::cerr << "--quadrupole and --softening cannot be combined." << std::endl;
+    std::exit(EXIT_FAILURE);
+  }
+  if (o.tree_energy && o.algorithm != Algorithm::Octree) {
+    std::cerr << "--tree-energy is supported by --algorithm octree only." << std::endl;
+    std::exit(EXIT_FAILURE);
+  }
+  if (o.tree_energy && !o.save_energy) {
+    std::cerr << "--tree-energy changes what --save energy|all records: it needs one of them." << std::endl;
     std::exit(EXIT_FAILURE);
   }
   return o;

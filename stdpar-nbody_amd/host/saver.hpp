@@ -16,7 +16,8 @@ template <typename T, int D>
 class Saver {
  public:
   explicit Saver(Options const& o)
-   : pos_(o.save_pos), energy_(o.save_energy), softening_(o.softening), nbodies_(std::uint32_t(o.size)), nsteps_(std::uint32_t(o.steps)) {
+   : pos_(o.save_pos), energy_(o.save_energy), tree_energy_(o.tree_energy), quadrupole_(o.quadrupole), softening_(o.softening),
+     theta_(o.theta), nbodies_(std::uint32_t(o.size)), nsteps_(std::uint32_t(o.steps)) {
     std::uint32_t const tsz = sizeof(T), dim = D;
     if (pos_) {
       pos_file_.open("positions.bin", std::ios::out | std::ios::binary);
@@ -41,7 +42,7 @@ class Saver {
       pos_file_.write(reinterpret_cast<char const*>(sys.x.data()), std::streamsize(std::size_t(nbodies_) * sizeof(T) * D));
     }
     if (energy_) {
-      auto [kinetic, potential] = dev.calc_energies(softening_);
+      auto [kinetic, potential] = tree_energy_ ? dev.octree_energies(theta_, softening_, quadrupole_) : dev.calc_energies(softening_);
       put(energy_file_, kinetic);
       put(energy_file_, potential);
     }
@@ -53,7 +54,9 @@ class Saver {
     f.write(reinterpret_cast<char const*>(&v), sizeof v);
   }
   bool pos_, energy_;
-  double softening_;  // --softening: the energies of the softened dynamics
+  bool tree_energy_, quadrupole_;  // --tree-energy: the octree's energies at theta_, with the --quadrupole term if the run has it
+  double softening_;               // --softening: the energies of the softened dynamics
+  double theta_;
   std::uint32_t nbodies_, nsteps_;
   std::ofstream pos_file_, energy_file_;
 };
