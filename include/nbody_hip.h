@@ -80,7 +80,9 @@ typedef struct nbody_state {
  * 2.4: Plummer softening: nbody_all_pairs_softened_force, nbody_calc_energies_softened, nbody_octree_compute_softened_force.
  *      Additive, same version: octree quadrupole moments, nbody_octree_compute_quadrupoles, nbody_octree_compute_quadrupole_force,
  *      nbody_octree_read_root_quadrupole.  Additive, same version: octree potentials and energies, nbody_octree_compute_potential,
- *      nbody_octree_compute_softened_potential, nbody_octree_compute_quadrupole_potential, nbody_octree_calc_energies. */
+ *      nbody_octree_compute_softened_potential, nbody_octree_compute_quadrupole_potential, nbody_octree_calc_energies.
+ *      Additive, same version: the fourth-order Hermite integrator for all-pairs, nbody_hermite_create, nbody_hermite_create_on,
+ *      nbody_hermite_destroy, nbody_hermite_force_jerk, nbody_hermite_step, nbody_hermite_read. */
 #define NBODY_HIP_ABI_VERSION 2004
 int nbody_abi_version(void);
 
@@ -316,6 +318,40 @@ int nbody_octree_compute_softened_potential(nbody_octree* t, const nbody_state* 
 int nbody_octree_compute_quadrupole_potential(nbody_octree* t, const nbody_state* s, double theta, void* phi, void* stream);
 int nbody_octree_calc_energies(nbody_octree* t, const nbody_state* s, double theta, double eps, int quadrupole, void* kinetic_out,
                                void* potential_out, void* stream);
+
+/* ---- fourth-order Hermite integrator for all-pairs (no reference counterpart: its only integrator is K3's leapfrog step) ------
+ * The predictor-corrector of Makino & Aarseth (1992) with a fixed step dt and Plummer softening: one evaluation of the acceleration
+ * AND its time derivative (the jerk) per step.  With e2 = fl_T(T(eps) * T(eps)), d = x_j - x_i, u = v_j - v_i, q = |d|^2 + e2:
+ *   a_i = c * sum_j m_j d q^(-3/2),     j_i = c * sum_j m_j (u - 3 (d.u) / q * d) q^(-3/2)
+ * The self pair, and coincident bodies at equal velocity, add 0 because d = 0 (and u = 0): no branch, no index test, as in the
+ * softened K1.  The weight m q^(-3/2) is the softened K1's, operation for operation; 1 / q comes from the same reciprocal square
+ * root (no divide, no second transcendental).  eps obeys the rules of the softening section above; eps = 0 is NOT supported
+ * (NBODY_ERR_ARG): the unsoftened pair needs K1's near-pair forms, which have no jerk twin.  One step from (x, v, a0, j0):
+ *   predict   xp = x + dt v + dt^2/2 a0 + dt^3/6 j0,   vp = v + dt a0 + dt^2/2 j0
+ *   evaluate  (a1, j1) at (xp, vp), all bodies
+ *   correct   v1 = v + dt/2 (a0 + a1) + dt^2/12 (j0 - j1),   x1 = x + dt/2 (v + v1) + dt^2/12 (a0 - a1)
+ *   then      x <- x1, v <- v1, a <- a1, jerk <- j1
+ * (P(EC)^1: the force at the corrected positions is not evaluated again.)  dt is converted to T once, as K3 does.
+ * The handle owns the jerk, the packed predicted state and the partial sums; everything is allocated by create, so the phase calls
+ * allocate nothing and may be recorded into a step graph.  A body's sums are added in an order that follows from sz alone (no
+ * atomics, no waiting between blocks): two runs, an eager step and a replayed recorded one give the same bits.
+ *  - Whole system only: first = 0, count = sz, else NBODY_ERR_ARG.  (Sharding would need an exchange of xp AND vp per step.)
+ *  - Argument errors are found before the device is touched, in this order: s NULL; the state's dtype, dim, window, tuning; eps
+ *    (the message names the softening); h NULL; h made for another dtype, dim or n (all NBODY_ERR_ARG).
+ *  - nbody_hermite_step before nbody_hermite_force_jerk on that handle: NBODY_ERR_STATE.  A handle used with a stream of another
+ *    device: NBODY_ERR_ARG.  Every entry switches to the handle's device and restores the caller's.
+ *  - nbody_hermite_read and nbody_hermite_create(_on) between nbody_graph_begin and nbody_graph_end: NBODY_ERR_STATE. */
+typedef struct nbody_hermite nbody_hermite;
+int  nbody_hermite_create(nbody_hermite** out, int dtype, int dim, uint32_t n);                /* on the current device */
+int  nbody_hermite_create_on(nbody_hermite** out, int dtype, int dim, uint32_t n, int device); /* device < 0: the current one */
+void nbody_hermite_destroy(nbody_hermite* h);
+/* a = s->a and the handle's jerk at (s->x, s->v): starts a run, or restarts it after an upload.  Asynchronous, recordable. */
+int  nbody_hermite_force_jerk(nbody_hermite* h, const nbody_state* s, double eps, void* stream);
+/* One step as above: reads s->x, s->v, s->a and the jerk, rewrites them.  s->ao is neither read nor written.  Asynchronous, recordable. */
+int  nbody_hermite_step(nbody_hermite* h, const nbody_state* s, double eps, void* stream);
+/* Blocking.  what: 0 jerk T[n][D] | 1 predicted x T[n][D] | 2 predicted v T[n][D] of the last step (after force_jerk: x and v as
+ * they were evaluated).  bytes must be n * D * sizeof(T) (NBODY_ERR_ARG); NBODY_ERR_STATE before the first force_jerk. */
+int  nbody_hermite_read(nbody_hermite* h, int what, void* host_out, size_t bytes, void* stream);
 
 /* ---- owning context (device mirrors of a host System), used by the C++ CLI host ------------------ */
 

@@ -60,6 +60,8 @@ ABI_SYMBOLS = [
     "nbody_octree_compute_quadrupoles", "nbody_octree_compute_quadrupole_force", "nbody_octree_read_root_quadrupole",
     "nbody_octree_compute_potential", "nbody_octree_compute_softened_potential", "nbody_octree_compute_quadrupole_potential",
     "nbody_octree_calc_energies",
+    "nbody_hermite_create", "nbody_hermite_create_on", "nbody_hermite_destroy", "nbody_hermite_force_jerk", "nbody_hermite_step",
+    "nbody_hermite_read",
 ]
 ABI_MAJOR = 2
 COMM_ID_BYTES = 128
@@ -94,6 +96,9 @@ def lib():
         L.nbody_octree_compute_softened_potential.argtypes = [vp, vp, d, d, vp, vp]
         L.nbody_octree_compute_quadrupole_potential.argtypes = [vp, vp, d, vp, vp]
         L.nbody_octree_calc_energies.argtypes = [vp, vp, d, d, C.c_int, vp, vp, vp]
+        L.nbody_hermite_force_jerk.argtypes = [vp, vp, d, vp]
+        L.nbody_hermite_step.argtypes = [vp, vp, d, vp]
+        L.nbody_hermite_read.argtypes = [vp, C.c_int, vp, C.c_size_t, vp]
         _lib = L
     return _lib
 
@@ -418,6 +423,41 @@ class Octree:
         return out
 
 
+class Hermite:
+    """Fourth-order Hermite integrator for all-pairs (nbody_hermite_*): owns the jerk, the packed predicted state and the partial sums."""
+
+    def __init__(self, dtype, dim, n, device=-1):
+        """device: where the handle's buffers live (-1: the calling thread's current device)."""
+        self.h = C.c_void_p()
+        self.dtype, self.dim, self.n = dtype, dim, n
+        _check(lib().nbody_hermite_create_on(C.byref(self.h), dtype, dim, C.c_uint32(n), device))
+
+    def close(self):
+        if self.h:
+            lib().nbody_hermite_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def force_jerk(self, st, eps, stream=None):
+        """a = st.a and the handle's jerk at (st.x, st.v), Plummer softening eps > 0: starts (or restarts) a run."""
+        _check(lib().nbody_hermite_force_jerk(self.h, C.byref(st), eps, stream))
+
+    def step(self, st, eps, stream=None):
+        """One predictor-corrector step of st.dt: rewrites st.x, st.v, st.a and the jerk; st.ao is untouched.  Recordable."""
+        _check(lib().nbody_hermite_step(self.h, C.byref(st), eps, stream))
+
+    def read(self, what, stream=None):
+        """0 the jerk, 1 the predicted positions, 2 the predicted velocities of the last step: (n, dim) of T (blocking)."""
+        out = np.zeros((self.n, self.dim), np_dtype(self.dtype))
+        _check(lib().nbody_hermite_read(self.h, what, _p(out), out.nbytes, stream))
+        return out
+
+
 class DeviceSystem:
     """Owning device mirror of a System<T,N>; phase methods mirror the calls of the reference drivers."""
 
@@ -428,6 +468,7 @@ class DeviceSystem:
         self.stream = lib().nbody_ctx_stream(self.h)
         self._bvh = None
         self._octree = None
+        self._hermite = None
 
     @classmethod
     def from_host(cls, hs, device=0):
@@ -442,6 +483,9 @@ class DeviceSystem:
         if self._octree is not None:
             self._octree.close()
             self._octree = None
+        if self._hermite is not None:
+            self._hermite.close()
+            self._hermite = None
         if self.h:
             lib().nbody_destroy(self.h)
             self.h = C.c_void_p()
@@ -504,6 +548,25 @@ class DeviceSystem:
     def accelerate_step(self, first=0, count=None):
         st = self.state(first, count)
         _check(lib().nbody_accelerate_step(C.byref(st), C.c_void_p(self.stream)))
+
+    # fourth-order Hermite (no reference counterpart)
+    @property
+    def hermite(self):
+        if self._hermite is None:
+            self._hermite = Hermite(self.dtype, self.dim, self.n, self.device)
+        return self._hermite
+
+    def hermite_start(self, eps):
+        """Acceleration and jerk of the state as it is (nbody_hermite_force_jerk): before the first hermite_step and after an upload."""
+        self.hermite.force_jerk(self.state(), eps, self.stream)
+
+    def hermite_step(self, eps):
+        """One Hermite step of dt (nbody_hermite_step); a StepGraph may record it (after hermite_start has been called)."""
+        self.hermite.step(self.state(), eps, self.stream)
+
+    def hermite_jerk(self):
+        """The jerk of the last hermite_start / hermite_step, (n, dim) of T (blocking)."""
+        return self.hermite.read(0, self.stream)
 
     def calc_energies(self, softening=0.0):
         """(kinetic, potential) as in System::calc_energies (src/system.h:62-79); blocking.  softening > 0: the potential of the

@@ -62,6 +62,10 @@ inline unsigned long long capture_id(hipStream_t st) {
   return id ? id : ~0ull;
 }
 
+// context.hip: captures begun with nbody_graph_begin on the calling thread and not yet ended (they are thread-local captures): an
+// entry that allocates and has no stream to ask refuses while this is not 0
+int captures_on_this_thread();
+
 // device a stream was created on; the NULL stream belongs to whatever device is current
 inline int stream_device(hipStream_t st) {
   if (st == nullptr) return current_device();

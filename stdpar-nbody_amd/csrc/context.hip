@@ -8,6 +8,9 @@
 namespace nbody {
 
 static thread_local std::string g_last_error;
+static thread_local int g_captures = 0;  // nbody_graph_begin .. nbody_graph_end on this thread
+
+int captures_on_this_thread() { return g_captures; }
 
 void set_error(const char* fmt, ...) {
   char buf[1024];
@@ -198,6 +201,7 @@ extern "C" int nbody_graph_begin(void* stream) {
   NB_ARG(stream != nullptr, "graph capture needs an explicit (non-default) stream");
   device_guard guard(stream_device(as_stream(stream)));
   NB_HIP(hipStreamBeginCapture(as_stream(stream), hipStreamCaptureModeThreadLocal));
+  ++g_captures;
   return NBODY_OK;
 }
 
@@ -206,6 +210,7 @@ extern "C" int nbody_graph_end(void* stream, nbody_graph** out) {
   *out = nullptr;
   device_guard guard(stream_device(as_stream(stream)));
   hipGraph_t graph = nullptr;
+  if (g_captures > 0) --g_captures;
   NB_HIP(hipStreamEndCapture(as_stream(stream), &graph));
   hipGraphExec_t exec = nullptr;
   hipError_t e        = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);

@@ -45,6 +45,7 @@ class Device {
     push();
   }
   ~Device() {
+    if (hermite_) nbody_hermite_destroy(hermite_);
     if (octree_) nbody_octree_destroy(octree_);
     if (tree_) nbody_bvh_destroy(tree_);
     for (auto* c : comm_) nbody_comm_destroy(c);
@@ -101,6 +102,14 @@ class Device {
       backend_check(nbody_allgather_positions(comm_[g], &view_[g], stream(g)), "nbody_allgather_positions");
     if (multi()) backend_check(nbody_comm_group_end(), "nbody_comm_group_end");
   }
+
+  // --integrator hermite (no reference counterpart): acceleration and jerk of the uploaded state once, then one call per step
+  void hermite_start(double eps) {
+    single("--integrator hermite");
+    if (!hermite_) backend_check(nbody_hermite_create_on(&hermite_, dtype, D, host_.n, 0), "nbody_hermite_create_on");
+    backend_check(nbody_hermite_force_jerk(hermite_, &view_[0], eps, stream()), "nbody_hermite_force_jerk");
+  }
+  void hermite_step(double eps) { backend_check(nbody_hermite_step(hermite_, &view_[0], eps, stream()), "nbody_hermite_step"); }
 
   // System::calc_energies (src/system.h:62-79) on the device: {kinetic, potential}
   // softening > 0: the potential of the softened force (nbody_calc_energies_softened)
@@ -199,6 +208,7 @@ class Device {
   std::vector<nbody_state> view_;
   nbody_bvh* tree_ = nullptr;
   nbody_octree* octree_ = nullptr;
+  nbody_hermite* hermite_ = nullptr;
 };
 
 }  // namespace nb

@@ -11,6 +11,7 @@ namespace nb {
 
 enum class Workload { Uniform, Plummer, Galaxy, Load };
 enum class Algorithm { AllPairs, AllPairsCollapsed, Octree, Bvh };
+enum class Integrator { Leapfrog, Hermite };
 
 struct Options {
   std::size_t size         = 1000;
@@ -39,6 +40,10 @@ struct Options {
   // not in the reference either (nor in --help): --tree-energy, --save energy|all records the octree's energies at the run's --theta,
   // with the potential that matches the run's force (monopole, --softening or --quadrupole), instead of the exact O(N^2) sum
   bool tree_energy = false;
+  // not in the reference either (nor in --help): --integrator leapfrog|hermite.  leapfrog (default): the reference's step, the same
+  // run as without the flag.  hermite: the fourth-order predictor-corrector with force + jerk (nbody_hermite_*); all-pairs on one
+  // GPU with --softening EPS > 0 only
+  Integrator integrator = Integrator::Leapfrog;
 };
 
 namespace detail {
@@ -114,6 +119,11 @@ inline Options parse_options(std::vector<std::string> const& argv) {
         std::exit(EXIT_FAILURE);
       }
       o.softening = v;
+    } else if (f == "--integrator") {
+      auto const& i = value();
+      if (i == "leapfrog") o.integrator = Integrator::Leapfrog;
+      else if (i == "hermite") o.integrator = Integrator::Hermite;
+      else detail::reject("integrator", i, "leapfrog (default), hermite");
     } else if (f == "--quadrupole") {
       o.quadrupole = true;
     } else if (f == "--tree-energy") {
@@ -140,6 +150,20 @@ inline Options parse_options(std::vector<std::string> const& argv) {
   if (o.csv_detailed && o.csv_total) {
     std::cerr << "Cannot capture a CSV detailed and coarse trace in the same run. Specify one or the other." << std::endl;
     std::exit(EXIT_FAILURE);
+  }
+  if (o.integrator == Integrator::Hermite) {
+    if (o.algorithm != Algorithm::AllPairs) {
+      std::cerr << "--integrator hermite is supported by --algorithm all-pairs only." << std::endl;
+      std::exit(EXIT_FAILURE);
+    }
+    if (!(o.softening > 0.0)) {
+      std::cerr << "--integrator hermite needs --softening EPS with EPS > 0." << std::endl;
+      std::exit(EXIT_FAILURE);
+    }
+    if (o.gpus_given) {
+      std::cerr << "--integrator hermite runs on one GPU: it cannot be combined with --gpus." << std::endl;
+      std::exit(EXIT_FAILURE);
+    }
   }
   if (o.softening > 0.0 && (o.algorithm == Algorithm::Bvh || o.algorithm == Algorithm::AllPairsCollapsed)) {
     std::cerr << "--softening is supported by --algorithm all-pairs and octree only, not by "
