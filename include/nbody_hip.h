@@ -82,7 +82,9 @@ typedef struct nbody_state {
  *      nbody_octree_read_root_quadrupole.  Additive, same version: octree potentials and energies, nbody_octree_compute_potential,
  *      nbody_octree_compute_softened_potential, nbody_octree_compute_quadrupole_potential, nbody_octree_calc_energies.
  *      Additive, same version: the fourth-order Hermite integrator for all-pairs, nbody_hermite_create, nbody_hermite_create_on,
- *      nbody_hermite_destroy, nbody_hermite_force_jerk, nbody_hermite_step, nbody_hermite_read. */
+ *      nbody_hermite_destroy, nbody_hermite_force_jerk, nbody_hermite_step, nbody_hermite_read.  Additive, same version: block
+ *      (individual) time steps for it, nbody_hermite_block_start, nbody_hermite_block_step, nbody_hermite_block_advance,
+ *      nbody_hermite_block_read. */
 #define NBODY_HIP_ABI_VERSION 2004
 int nbody_abi_version(void);
 
@@ -352,6 +354,45 @@ int  nbody_hermite_step(nbody_hermite* h, const nbody_state* s, double eps, void
 /* Blocking.  what: 0 jerk T[n][D] | 1 predicted x T[n][D] | 2 predicted v T[n][D] of the last step (after force_jerk: x and v as
  * they were evaluated).  bytes must be n * D * sizeof(T) (NBODY_ERR_ARG); NBODY_ERR_STATE before the first force_jerk. */
 int  nbody_hermite_read(nbody_hermite* h, int what, void* host_out, size_t bytes, void* stream);
+
+/* ---- block (individual) time steps for the Hermite integrator: the Aarseth criterion on power-of-two steps -------------------
+ * dt_max = s->dt is the largest step and the synchronisation interval, L = max_level (0 .. 20), tick = dt_max / 2^L.  Body i has a
+ * level l_i in [0, L], a step of 2^(L - l_i) ticks and a last-update time tau_i in ticks since the start of the current interval
+ * (integers: time accumulates no rounding); tau_i is always a multiple of the body's step.
+ *   start       a and the jerk of all bodies (nbody_hermite_force_jerk); want_i = eta_start |a_i| / |j_i| (|j_i| = 0: level 0);
+ *               l_i = the smallest level with dt_max 2^-l <= want_i, clamped to [0, L]; tau_i = 0.
+ *   block step  tau_next = min_i(tau_i + step_i); the active set is every i with tau_i + step_i == tau_next, in ascending body
+ *               order.  ALL bodies are predicted to tau_next with h_i = T(tau_next - tau_i) * T(tick) (the predictor above); a and
+ *               the jerk of the ACTIVE bodies only, against all N predicted bodies; for each active body the corrector above with
+ *               h = step_i * tick, then with a0, j0 the old and a1, j1 the new values
+ *                 a2 = (-6 (a0 - a1) - h (4 j0 + 2 j1)) / h^2,  a3 = (12 (a0 - a1) + 6 h (j0 + j1)) / h^3,  a2 <- a2 + h a3
+ *                 want = sqrt(eta (|a1| |a2| + |j1|^2) / (|j1| |a3| + |a2|^2))            (denominator 0: no limit)
+ *               (1 / h is 2^l_i * fl_T(1 / T(dt_max)), an exact scaling).  New level: if want < h, the smallest level deeper than
+ *               l_i whose step is <= want, at most L; else if want >= 2 h, l_i > 0 and tau_next is a multiple of twice the body's
+ *               step, l_i - 1 (one doubling at most); else unchanged.  tau_i = tau_next.  Inactive bodies are not written.
+ *   At tau_next = 2^L every body is active, the system is synchronous at t + dt_max, and tau starts again from 0.
+ * With max_level = 0 a block step is nbody_hermite_step, bit for bit.  The active list is a stable compaction (no atomics decide a
+ * slot) and the launch shape of the active set's force + jerk follows from (sz, n_active) alone, chunks added in chunk order: two
+ * runs from the same state give the same bits.  The schedule arrays are allocated by the first block_start on a handle.
+ *  - Argument errors before the device is touched, in this order: the state as for nbody_hermite_step; eps; eta / eta_start (finite,
+ *    > 0, also as T); max_level (0 .. 20); h NULL; h made for another dtype, dim or n; s->dt (finite, > 0, tick and 1 / dt normal
+ *    numbers of T); for a step, s->dt other than block_start's (all NBODY_ERR_ARG).
+ *  - block_start allocates on first use and block_step / block_advance read the size of the active set back (8 bytes, blocking):
+ *    all of them, and block_read, return NBODY_ERR_STATE between nbody_graph_begin and nbody_graph_end, and leave the capture usable.
+ *  - block_step / block_advance / block_read before block_start on that handle, or after a later nbody_hermite_force_jerk (which
+ *    restarts the fixed-step run): NBODY_ERR_STATE.  nbody_hermite_step may follow a block_advance (the system is synchronous). */
+int  nbody_hermite_block_start(nbody_hermite* h, const nbody_state* s, double eps, double eta_start, int max_level, void* stream);
+/* One block step.  *n_active: the size of its active set, *tau: its tau_next in ticks (2^max_level: the interval is complete);
+ * either may be NULL.  Blocking for the schedule, asynchronous for the force + jerk and the corrector. */
+int  nbody_hermite_block_step(nbody_hermite* h, const nbody_state* s, double eps, double eta, void* stream, uint32_t* n_active,
+                              uint32_t* tau);
+/* Block steps until the system is synchronous at t + s->dt.  *block_steps: how many, *body_steps: the sum of their active sets
+ * (the force + jerk evaluations made); either may be NULL. */
+int  nbody_hermite_block_advance(nbody_hermite* h, const nbody_state* s, double eps, double eta, void* stream, uint64_t* block_steps,
+                                 uint64_t* body_steps);
+/* Blocking.  what: 0 levels int32[n] | 1 tau_i uint32[n] | 2 the active list of the last block step, uint32[n_active] ascending.
+ * bytes must match (NBODY_ERR_ARG). */
+int  nbody_hermite_block_read(nbody_hermite* h, int what, void* host_out, size_t bytes, void* stream);
 
 /* ---- owning context (device mirrors of a host System), used by the C++ CLI host ------------------ */
 

@@ -62,6 +62,7 @@ ABI_SYMBOLS = [
     "nbody_octree_calc_energies",
     "nbody_hermite_create", "nbody_hermite_create_on", "nbody_hermite_destroy", "nbody_hermite_force_jerk", "nbody_hermite_step",
     "nbody_hermite_read",
+    "nbody_hermite_block_start", "nbody_hermite_block_step", "nbody_hermite_block_advance", "nbody_hermite_block_read",
 ]
 ABI_MAJOR = 2
 COMM_ID_BYTES = 128
@@ -99,6 +100,10 @@ def lib():
         L.nbody_hermite_force_jerk.argtypes = [vp, vp, d, vp]
         L.nbody_hermite_step.argtypes = [vp, vp, d, vp]
         L.nbody_hermite_read.argtypes = [vp, C.c_int, vp, C.c_size_t, vp]
+        L.nbody_hermite_block_start.argtypes = [vp, vp, d, d, C.c_int, vp]
+        L.nbody_hermite_block_step.argtypes = [vp, vp, d, d, vp, vp, vp]
+        L.nbody_hermite_block_advance.argtypes = [vp, vp, d, d, vp, vp, vp]
+        L.nbody_hermite_block_read.argtypes = [vp, C.c_int, vp, C.c_size_t, vp]
         _lib = L
     return _lib
 
@@ -457,6 +462,29 @@ class Hermite:
         _check(lib().nbody_hermite_read(self.h, what, _p(out), out.nbytes, stream))
         return out
 
+    # block (individual) time steps
+    def block_start(self, st, eps, eta_start, max_level, stream=None):
+        """a, the jerk and the first levels (nbody_hermite_block_start): st.dt is the largest step, st.dt / 2^max_level the smallest."""
+        _check(lib().nbody_hermite_block_start(self.h, C.byref(st), eps, eta_start, max_level, stream))
+
+    def block_step(self, st, eps, eta, stream=None):
+        """One block step: (n_active, tau_next in ticks).  Blocking for the schedule."""
+        na, tau = C.c_uint32(), C.c_uint32()
+        _check(lib().nbody_hermite_block_step(self.h, C.byref(st), eps, eta, stream, C.byref(na), C.byref(tau)))
+        return na.value, tau.value
+
+    def block_advance(self, st, eps, eta, stream=None):
+        """Block steps until the system is synchronous at t + st.dt: (block steps, body steps)."""
+        bs, bod = C.c_uint64(), C.c_uint64()
+        _check(lib().nbody_hermite_block_advance(self.h, C.byref(st), eps, eta, stream, C.byref(bs), C.byref(bod)))
+        return bs.value, bod.value
+
+    def block_read(self, what, stream=None, count=None):
+        """0 the levels (int32), 1 tau_i in ticks (uint32), 2 the active list of the last block step (uint32, `count` of them)."""
+        out = np.zeros(self.n if what != 2 else count, np.int32 if what == 0 else np.uint32)
+        _check(lib().nbody_hermite_block_read(self.h, what, _p(out), out.nbytes, stream))
+        return out
+
 
 class DeviceSystem:
     """Owning device mirror of a System<T,N>; phase methods mirror the calls of the reference drivers."""
@@ -567,6 +595,26 @@ class DeviceSystem:
     def hermite_jerk(self):
         """The jerk of the last hermite_start / hermite_step, (n, dim) of T (blocking)."""
         return self.hermite.read(0, self.stream)
+
+    def hermite_block_start(self, eps, eta_start=0.01, max_level=12):
+        """Starts a run with block time steps (nbody_hermite_block_start): dt is the largest step, dt / 2^max_level the smallest."""
+        self.hermite.block_start(self.state(), eps, eta_start, max_level, self.stream)
+
+    def hermite_block_step(self, eps, eta):
+        """One block step: (n_active, tau_next in ticks); tau_next == 2^max_level completes the interval of dt."""
+        return self.hermite.block_step(self.state(), eps, eta, self.stream)
+
+    def hermite_block_advance(self, eps, eta):
+        """Block steps until the system is synchronous at t + dt: (block steps, body steps)."""
+        return self.hermite.block_advance(self.state(), eps, eta, self.stream)
+
+    def hermite_block_levels(self):
+        """(levels, tau) of the bodies, int32 and uint32 (blocking)."""
+        return self.hermite.block_read(0, self.stream), self.hermite.block_read(1, self.stream)
+
+    def hermite_block_active(self, n_active):
+        """The active list of the last block step (ascending body indices); n_active as hermite_block_step returned it."""
+        return self.hermite.block_read(2, self.stream, n_active)
 
     def calc_energies(self, softening=0.0):
         """(kinetic, potential) as in System::calc_energies (src/system.h:62-79); blocking.  softening > 0: the potential of the

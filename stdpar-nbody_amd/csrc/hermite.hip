@@ -13,6 +13,8 @@
 // The rounding order of a body's sums (slices of a tile by wave, tiles in order, waves in order, chunks in order) follows from sz
 // alone: hermite_plan reads nothing else — not the device, not the CU count — so two runs, an eager step and a replayed one, and
 // a handle destroyed and made again give the same bits.  No atomics on a or the jerk, no waiting between blocks.
+// Block (individual) time steps on the same handle: hermite_block.inc, included below; the body of the force + jerk kernel is
+// hermite_pair_body.inc, shared with the kernel of the active set.
 #include "common.hpp"
 
 namespace nbody {
@@ -155,104 +157,9 @@ __device__ __forceinline__ void pair_batch_hermite(T (&acc)[R][D], T (&jacc)[R][
 template <typename T, int D, int R>
 __global__ __launch_bounds__(kHBlock) void hermite_force_jerk_kernel(const hsrc_rec<T>* __restrict__ recs, T* __restrict__ part, T e2,
                                                                      uint32_t n, uint32_t ntiles, uint32_t tiles_per_chunk) {
-  using rec_t       = hsrc_rec<T>;
-  constexpr int SUB = kHTile / kHWaves;         // records of a tile one wave takes
-  constexpr int U   = (sizeof(T) == 8 ? 2 : 4) / R;  // records a batch: 2 pairs in flight per lane in double, 4 in float
-  constexpr int NP  = (kHWaves - 1) * R * 2 * D * 64;  // the other waves' sums, handed over through LDS
-  constexpr size_t kTileBytes = sizeof(rec_t) * kHTile, kPartBytes = sizeof(T) * NP;
-  __shared__ __attribute__((aligned(64))) unsigned char smem[kTileBytes > kPartBytes ? kTileBytes : kPartBytes];
-  rec_t* tile = reinterpret_cast<rec_t*>(smem);
-  T* hand     = reinterpret_cast<T*>(smem);  // after the last tile has been consumed
-
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-
-  T xi[R][D], vi[R][D], acc[R][D], jacc[R][D];
-  uint32_t ti[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    ti[r]            = blockIdx.x * (64 * R) + r * 64 + lane;
-    const uint32_t i = ti[r] < n ? ti[r] : 0u;  // clamp: out-of-range lanes compute, never store
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-      xi[r][k]   = recs[i].p[k];
-      vi[r][k]   = recs[i].v[k];
-      acc[r][k]  = T(0);
-      jacc[r][k] = T(0);
-    }
-  }
-
-  const uint32_t t0 = blockIdx.y * tiles_per_chunk;
-  const uint32_t t1 = t0 + tiles_per_chunk < ntiles ? t0 + tiles_per_chunk : ntiles;
-  const pair_consts<T> pc;
-
-  // one record per lane, as 8 values: a 64-byte struct copy is left in private memory (scratch) by the compiler
-  const T* flat = reinterpret_cast<const T*>(recs);
-  T* tflat      = reinterpret_cast<T*>(smem);
-  T stage[8];
-  auto stage_load = [&](uint32_t t) {  // the record array is padded to whole tiles
-#pragma unroll
-    for (int k = 0; k < 8; ++k) stage[k] = flat[(uint64_t(t) * kHTile + threadIdx.x) * 8 + k];
-  };
-  stage_load(t0);
-  for (uint32_t t = t0; t < t1; ++t) {
-    __syncthreads();  // every wave is done reading the previous tile
-#pragma unroll
-    for (int k = 0; k < 8; ++k) tflat[threadIdx.x * 8 + k] = stage[k];
-    __syncthreads();
-    if (t + 1 < t1) stage_load(t + 1);  // in flight while this tile is consumed
-
-    const rec_t* src = &tile[wave * SUB];
-#pragma unroll 1
-    for (int jj = 0; jj < SUB; jj += U) {
-      rec_t s[U];  // field by field: a 64-byte struct copy is left in private memory (scratch) by the compiler
-#pragma unroll
-      for (int b = 0; b < U; ++b) {  // wave-uniform address: LDS broadcast
-#pragma unroll
-        for (int k = 0; k < D; ++k) {
-          s[b].p[k] = src[jj + b].p[k];
-          s[b].v[k] = src[jj + b].v[k];
-        }
-        s[b].m = src[jj + b].m;
-      }
-      pair_batch_hermite<T, D, R, U>(acc, jacc, xi, vi, s, pc, e2);
-    }
-  }
-
-  // the four slices in wave order
-  __syncthreads();
-  if (wave > 0) {
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-      for (int k = 0; k < D; ++k) {
-        hand[((((wave - 1) * R + r) * 2 * D) + k) * 64 + lane]     = acc[r][k];
-        hand[((((wave - 1) * R + r) * 2 * D) + D + k) * 64 + lane] = jacc[r][k];
-      }
-  }
-  __syncthreads();
-  if (wave == 0) {
-#pragma unroll
-    for (int p = 1; p < kHWaves; ++p)
-#pragma unroll
-      for (int r = 0; r < R; ++r)
-#pragma unroll
-        for (int k = 0; k < D; ++k) {
-          acc[r][k] += hand[((((p - 1) * R + r) * 2 * D) + k) * 64 + lane];
-          jacc[r][k] += hand[((((p - 1) * R + r) * 2 * D) + D + k) * 64 + lane];
-        }
-    T* out = part + uint64_t(blockIdx.y) * (2 * D) * n;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      if (ti[r] < n) {
-#pragma unroll
-        for (int k = 0; k < D; ++k) {
-          out[uint64_t(k) * n + ti[r]]     = acc[r][k];
-          out[uint64_t(D + k) * n + ti[r]] = jacc[r][k];
-        }
-      }
-    }
-  }
+#define HFJ_GATHER 0
+#include "hermite_pair_body.inc"
+#undef HFJ_GATHER
 }
 
 // ---- correct -------------------------------------------------------------------------------------------------------------------
@@ -298,6 +205,20 @@ struct nbody_hermite {
   void* part = nullptr;  // T[chunks][2 D][n]
   void* jerk = nullptr;  // T[n][D]
   bool started = false;  // nbody_hermite_force_jerk has run (host call order, which a recorded step replays)
+  // block time steps (hermite_block.inc): allocated by the first nbody_hermite_block_start
+  int32_t* blev    = nullptr;  // level l_i, [n]
+  uint32_t* btau   = nullptr;  // last update time tau_i in ticks, [n]
+  uint32_t* bact   = nullptr;  // active list of the block step in flight, ascending, [n]
+  uint32_t* bcount = nullptr;  // active bodies per schedule strip, then its exclusive scan, [bstrips]
+  uint32_t* bsched = nullptr;  // {running minimum, n_act, tau_next, -}
+  uint32_t* bpin   = nullptr;  // pinned, mapped host memory: {n_act, tau_next}, written by the schedule
+  uint32_t* bpin_dev = nullptr;  // its device address
+  void* bpart      = nullptr;  // T[bslots][2 D]: partial sums of the active set, sized for the worst n_act
+  uint32_t bstrips = 0, blast = 0;  // blast: n_act of the last block step
+  uint64_t bslots  = 0;
+  int blevels      = 0;      // max_level of the last block_start
+  double bdt       = 0.0;    // its s->dt
+  bool block_on    = false;  // nbody_hermite_block_start has run and no nbody_hermite_force_jerk since
 };
 
 namespace nbody {
@@ -346,11 +267,14 @@ static int hermite_call(nbody_hermite* h, const nbody_state* s, double eps, void
     const int r = h->plan.R == 2 ? hermite_launch<T, D, 2, START>(h, s, e2, as_stream(stream))
                                  : hermite_launch<T, D, 1, START>(h, s, e2, as_stream(stream));
     if (START && r == NBODY_OK) h->started = true;
+    if (START) h->block_on = false;  // levels and tau belong to the state nbody_hermite_block_start saw
     return r;
   });
 }
 
 }  // namespace nbody
+
+#include "hermite_block.inc"
 
 extern "C" int nbody_hermite_create(nbody_hermite** out, int dtype, int dim, uint32_t n) {
   return nbody_hermite_create_on(out, dtype, dim, n, -1);
@@ -400,6 +324,7 @@ extern "C" void nbody_hermite_destroy(nbody_hermite* h) {
   (void)hipFree(h->recs);
   (void)hipFree(h->part);
   (void)hipFree(h->jerk);
+  hermite_block_free(h);
   delete h;
 }
 

@@ -110,6 +110,15 @@ class Device {
     backend_check(nbody_hermite_force_jerk(hermite_, &view_[0], eps, stream()), "nbody_hermite_force_jerk");
   }
   void hermite_step(double eps) { backend_check(nbody_hermite_step(hermite_, &view_[0], eps, stream()), "nbody_hermite_step"); }
+  // --hermite-eta ETA: block time steps; one call advances the system by dt (as many block steps as its levels ask for)
+  void hermite_block_start(double eps, double eta_start, int max_level) {
+    single("--hermite-eta");
+    if (!hermite_) backend_check(nbody_hermite_create_on(&hermite_, dtype, D, host_.n, 0), "nbody_hermite_create_on");
+    backend_check(nbody_hermite_block_start(hermite_, &view_[0], eps, eta_start, max_level, stream()), "nbody_hermite_block_start");
+  }
+  void hermite_block_advance(double eps, double eta) {
+    backend_check(nbody_hermite_block_advance(hermite_, &view_[0], eps, eta, stream(), nullptr, nullptr), "nbody_hermite_block_advance");
+  }
 
   // System::calc_energies (src/system.h:62-79) on the device: {kinetic, potential}
   // softening > 0: the potential of the softened force (nbody_calc_energies_softened)

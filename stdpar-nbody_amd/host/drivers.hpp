@@ -52,14 +52,32 @@ void run_all_pairs(System<T, D>& sys, Device<T, D>& dev, Options o, char const* 
   // --integrator hermite: acceleration and jerk of the starting state once, then one predictor-corrector call per step; the step has
   // no separate accelerate phase (its time goes to the force column, accel stays 0.00)
   bool const hermite = o.integrator == Integrator::Hermite && !collapsed;
-  if (hermite) {
+  // --hermite-eta: block time steps.  One step of the run is one advance of dt; it reads the size of every active set back, so it
+  // is not recorded: warm-up and timed steps are plain calls (eta_start = ETA / 2 for the first levels, which have no a2, a3 yet)
+  bool const block = hermite && o.hermite_eta > 0.0;
+  if (block) {
+    dev.hermite_block_start(o.softening, 0.5 * o.hermite_eta, o.hermite_levels);
+    dev.sync();
+  } else if (hermite) {
     dev.hermite_start(o.softening);
     dev.sync();
   }
-  if (hermite && o.csv_detailed) {
+  auto hermite_one = [&] {
+    if (block) dev.hermite_block_advance(o.softening, o.hermite_eta);
+    else dev.hermite_step(o.softening);
+  };
+  if (block && !o.csv_detailed) {
+    for (std::size_t step = 0; step < o.warmup_steps; ++step) hermite_one();
+    dev.sync();
+    t_total = timed([&] {
+      for (std::size_t step = o.warmup_steps; step < o.steps; ++step) hermite_one();
+      dev.sync();
+    });
+    o.steps -= o.warmup_steps;
+  } else if (hermite && o.csv_detailed) {
     t_total = timed([&] {
       for (std::size_t step = 0; step < o.steps; ++step) {
-        t_force += timed([&] { dev.hermite_step(o.softening); dev.sync(); });
+        t_force += timed([&] { hermite_one(); dev.sync(); });
         saver.save_all(sys, dev);
       }
     });

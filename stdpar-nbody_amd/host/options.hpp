@@ -44,6 +44,12 @@ struct Options {
   // run as without the flag.  hermite: the fourth-order predictor-corrector with force + jerk (nbody_hermite_*); all-pairs on one
   // GPU with --softening EPS > 0 only
   Integrator integrator = Integrator::Leapfrog;
+  // not in the reference either (nor in --help): --hermite-eta ETA (with --integrator hermite only, ETA > 0) switches the Hermite
+  // integrator to block time steps with accuracy parameter ETA (nbody_hermite_block_*): every step of the run advances the system by
+  // dt in as many block steps as the bodies' levels ask for; --hermite-levels L (0 .. 20, default 12): the smallest step is dt / 2^L
+  double hermite_eta = 0.0;  // 0: fixed step
+  int hermite_levels = 12;
+  bool hermite_levels_given = false;
 };
 
 namespace detail {
@@ -124,6 +130,25 @@ inline Options parse_options(std::vector<std::string> const& argv) {
       if (i == "leapfrog") o.integrator = Integrator::Leapfrog;
       else if (i == "hermite") o.integrator = Integrator::Hermite;
       else detail::reject("integrator", i, "leapfrog (default), hermite");
+    } else if (f == "--hermite-eta") {
+      auto const& e = value();
+      char* end     = nullptr;
+      double const v = std::strtod(e.c_str(), &end);
+      if (e.empty() || end != e.c_str() + e.size() || !std::isfinite(v) || !(v > 0.0)) {
+        std::cerr << "--hermite-eta needs a finite accuracy parameter > 0, got \"" << e << "\"." << std::endl;
+        std::exit(EXIT_FAILURE);
+      }
+      o.hermite_eta = v;
+    } else if (f == "--hermite-levels") {
+      auto const& l = value();
+      char* end     = nullptr;
+      long const v  = std::strtol(l.c_str(), &end, 10);
+      if (l.empty() || end != l.c_str() + l.size() || v < 0 || v > 20) {
+        std::cerr << "--hermite-levels needs a level count in 0 .. 20, got \"" << l << "\"." << std::endl;
+        std::exit(EXIT_FAILURE);
+      }
+      o.hermite_levels       = int(v);
+      o.hermite_levels_given = true;
     } else if (f == "--quadrupole") {
       o.quadrupole = true;
     } else if (f == "--tree-energy") {
@@ -164,6 +189,14 @@ inline Options parse_options(std::vector<std::string> const& argv) {
       std::cerr << "--integrator hermite runs on one GPU: it cannot be combined with --gpus." << std::endl;
       std::exit(EXIT_FAILURE);
     }
+  }
+  if (o.hermite_eta > 0.0 && o.integrator != Integrator::Hermite) {
+    std::cerr << "--hermite-eta needs --integrator hermite." << std::endl;
+    std::exit(EXIT_FAILURE);
+  }
+  if (o.hermite_levels_given && !(o.hermite_eta > 0.0)) {
+    std::cerr << "--hermite-levels needs --hermite-eta ETA." << std::endl;
+    std::exit(EXIT_FAILURE);
   }
   if (o.softening > 0.0 && (o.algorithm == Algorithm::Bvh || o.algorithm == Algorithm::AllPairsCollapsed)) {
     std::cerr << "--softening is supported by --algorithm all-pairs and octree only, not by "
