@@ -84,7 +84,9 @@ typedef struct nbody_state {
  *      Additive, same version: the fourth-order Hermite integrator for all-pairs, nbody_hermite_create, nbody_hermite_create_on,
  *      nbody_hermite_destroy, nbody_hermite_force_jerk, nbody_hermite_step, nbody_hermite_read.  Additive, same version: block
  *      (individual) time steps for it, nbody_hermite_block_start, nbody_hermite_block_step, nbody_hermite_block_advance,
- *      nbody_hermite_block_read. */
+ *      nbody_hermite_block_read.  Additive, same version: block (individual) time steps for the octree leapfrog,
+ *      nbody_octree_block_create, nbody_octree_block_create_on, nbody_octree_block_destroy, nbody_octree_block_start,
+ *      nbody_octree_block_step, nbody_octree_block_advance, nbody_octree_block_read. */
 #define NBODY_HIP_ABI_VERSION 2004
 int nbody_abi_version(void);
 
@@ -393,6 +395,65 @@ int  nbody_hermite_block_advance(nbody_hermite* h, const nbody_state* s, double 
 /* Blocking.  what: 0 levels int32[n] | 1 tau_i uint32[n] | 2 the active list of the last block step, uint32[n_active] ascending.
  * bytes must match (NBODY_ERR_ARG). */
 int  nbody_hermite_block_read(nbody_hermite* h, int what, void* host_out, size_t bytes, void* stream);
+
+/* ---- block (individual) time steps for the octree leapfrog (no reference counterpart) ----------------------------------------
+ * A per-body velocity-Verlet (kick-drift-kick) step on the level grid of the Hermite block steps above, with the force from the
+ * softened monopole walk (nbody_octree_compute_softened_force).  dt_max = s->dt is the largest step and the synchronisation
+ * interval, L = max_level (0 .. 20), tick = dt_max / 2^L.  Body i has a level l_i in [0, L], a step of 2^(L - l_i) ticks, a
+ * last-update time tau_i in integer ticks since the start of the current interval (always a multiple of the body's step), and its
+ * acceleration a_i = s->a[i] at (x_i, tau_i).  eps > 0 is required, as for the Hermite integrator.
+ *   criterion   want_i = sqrt(2 eta eps / |a_i|), evaluated in T as sqrt(k / sqrt(|a_i|^2)) with k = T(2) * T(eta) * T(eps) and
+ *               |a_i|^2 an FMA chain over the components; |a_i| = 0 means no limit.
+ *   start       the tree on x (bounds, insert, multipoles), the softened monopole force of ALL bodies into s->a, then
+ *               l_i = the smallest level with dt_max 2^-l <= want_i, clamped to [0, L] (no limit: level 0); tau_i = 0.
+ *   block step  1. tau_next = min_i(tau_i + step_i);
+ *               2. the active set is every i with tau_i + step_i == tau_next;
+ *               3. ALL bodies are predicted: xp_i = x_i + h_i v_i + h_i^2/2 a_i, h_i = T(tau_next - tau_i) * T(tick), evaluated as
+ *                  fma(h, fma(h/2, a, v), x);
+ *               4. the tree is built on xp: clear, bounds, insert, multipoles, as a fixed step builds it on x;
+ *               5. a1 = the softened monopole force of the ACTIVE bodies only, walked from that tree in key order by the kernel of
+ *                  nbody_octree_compute_softened_force (so a1_i is bit for bit what that call gives body i on the positions xp);
+ *               6. for each active body v_i += h_i/2 (a_i + a1_i) (as fma(h/2, a + a1, v)), x_i = xp_i, a_i = a1_i, the new level,
+ *                  tau_i = tau_next.  New level, the Hermite block steps' rule with h = the body's step and want from a1: if
+ *                  want < h, the smallest level deeper than l_i whose step is <= want, at most L; else if want >= 2 h (or no
+ *                  limit), l_i > 0 and tau_next is a multiple of twice the body's step, l_i - 1 (one doubling at most); else l_i;
+ *               7. inactive bodies are not written (x, v, a, level, tau);
+ *               8. at tau_next = 2^L every body is active, the system is synchronous at t + dt_max, and tau starts again from 0.
+ * s->ao is neither read nor written.  Both active lists (ascending body order for the kick and for block_read, key order for the
+ * walk) are stable compactions — no atomic decides a slot — and a body's force is the walk's, which has no cross-body reduction: two
+ * runs from the same state give the same bits.
+ *  - Scope: monopole and softened only; the whole system only (first = 0, count = sz).  Not recordable into a step graph: a block
+ *    step reads (n_active, tau_next) back (8 bytes, blocking).
+ *  - The handle owns the levels, tau, the schedule words, both active lists, xp and the scratch for a1; all allocated by create.
+ *    The tree is the caller's: any nbody_octree made for the same (dtype, dim, n).  A block step leaves it built on xp, with its phase
+ *    flags as after nbody_octree_compute_tree; nbody_octree_info after a step or an advance reports a build that hit the depth limit
+ *    or the node pool on ANY block step since the last call (the device-side flag is sticky).
+ *  - Argument errors before the device is touched, in this order (all NBODY_ERR_ARG): s NULL; the state's dtype, dim, window, tuning;
+ *    the whole-system rule; eps (the message names the softening); eta (finite, > 0, also as T, and 2 eta eps a positive finite T);
+ *    max_level (0 .. 20; start only); h NULL; t NULL; h, then t, made for another dtype, dim or n; s->dt (finite, > 0, tick a normal
+ *    number of T).  Then: a handle or tree used with a stream of another device (NBODY_ERR_ARG); any of start / step / advance / read
+ *    between nbody_graph_begin and nbody_graph_end (NBODY_ERR_STATE; the capture stays usable); a tree after
+ *    nbody_octree_set_walk(t, 2) (NBODY_ERR_ARG with the softened walk's message, as nbody_octree_compute_softened_force returns it);
+ *    step / advance / read before start on that handle (NBODY_ERR_STATE); for a step, s->dt other than start's (NBODY_ERR_ARG). */
+typedef struct nbody_octree_block nbody_octree_block;
+int  nbody_octree_block_create(nbody_octree_block** out, int dtype, int dim, uint32_t n);                /* on the current device */
+int  nbody_octree_block_create_on(nbody_octree_block** out, int dtype, int dim, uint32_t n, int device); /* device < 0: the current one */
+void nbody_octree_block_destroy(nbody_octree_block* h);
+/* Starts a run (or restarts it after an upload): the force of all bodies into s->a, the first levels, tau = 0. */
+int  nbody_octree_block_start(nbody_octree_block* h, nbody_octree* t, const nbody_state* s, double theta, double eps, double eta,
+                              int max_level, void* stream);
+/* One block step.  *n_active: the size of its active set, *tau: its tau_next in ticks (2^max_level: the interval is complete);
+ * either may be NULL.  Blocking for the schedule, asynchronous for the walk and the kick. */
+int  nbody_octree_block_step(nbody_octree_block* h, nbody_octree* t, const nbody_state* s, double theta, double eps, double eta,
+                             void* stream, uint32_t* n_active, uint32_t* tau);
+/* Block steps until the system is synchronous at t + s->dt.  *block_steps: how many, *body_steps: the sum of their active sets (the
+ * force evaluations made); either may be NULL. */
+int  nbody_octree_block_advance(nbody_octree_block* h, nbody_octree* t, const nbody_state* s, double theta, double eps, double eta,
+                                void* stream, uint64_t* block_steps, uint64_t* body_steps);
+/* Blocking.  what: 0 levels int32[n] | 1 tau_i uint32[n] | 2 the active list of the last block step, uint32[n_active] in ascending
+ * body order | 3 the predicted positions xp of the last block step, T[n][D].  bytes must match (NBODY_ERR_ARG); 2 and 3 before the
+ * first block step: NBODY_ERR_STATE. */
+int  nbody_octree_block_read(nbody_octree_block* h, int what, void* host_out, size_t bytes, void* stream);
 
 /* ---- owning context (device mirrors of a host System), used by the C++ CLI host ------------------ */
 

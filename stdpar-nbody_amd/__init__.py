@@ -63,6 +63,8 @@ ABI_SYMBOLS = [
     "nbody_hermite_create", "nbody_hermite_create_on", "nbody_hermite_destroy", "nbody_hermite_force_jerk", "nbody_hermite_step",
     "nbody_hermite_read",
     "nbody_hermite_block_start", "nbody_hermite_block_step", "nbody_hermite_block_advance", "nbody_hermite_block_read",
+    "nbody_octree_block_create", "nbody_octree_block_create_on", "nbody_octree_block_destroy", "nbody_octree_block_start",
+    "nbody_octree_block_step", "nbody_octree_block_advance", "nbody_octree_block_read",
 ]
 ABI_MAJOR = 2
 COMM_ID_BYTES = 128
@@ -104,6 +106,12 @@ def lib():
         L.nbody_hermite_block_step.argtypes = [vp, vp, d, d, vp, vp, vp]
         L.nbody_hermite_block_advance.argtypes = [vp, vp, d, d, vp, vp, vp]
         L.nbody_hermite_block_read.argtypes = [vp, C.c_int, vp, C.c_size_t, vp]
+        L.nbody_octree_block_destroy.restype = None
+        L.nbody_octree_block_destroy.argtypes = [vp]
+        L.nbody_octree_block_start.argtypes = [vp, vp, vp, d, d, d, C.c_int, vp]
+        L.nbody_octree_block_step.argtypes = [vp, vp, vp, d, d, d, vp, vp, vp]
+        L.nbody_octree_block_advance.argtypes = [vp, vp, vp, d, d, d, vp, vp, vp]
+        L.nbody_octree_block_read.argtypes = [vp, C.c_int, vp, C.c_size_t, vp]
         _lib = L
     return _lib
 
@@ -486,6 +494,54 @@ class Hermite:
         return out
 
 
+class OctreeBlock:
+    """Block (individual) time steps for the octree leapfrog (nbody_octree_block_*): owns the levels, tau, the active lists, the
+    predicted positions and the scratch of the active set's forces; the tree is the caller's Octree."""
+
+    def __init__(self, dtype, dim, n, device=-1):
+        """device: where the handle's buffers live (-1: the calling thread's current device)."""
+        self.h = C.c_void_p()
+        self.dtype, self.dim, self.n = dtype, dim, n
+        _check(lib().nbody_octree_block_create_on(C.byref(self.h), dtype, dim, C.c_uint32(n), device))
+
+    def close(self):
+        if self.h:
+            lib().nbody_octree_block_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def start(self, tree, st, theta, eps, eta, max_level, stream=None):
+        """The softened force of all bodies into st.a and the first levels: st.dt is the largest step, st.dt / 2^max_level the smallest."""
+        _check(lib().nbody_octree_block_start(self.h, tree.h, C.byref(st), theta, eps, eta, max_level, stream))
+
+    def step(self, tree, st, theta, eps, eta, stream=None):
+        """One block step: (n_active, tau_next in ticks).  Blocking for the schedule."""
+        na, tau = C.c_uint32(), C.c_uint32()
+        _check(lib().nbody_octree_block_step(self.h, tree.h, C.byref(st), theta, eps, eta, stream, C.byref(na), C.byref(tau)))
+        return na.value, tau.value
+
+    def advance(self, tree, st, theta, eps, eta, stream=None):
+        """Block steps until the system is synchronous at t + st.dt: (block steps, body steps)."""
+        bs, bod = C.c_uint64(), C.c_uint64()
+        _check(lib().nbody_octree_block_advance(self.h, tree.h, C.byref(st), theta, eps, eta, stream, C.byref(bs), C.byref(bod)))
+        return bs.value, bod.value
+
+    def read(self, what, stream=None, count=None):
+        """0 the levels (int32), 1 tau_i in ticks (uint32), 2 the active list of the last block step (uint32, `count` of them,
+        ascending), 3 its predicted positions, (n, dim) of T."""
+        if what == 3:
+            out = np.zeros((self.n, self.dim), np_dtype(self.dtype))
+        else:
+            out = np.zeros(self.n if what != 2 else count, np.int32 if what == 0 else np.uint32)
+        _check(lib().nbody_octree_block_read(self.h, what, _p(out), out.nbytes, stream))
+        return out
+
+
 class DeviceSystem:
     """Owning device mirror of a System<T,N>; phase methods mirror the calls of the reference drivers."""
 
@@ -497,6 +553,7 @@ class DeviceSystem:
         self._bvh = None
         self._octree = None
         self._hermite = None
+        self._octree_block = None
 
     @classmethod
     def from_host(cls, hs, device=0):
@@ -514,6 +571,9 @@ class DeviceSystem:
         if self._hermite is not None:
             self._hermite.close()
             self._hermite = None
+        if self._octree_block is not None:
+            self._octree_block.close()
+            self._octree_block = None
         if self.h:
             lib().nbody_destroy(self.h)
             self.h = C.c_void_p()
@@ -615,6 +675,38 @@ class DeviceSystem:
     def hermite_block_active(self, n_active):
         """The active list of the last block step (ascending body indices); n_active as hermite_block_step returned it."""
         return self.hermite.block_read(2, self.stream, n_active)
+
+    # block time steps for the octree leapfrog (no reference counterpart)
+    @property
+    def octree_block(self):
+        if self._octree_block is None:
+            self._octree_block = OctreeBlock(self.dtype, self.dim, self.n, self.device)
+        return self._octree_block
+
+    def octree_block_start(self, theta, eps, eta, max_level=12):
+        """Starts a run of the octree leapfrog with block time steps (nbody_octree_block_start): the softened force of all bodies and
+        the first levels; dt is the largest step, dt / 2^max_level the smallest."""
+        self.octree_block.start(self.octree, self.state(), theta, eps, eta, max_level, self.stream)
+
+    def octree_block_step(self, theta, eps, eta):
+        """One block step: (n_active, tau_next in ticks); tau_next == 2^max_level completes the interval of dt."""
+        return self.octree_block.step(self.octree, self.state(), theta, eps, eta, self.stream)
+
+    def octree_block_advance(self, theta, eps, eta):
+        """Block steps until the system is synchronous at t + dt: (block steps, body steps)."""
+        return self.octree_block.advance(self.octree, self.state(), theta, eps, eta, self.stream)
+
+    def octree_block_levels(self):
+        """(levels, tau) of the bodies, int32 and uint32 (blocking)."""
+        return self.octree_block.read(0, self.stream), self.octree_block.read(1, self.stream)
+
+    def octree_block_active(self, n_active):
+        """The active list of the last block step (ascending body indices); n_active as octree_block_step returned it."""
+        return self.octree_block.read(2, self.stream, n_active)
+
+    def octree_block_predicted(self):
+        """The predicted positions of the last block step, (n, dim) of T (blocking)."""
+        return self.octree_block.read(3, self.stream)
 
     def calc_energies(self, softening=0.0):
         """(kinetic, potential) as in System::calc_energies (src/system.h:62-79); blocking.  softening > 0: the potential of the

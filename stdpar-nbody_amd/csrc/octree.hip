@@ -2937,6 +2937,16 @@ static int ot_walk_list(nbody_octree* t, const nbody_state* s, hipStream_t st, c
   return NBODY_OK;
 }
 
+// the softened walk's refusal after nbody_octree_set_walk(t, 2) (also the block steps', which take that walk: octree_block.inc)
+static int ot_soft_walk_form(const nbody_octree* t) {
+  if (t->walk == 2) {
+    set_error("octree walk: the softened walk exists in the compiler-scheduled form only (walk form 1 or 0 = auto), not as the ISA "
+              "visit round set by nbody_octree_set_walk(t, 2)");
+    return NBODY_ERR_ARG;
+  }
+  return NBODY_OK;
+}
+
 // soft: the softened walk (e2 > 0), which exists in the compiler-scheduled form only
 template <typename T, int D>
 static int ot_force_run(nbody_octree* t, const nbody_state* s, double theta, hipStream_t st, bool soft = false, T e2 = T(0),
@@ -2946,11 +2956,8 @@ static int ot_force_run(nbody_octree* t, const nbody_state* s, double theta, hip
               "ISA visit round set by nbody_octree_set_walk(t, 2)");
     return NBODY_ERR_ARG;
   }
-  if (soft && t->walk == 2) {
-    set_error("octree walk: the softened walk exists in the compiler-scheduled form only (walk form 1 or 0 = auto), not as the ISA "
-              "visit round set by nbody_octree_set_walk(t, 2)");
-    return NBODY_ERR_ARG;
-  }
+  if (soft)
+    if (int r = ot_soft_walk_form(t)) return r;
   if (s->count == 0) return NBODY_OK;
   const uint32_t* list = nullptr;
   if (int r = ot_walk_list(t, s, st, &list)) return r;
@@ -3558,3 +3565,5 @@ extern "C" int nbody_octree_calc_energies(nbody_octree* t, const nbody_state* s,
   };
   return energies_from_sums(s, st, fill, &ctx, kinetic_out, potential_out);
 }
+
+#include "octree_block.inc"

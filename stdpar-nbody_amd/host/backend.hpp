@@ -46,6 +46,7 @@ class Device {
   }
   ~Device() {
     if (hermite_) nbody_hermite_destroy(hermite_);
+    if (octree_block_) nbody_octree_block_destroy(octree_block_);
     if (octree_) nbody_octree_destroy(octree_);
     if (tree_) nbody_bvh_destroy(tree_);
     for (auto* c : comm_) nbody_comm_destroy(c);
@@ -187,6 +188,16 @@ class Device {
                   "nbody_octree_calc_energies");
     return {ke, pe};
   }
+  // --block-eta ETA: block time steps of the octree leapfrog; one advance moves the system by dt (as many block steps as its levels ask for)
+  void octree_block_start(double theta, double eps, double eta, int max_level) {
+    octree_alloc();
+    if (!octree_block_) backend_check(nbody_octree_block_create_on(&octree_block_, dtype, D, host_.n, 0), "nbody_octree_block_create_on");
+    backend_check(nbody_octree_block_start(octree_block_, octree_, &view_[0], theta, eps, eta, max_level, stream()), "nbody_octree_block_start");
+  }
+  void octree_block_advance(double theta, double eps, double eta) {
+    backend_check(nbody_octree_block_advance(octree_block_, octree_, &view_[0], theta, eps, eta, stream(), nullptr, nullptr),
+                  "nbody_octree_block_advance");
+  }
   // {tree size, total mass}; also where device-side build errors (depth limit, node pool) surface
   std::pair<std::uint32_t, T> octree_info() {
     std::uint32_t size = 0;
@@ -218,6 +229,7 @@ class Device {
   nbody_bvh* tree_ = nullptr;
   nbody_octree* octree_ = nullptr;
   nbody_hermite* hermite_ = nullptr;
+  nbody_octree_block* octree_block_ = nullptr;
 };
 
 }  // namespace nb

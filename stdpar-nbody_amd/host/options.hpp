@@ -50,6 +50,13 @@ struct Options {
   double hermite_eta = 0.0;  // 0: fixed step
   int hermite_levels = 12;
   bool hermite_levels_given = false;
+  // not in the reference either (nor in --help): --block-eta ETA (octree with --softening EPS > 0 only, ETA > 0) runs the octree
+  // leapfrog with block time steps (nbody_octree_block_*): every step of the run advances the system by dt in as many block steps as
+  // the bodies' levels ask for, each body on the power-of-two step its acceleration allows; --block-levels L (0 .. 20, default 12):
+  // the smallest step is dt / 2^L
+  double block_eta = 0.0;  // 0: one shared step
+  int block_levels = 12;
+  bool block_levels_given = false;
 };
 
 namespace detail {
@@ -149,6 +156,25 @@ inline Options parse_options(std::vector<std::string> const& argv) {
       }
       o.hermite_levels       = int(v);
       o.hermite_levels_given = true;
+    } else if (f == "--block-eta") {
+      auto const& e = value();
+      char* end     = nullptr;
+      double const v = std::strtod(e.c_str(), &end);
+      if (e.empty() || end != e.c_str() + e.size() || !std::isfinite(v) || !(v > 0.0)) {
+        std::cerr << "--block-eta needs a finite accuracy parameter > 0, got \"" << e << "\"." << std::endl;
+        std::exit(EXIT_FAILURE);
+      }
+      o.block_eta = v;
+    } else if (f == "--block-levels") {
+      auto const& l = value();
+      char* end     = nullptr;
+      long const v  = std::strtol(l.c_str(), &end, 10);
+      if (l.empty() || end != l.c_str() + l.size() || v < 0 || v > 20) {
+        std::cerr << "--block-levels needs a level count in 0 .. 20, got \"" << l << "\"." << std::endl;
+        std::exit(EXIT_FAILURE);
+      }
+      o.block_levels       = int(v);
+      o.block_levels_given = true;
     } else if (f == "--quadrupole") {
       o.quadrupole = true;
     } else if (f == "--tree-energy") {
@@ -175,6 +201,32 @@ inline Options parse_options(std::vector<std::string> const& argv) {
   if (o.csv_detailed && o.csv_total) {
     std::cerr << "Cannot capture a CSV detailed and coarse trace in the same run. Specify one or the other." << std::endl;
     std::exit(EXIT_FAILURE);
+  }
+  if (o.block_levels_given && !(o.block_eta > 0.0)) {
+    std::cerr << "--block-levels needs --block-eta ETA." << std::endl;
+    std::exit(EXIT_FAILURE);
+  }
+  if (o.block_eta > 0.0) {  // block time steps of the octree leapfrog: softened monopole walk, one GPU
+    if (o.algorithm != Algorithm::Octree) {
+      std::cerr << "--block-eta is supported by --algorithm octree only." << std::endl;
+      std::exit(EXIT_FAILURE);
+    }
+    if (o.integrator == Integrator::Hermite) {
+      std::cerr << "--block-eta steps the octree leapfrog: it cannot be combined with --integrator hermite." << std::endl;
+      std::exit(EXIT_FAILURE);
+    }
+    if (o.quadrupole) {
+      std::cerr << "--block-eta takes the softened monopole walk: it cannot be combined with --quadrupole." << std::endl;
+      std::exit(EXIT_FAILURE);
+    }
+    if (!(o.softening > 0.0)) {
+      std::cerr << "--block-eta needs --softening EPS with EPS > 0." << std::endl;
+      std::exit(EXIT_FAILURE);
+    }
+    if (o.gpus_given) {
+      std::cerr << "--block-eta runs on one GPU: it cannot be combined with --gpus." << std::endl;
+      std::exit(EXIT_FAILURE);
+    }
   }
   if (o.integrator == Integrator::Hermite) {
     if (o.algorithm != Algorithm::AllPairs) {

@@ -2,7 +2,8 @@
 """Compare the gfx950 instruction text of two builds of libnbody_hip.so, kernel by kernel (no GPU needed).
 
 Disassembles every code object embedded in each library (llvm-objdump -d --no-show-raw-insn), strips addresses, branch-target
-offsets and symbol comments, and for every kernel symbol present in both reports whether its instruction text is identical.  Used to
+offsets, symbol comments and the s_nop padding behind a function's last instruction (it belongs to whatever the linker placed
+next, not to the function), and for every kernel symbol present in both reports whether its instruction text is identical.  Used to
 show that a change which adds kernels left the existing ones as they were.
 
     python tools/compare_kernel_isa.py OLD.so NEW.so [-v]
@@ -46,6 +47,9 @@ def kernels(lib_path):
                     out[cur].append(ins)
             pos += len(ELF_AMDGPU)
             k += 1
+    for v in out.values():  # alignment padding up to the next function or the end of the section
+        while v and v[-1] == "s_nop 0":
+            v.pop()
     return {n: tuple(v) for n, v in out.items() if v}
 
 
