@@ -14,15 +14,18 @@
 //   - LDS tiles (all_pairs_force_kernel): tiles staged in LDS by all 256 lanes with a register prefetch of the
 //     next tile; the inner loop reads each record as an LDS broadcast (ds_read_b128) into VGPRs;
 //   - scalar stream (all_pairs_force_sgpr_kernel, default from 2048 bodies): the record is wave-uniform, so it belongs in
-//     SGPRs: ONE pre-pass launch per call (k1_prepare_kernel) packs the records (32 B x N), sums the positions' moments for the
-//     pair rule and resets the turn words; every wave streams its slice with s_load_dwordx16 two batches deep (inline asm) and the
-//     VALU instructions take their source operands from SGPRs.  No staging loads, no LDS traffic, no barriers in the loop, half
-//     the VGPRs.
-//   Pair rule (common.hpp, pair_batch): f64 is reciprocal-free — 16 full-rate ops + v_rsq_f64 per pair on sparse systems
-//   (the launch-level far mode: the positions' variances, common.hpp k1_rule, say that few batches can hold a pair closer than 2),
-//   17 + 1 on dense ones; pairs below 2^-16 take the guarded reciprocal form.
-//   Measured: N = 2^20 galaxy 602-633 ms per pass by the clock the box sustains = 44-46.5 % of the 78.6 TF FP64 vector peak
-//   (profiles/r05/bench_n1.json; VALU 98 % busy: 97 % of what 16 + rsq allow).
+//     SGPRs: ONE pre-pass launch per call (k1_prepare_kernel) packs the records (32 B x N; in f64 also the sources' pair constants
+//     M15 = 1.5 m, M1875 = 1.875 m, 16 B x N), sums the positions' moments for the pair rule and resets the turn words; every wave
+//     streams its slice with s_load_dwordx16 two batches deep (inline asm) and the VALU instructions take their source operands
+//     from SGPRs — in f64 all but M15, which a wave-uniform global_load_dwordx4 per batch puts into VGPRs without a VALU
+//     instruction (a VOP3 instruction reads one scalar value; common.hpp: weight_far_folded, cload).  No staging loads, no LDS
+//     traffic, no barriers in the loop, half the VGPRs.
+//   Pair rule (common.hpp, pair_batch): f64 is reciprocal-free with the source's mass folded into the polynomial — 15 full-rate
+//   ops + v_rsq_f64 per pair on sparse systems (the launch-level far mode: the positions' variances, common.hpp k1_rule, say that
+//   few batches can hold a pair closer than 2), 16 + 1 on dense ones; pairs below 2^-16 take the guarded reciprocal form.
+//   Measured: N = 2^20 galaxy 602-633 ms per pass by the clock the box sustains = 44-46.5 % of the 78.6 TF FP64 vector peak with
+//   the 16 + rsq form (profiles/r05/bench_n1.json; VALU 98 % busy: 97 % of what 16 + rsq allow); the folded form against it,
+//   alternating on one box: profiles/r07/time_folded_weight.txt.
 //
 // K2 (replaces src/all_pairs.h:29-50, intended semantics).  Lanes run along the SOURCE axis (one
 // ordered pair per lane and step), each wave owns 64 targets whose positions it broadcasts with
@@ -104,7 +107,8 @@ __global__ __launch_bounds__(kBlock) void pack_sources_kernel(const T* __restric
 
 // What a K1 launch needs done first, in ONE launch (rounds 2-4: a memset, the extent kernel, the pack kernel and another memset —
 // four dependent launches, 20 us of a 73 us call at n = 8192):
-//   PACK     the (x, m) records of the scalar-stream form, as pack_sources_kernel above;
+//   PACK     the (x, m) records of the scalar-stream form, as pack_sources_kernel above, and in f64 the sources' constants
+//            M15 = 1.5 m and M1875 = 1.875 m of K1's pair form beside them (common.hpp: src_cst, cst_batch; 16 bytes per source);
 //   MOMENTS  the first and second moments of all sz positions, relative to body 0 (so that a system far from the origin does not
 //            cancel), summed per block in a fixed order; the LAST block to deliver (a ticket) adds the blocks' sums in index order
 //            and writes the rule (common.hpp: k1_rule) — the same bits whichever block comes last;
@@ -112,7 +116,7 @@ __global__ __launch_bounds__(kBlock) void pack_sources_kernel(const T* __restric
 // One block per 256 bodies of the padded set; the ticket returns to 0, so a recorded launch can be replayed.
 template <typename T, int D, bool PACK, bool MOMENTS>
 __global__ __launch_bounds__(kBlock) void k1_prepare_kernel(const T* __restrict__ m, const T* __restrict__ x, src_rec<T, D>* __restrict__ out,
-                                                            uint32_t sz, uint32_t padded, k1_rule* rule, double* partial,
+                                                            cst_batch* __restrict__ cst, uint32_t sz, uint32_t padded, k1_rule* rule, double* partial,
                                                             uint32_t* turn, uint32_t turn_words) {
   const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
   T p[D];
@@ -125,6 +129,11 @@ __global__ __launch_bounds__(kBlock) void k1_prepare_kernel(const T* __restrict_
       for (int k = 0; k < 3; ++k) r.p[k] = k < D ? p[k < D ? k : 0] : T(0);
       r.m    = j < sz ? m[j] : T(0);
       out[j] = r;
+      if constexpr (sizeof(T) == 8) {  // (a zero-mass padding record: constants 0)
+        const src_cst<T> k  = src_cst<T>::of(r.m);
+        cst[j / 2].m15[j % 2]   = k.m15;
+        cst[j / 2].m1875[j % 2] = k.m1875;
+      }
     }
   }
   __shared__ double red[2 * D][kWaves];
@@ -259,6 +268,7 @@ struct k1_handoff {
 };
 template <typename T, int D, int R, int JS, int RULE = 0>
 __global__ __launch_bounds__(64 * kSgprWaves<JS>) void all_pairs_force_sgpr_kernel(const src_rec<T, D>* __restrict__ packed,
+                                                                                   const cst_batch* __restrict__ cst,
                                                                                    const T* __restrict__ x, T* a, T c, uint32_t sz,
                                                                                    uint32_t first, uint32_t count,
                                                                                    uint32_t tiles_per_chunk, k1_handoff h,
@@ -272,6 +282,7 @@ __global__ __launch_bounds__(64 * kSgprWaves<JS>) void all_pairs_force_sgpr_kern
 // they were (tools/check_k1_handoff.py holds this one to the same hand-off rules with KERNEL set to its name).
 template <typename T, int D, int R, int JS>
 __global__ __launch_bounds__(64 * kSgprWaves<JS>) void all_pairs_softened_sgpr_kernel(const src_rec<T, D>* __restrict__ packed,
+                                                                                      const cst_batch* __restrict__ cst,
                                                                                       const T* __restrict__ x, T* a, T c, uint32_t sz,
                                                                                       uint32_t first, uint32_t count,
                                                                                       uint32_t tiles_per_chunk, k1_handoff h, T e2) {
@@ -295,7 +306,7 @@ struct scratch_buf {
 struct packed_slot {
   int device;
   hipStream_t stream;
-  scratch_buf buf[6];  // 0: packed sources, 1: K1 turn words, 2: energies work area, 3: the pair rule + partial moments, 4: K1 hand-off status (k1_status), 5: K1 chunk sums of small launches
+  scratch_buf buf[7];  // 0: packed sources, 1: K1 turn words, 2: energies work area, 3: the pair rule + partial moments, 4: K1 hand-off status (k1_status), 5: K1 chunk sums of small launches, 6: the packed sources' f64 pair constants (cst_batch)
   std::vector<void*> retired;
   bool k1_dirty  = false;  // a K1 that passes turns (or a recorded step, which may hold one) has been queued since the status was last read
   bool k1_failed = false;  // the last read found the sticky error set
@@ -449,6 +460,9 @@ int ap_pack_sources(const nbody_state* s, hipStream_t st, void** packed_out) {
   return rc;
 }
 
+// Bytes of scratch buffer 6 for `padded` packed records (f64 only): one cst_batch per two of them.
+static size_t ap_cst_bytes(size_t padded) { return sizeof(cst_batch) * (padded / 2); }
+
 // Bytes of scratch buffer 3 for a system of sz bodies: the rule, then one row of 2 D partial sums per prepare block.
 static size_t ap_rule_bytes(uint32_t sz, int dim) {
   const size_t padded = (size_t(sz) + kTileJ - 1) / kTileJ * kTileJ;
@@ -459,26 +473,32 @@ static size_t ap_rule_bytes(uint32_t sz, int dim) {
 // form), the pair rule of the whole system (sz >= kFarMinBodies; nullptr = "dense" below) and the turn words handed back to chunk 0.
 // The softened K1 has no pair rule (with_rule false): no moments are summed.
 template <typename T, int D>
-static int ap_prepare(const nbody_state* s, hipStream_t st, bool pack, src_rec<T, D>** packed_out, const k1_rule** rule_out,
-                      uint32_t* turn, size_t turn_words, bool with_rule = true) {
+static int ap_prepare(const nbody_state* s, hipStream_t st, bool pack, src_rec<T, D>** packed_out, const cst_batch** cst_out,
+                      const k1_rule** rule_out, uint32_t* turn, size_t turn_words, bool with_rule = true) {
   const uint32_t padded = (s->sz + kTileJ - 1) / kTileJ * kTileJ;
   const bool moments    = with_rule && s->sz >= kFarMinBodies;
   void* scratch         = nullptr;
-  if (pack)
+  void* consts          = nullptr;
+  if (pack) {
     if (int r = ap_scratch_get(st, 0, 4 * sizeof(T) * size_t(padded), &scratch)) return r;
+    if (sizeof(T) == 8)
+      if (int r = ap_scratch_get(st, 6, ap_cst_bytes(padded), &consts)) return r;
+  }
   void* q = nullptr;
   if (int r = ap_scratch_get(st, 3, ap_rule_bytes(s->sz, D), &q)) return r;  // (the ticket lives there even without moments)
   auto* rule    = static_cast<k1_rule*>(q);
   auto* partial = reinterpret_cast<double*>(static_cast<char*>(q) + 32);
   auto* out     = static_cast<src_rec<T, D>*>(scratch);
+  auto* cst     = static_cast<cst_batch*>(consts);
   const dim3 grid(padded / kBlock), block(kBlock);
   const T *m = static_cast<const T*>(s->m), *x = static_cast<const T*>(s->x);
   const uint32_t words = uint32_t(turn_words);
-  if (pack && moments) hipLaunchKernelGGL((k1_prepare_kernel<T, D, true, true>), grid, block, 0, st, m, x, out, s->sz, padded, rule, partial, turn, words);
-  else if (pack) hipLaunchKernelGGL((k1_prepare_kernel<T, D, true, false>), grid, block, 0, st, m, x, out, s->sz, padded, rule, partial, turn, words);
-  else if (moments) hipLaunchKernelGGL((k1_prepare_kernel<T, D, false, true>), grid, block, 0, st, m, x, out, s->sz, padded, rule, partial, turn, words);
+  if (pack && moments) hipLaunchKernelGGL((k1_prepare_kernel<T, D, true, true>), grid, block, 0, st, m, x, out, cst, s->sz, padded, rule, partial, turn, words);
+  else if (pack) hipLaunchKernelGGL((k1_prepare_kernel<T, D, true, false>), grid, block, 0, st, m, x, out, cst, s->sz, padded, rule, partial, turn, words);
+  else if (moments) hipLaunchKernelGGL((k1_prepare_kernel<T, D, false, true>), grid, block, 0, st, m, x, out, cst, s->sz, padded, rule, partial, turn, words);
   NB_HIP(hipGetLastError());
   if (packed_out) *packed_out = out;
+  if (cst_out) *cst_out = cst;
   *rule_out = moments ? rule : nullptr;
   return NBODY_OK;
 }
@@ -531,11 +551,12 @@ static int launch_all_pairs_sgpr(const nbody_state* s, const k1_plan& plan, hipS
     if (const char* e = experiment_env("NBODY_K1_COLLECT"); e && e[0] == '0') h.sums = nullptr;  // experiments: turns at every size
   }
   src_rec<T, D>* packed = nullptr;
+  const cst_batch* cst  = nullptr;  // f64 only
   const k1_rule* rule   = nullptr;
-  if (int r = ap_prepare<T, D>(s, st, true, &packed, &rule, h.turn, h.turn ? sgpr_turn_words<R, JS>(s->count) : 0, !SOFT)) return r;
+  if (int r = ap_prepare<T, D>(s, st, true, &packed, &cst, &rule, h.turn, h.turn ? sgpr_turn_words<R, JS>(s->count) : 0, !SOFT)) return r;
   if constexpr (SOFT) {
     hipLaunchKernelGGL((all_pairs_softened_sgpr_kernel<T, D, R, JS>), dim3(blocks, plan.chunks), dim3(64 * kSgprWaves<JS>), 0, st,
-                       packed, static_cast<const T*>(s->x), static_cast<T*>(s->a), static_cast<T>(s->c), s->sz, s->first, s->count,
+                       packed, cst, static_cast<const T*>(s->x), static_cast<T*>(s->a), static_cast<T>(s->c), s->sz, s->first, s->count,
                        plan.tiles_per_chunk, h, e2);
     NB_HIP(hipGetLastError());
     if (h.turn != nullptr && h.sums == nullptr) ap_status_mark(st);
@@ -545,18 +566,18 @@ static int launch_all_pairs_sgpr(const nbody_state* s, const k1_plan& plan, hipS
   if (const char* e = getenv("NBODY_K1_RULE_FORCE"); e && JS == 8 && D == 3) {  // timing experiment: one rule per instantiation
     if (e[0] == '1')
       hipLaunchKernelGGL((all_pairs_force_sgpr_kernel<T, D, R, JS, 1>), dim3(blocks, plan.chunks), dim3(64 * kSgprWaves<JS>), 0, st,
-                         packed, static_cast<const T*>(s->x), static_cast<T*>(s->a), static_cast<T>(s->c), s->sz, s->first, s->count,
+                         packed, cst, static_cast<const T*>(s->x), static_cast<T*>(s->a), static_cast<T>(s->c), s->sz, s->first, s->count,
                          plan.tiles_per_chunk, h, rule);
     else
       hipLaunchKernelGGL((all_pairs_force_sgpr_kernel<T, D, R, JS, 2>), dim3(blocks, plan.chunks), dim3(64 * kSgprWaves<JS>), 0, st,
-                         packed, static_cast<const T*>(s->x), static_cast<T*>(s->a), static_cast<T>(s->c), s->sz, s->first, s->count,
+                         packed, cst, static_cast<const T*>(s->x), static_cast<T*>(s->a), static_cast<T>(s->c), s->sz, s->first, s->count,
                          plan.tiles_per_chunk, h, rule);
     NB_HIP(hipGetLastError());
     return NBODY_OK;
   }
 #endif
   hipLaunchKernelGGL((all_pairs_force_sgpr_kernel<T, D, R, JS>), dim3(blocks, plan.chunks), dim3(64 * kSgprWaves<JS>), 0, st,
-                     packed, static_cast<const T*>(s->x), static_cast<T*>(s->a), static_cast<T>(s->c), s->sz, s->first, s->count,
+                     packed, cst, static_cast<const T*>(s->x), static_cast<T*>(s->a), static_cast<T>(s->c), s->sz, s->first, s->count,
                      plan.tiles_per_chunk, h, rule);
   NB_HIP(hipGetLastError());
   if (h.turn != nullptr && h.sums == nullptr) ap_status_mark(st);  // turns were passed: the next wait for this stream reads the status
@@ -575,7 +596,7 @@ static int launch_all_pairs(const nbody_state* s, hipStream_t st, T e2) {
     return NBODY_OK;
   }
   const k1_rule* rule = nullptr;  // the same per-pair rule as the scalar-stream form (bitwise the same result)
-  if (int r = ap_prepare<T, D>(s, st, false, nullptr, &rule, nullptr, 0)) return r;
+  if (int r = ap_prepare<T, D>(s, st, false, nullptr, nullptr, &rule, nullptr, 0)) return r;
   hipLaunchKernelGGL((all_pairs_force_kernel<T, D, R, JS>), dim3(blocks), dim3(kBlock), 0, st, static_cast<const T*>(s->m),
                      static_cast<const T*>(s->x), static_cast<T*>(s->a), static_cast<T>(s->c), s->sz, s->first, s->count, rule);
   NB_HIP(hipGetLastError());
@@ -628,7 +649,7 @@ static int all_pairs_describe(const nbody_state* s, char* out, size_t len) {
   if (int rc = plan_all_pairs<T>(s, &p)) return rc;
   const char* t = sizeof(T) == 8 ? "double" : "float";
   const char* pair = sizeof(T) == 4 ? (s->sz >= kFarMinBodies ? "rsq+rcp[m y^3 at r2 >= 4 if sparse]" : "rsq+rcp")
-                                    : s->sz >= kFarMinBodies ? "far3[-eps if sparse]/near3" : "far3/near3";
+                                    : s->sz >= kFarMinBodies ? "far3m[-eps if sparse]/near3" : "far3m/near3";
   if (p.scalar) {
     bool collect = false;
     with_k1_instance(p, [&](auto r, auto js) {
@@ -644,13 +665,15 @@ static int all_pairs_describe(const nbody_state* s, char* out, size_t len) {
 }
 
 // Everything the K1 launch for this view needs from the stream's scratch slot, reserved ahead (nbody_create,
-// nbody_ctx_set_shard, nbody_ctx_configure_all_pairs) so that a recorded step never allocates: the packed records, the extent
-// keys and the turn words (one per target group: 32 KB at N = 2^20; this slot held 403 MB of chunk sums until round 3).
+// nbody_ctx_set_shard, nbody_ctx_configure_all_pairs) so that a recorded step never allocates: the packed records (in f64 their
+// pair constants too), the extent keys and the turn words (one per target group: 32 KB at N = 2^20; this slot held 403 MB of chunk sums until round 3).
 int ap_scratch_reserve(hipStream_t st, const nbody_state* s) {
   void* q             = nullptr;
   const size_t tsz    = s->dtype == NBODY_F32 ? 4 : 8;
   const size_t padded = (size_t(s->sz) + 2 * kTileJ - 1) / (2 * kTileJ) * (2 * kTileJ);  // K1 needs whole tiles, the streamed K2 pairs of them
   if (int r = ap_scratch_get(st, 0, 4 * tsz * padded, &q)) return r;
+  if (s->dtype == NBODY_F64)
+    if (int r = ap_scratch_get(st, 6, ap_cst_bytes(padded), &q)) return r;
   if (int r = ap_scratch_get(st, 3, ap_rule_bytes(s->sz, s->dim), &q)) return r;
   return dispatch(s->dtype, s->dim, [&](auto tg) {
     using T = typename decltype(tg)::type;
@@ -1371,7 +1394,7 @@ extern "C" int nbody_all_pairs_pair_rule(const nbody_state* s, void* stream, int
     using T         = typename decltype(tg)::type;
     constexpr int D = decltype(tg)::dim;
     const k1_rule* rule = nullptr;
-    if (int r = ap_prepare<T, D>(s, as_stream(stream), false, nullptr, &rule, nullptr, 0)) return r;
+    if (int r = ap_prepare<T, D>(s, as_stream(stream), false, nullptr, nullptr, &rule, nullptr, 0)) return r;
     if (rule == nullptr) return int(NBODY_OK);  // below kFarMinBodies: the dense rule by definition
     k1_rule host;
     NB_HIP(hipMemcpyAsync(&host, rule, sizeof host, hipMemcpyDeviceToHost, as_stream(stream)));

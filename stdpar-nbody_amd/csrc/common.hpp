@@ -137,6 +137,8 @@ inline int dispatch(int dtype, int dim, F&& f) {
 // Which form a pair takes depends on ITS OWN r2 alone (never on the other lanes of the wave), so a target's sum is bitwise
 // independent of the shard window.  Every form is within 2.5 ulp of the exact term with no bias
 // (tests/test_gpu_all_pairs.py::test_pair_term_accuracy, test_pair_term_two_body_ulps, test_pair_math_adversarial_separations).
+// K1 (both twins, both source paths) takes the two weight_far forms with the source's mass folded into the polynomial's constants
+// — weight_far_folded below: 6 and 7 ops + 1 — K2, the energies, Hermite and the tree walks weight_far as it stands.
 // weight() with NBODY_PAIR_POLISH = 2 is what round 1 shipped everywhere and what the compiler-scheduled tree walks still use.
 //
 // r2 must be > 0: callers fold TINY into the first FMA of r2 (r2 = fma(dx,dx,TINY)), which makes the
@@ -215,6 +217,44 @@ struct pair_math<double> {
     double my = mj * y3;
     return __builtin_fma(my, g, my);
   }
+
+  // K1's form of the same series (f64, both K1 twins, LDS tiles and scalar stream alike) with the source's mass folded into
+  // the polynomial's constants.  `my = mj*y3` above exists only because the mass multiplies a polynomial whose constants are
+  // global; with M15 = fl(1.5 mj) and M1875 = fl(1.875 mj) made ONCE per source (src_cst below: plain multiplies, by the
+  // pre-pass or per lane after the ds_read) the polynomial delivers mj (1 + e(3/2 + 15/8 e)) directly:
+  //     t = fma(e, M1875, M15);  s = fma(t, e, mj);  w = y3 * s                  6 full-rate ops + 1 transcendental (was 7)
+  // The eps term, where a pair takes it, goes into e instead of into the sum: r^3 + eps = (r2 + 2/3 eps y + O(eps^2))^(3/2), so
+  //     e' = 1 - (r2 + 2/3 eps y) y^2 = fma(-2/3 eps, y3, e)                     7 + 1 (was 8)
+  // and the SAME polynomial in e' carries both corrections, their cross term included (weight_far adds -eps y^3 beside
+  // e(3/2 + 15/8 e) and leaves the cross term 3 e eps y^3 out: up to 2^-21.6 * 2^-28, +-8 ulp at r2 = 2^-16); what is left out
+  // here is (eps u)^2 / 6 < 2^-58.  No per-source quantity is needed for it: 2/3 eps is one scalar constant (pair_consts).
+  // The rounding budget is that of weight_far: a and y3, ONE rounding at mass scale (M15 and M1875 are rounded, but they multiply
+  // e <= 2^-23: 2^-76 of the weight), the last product (tests/test_folded_weight.py emulates old and new in exact arithmetic).
+  // Bits change, accuracy does not.
+  // Operands: a VOP3 instruction of this chip reads ONE scalar value, and t has two per-source operands — so in the scalar
+  // stream M1875 arrives in SGPRs like the record itself, while M15 must be in a VGPR pair WITHOUT a VALU instruction having
+  // put it there (two v_mov per source would give back half of the op saved): all 64 lanes load the same 16 bytes
+  // (M15 of the batch's two sources) with one vector-memory instruction, requested a batch ahead (k1_sgpr_body.inc).
+  // fma(-0, y3, e) == e bit for bit (y3 > 0: the product is -0, and e + (-0) == e also for e == +-0), so a lane that selects
+  // 0 instead of 2/3 eps for a far pair of a MIXED batch gets the bits of the all-far batch's form: a pair's weight depends on
+  // that pair alone.  A zero-mass padding record has M15 = M1875 = 0 and w = y3 * 0 = 0.
+  // SMASS (mj is in SGPRs and this is its only use: the softened twin at one target per lane): s is written as the VOP3
+  // instruction it should be — hipcc otherwise copies mj into a VGPR pair with two v_mov per source to make it the tied
+  // accumulator of a v_fmac, which costs more than the multiply saved.
+  static constexpr double eps23 = 2.0 / 3.0 * DBL_EPSILON;
+  template <bool EPS, bool SMASS = false>
+  __device__ static __forceinline__ double weight_far_folded(double r2, double mj, double m15, double m1875, double keps = eps23) {
+    double y  = __builtin_amdgcn_rsq(r2);
+    double a  = y * y;
+    double e  = __builtin_fma(-r2, a, 1.0);
+    double y3 = a * y;
+    if constexpr (EPS) e = __builtin_fma(-keps, y3, e);  // keps: 2/3 eps (pair_consts), or a lane's own choice of that / 0
+    double t = __builtin_fma(e, m1875, m15);
+    double s;
+    if constexpr (SMASS) asm("v_fma_f64 %0, %1, %2, %3" : "=v"(s) : "v"(t), "v"(e), "s"(mj));
+    else s = __builtin_fma(t, e, mj);
+    return y3 * s;
+  }
 };
 
 template <>
@@ -240,6 +280,24 @@ template <typename T, int D>
 struct alignas(sizeof(T) * 4) src_rec {
   T p[3];  // D used
   T m;
+};
+
+// Per-source constants of K1's f64 pair form (pair_math<double>::weight_far_folded): M15 = fl(1.5 m), M1875 = fl(1.875 m), by
+// plain multiplies wherever they are made, so that every producer rounds the same — the pre-pass of the scalar stream (cst_batch
+// below) and the LDS-tile form, per lane after its ds_read.  Float has none.
+template <typename T>
+struct src_cst {
+  __device__ __forceinline__ static src_cst of(T) { return {}; }
+};
+template <>
+struct src_cst<double> {
+  double m15, m1875;
+  __device__ __forceinline__ static src_cst of(double m) { return {1.5 * m, 1.875 * m}; }
+};
+// What the scalar stream reads beside a 64-byte batch of two f64 records (sources 2b and 2b + 1): M15 of both in the first 16
+// bytes — ONE wave-uniform global_load_dwordx4 puts them into VGPRs — and M1875 of both in the second — one s_load_dwordx4.
+struct alignas(32) cst_batch {
+  double m15[2], m1875[2];
 };
 
 // acc += w * (xj - xi) with r2 built by FMAs starting from TINY.
@@ -322,9 +380,11 @@ struct pair_consts {
 template <>
 struct pair_consts<double> {
   double k15, k1875;
-  __device__ __forceinline__ pair_consts() : k15(1.5), k1875(1.875) {
+  double keps;  // 2/3 eps of K1's folded form (weight_far_folded), in an SGPR pair; no instruction where it is not used
+  __device__ __forceinline__ pair_consts() : k15(1.5), k1875(1.875), keps(pair_math<double>::eps23) {
     asm volatile("" : "+v"(k15));
     asm volatile("" : "+s"(k1875));
+    asm("" : "+s"(keps));
   }
 };
 
@@ -333,16 +393,17 @@ struct pair_consts<double> {
 // common head of the two rules above the branch and interleaves the f32 pair chains, which costs 15 % (24.4 against 21.2 ms at
 // config 3) — (ap_far_mode: the variances of ALL positions say that few batches can hold a pair closer than 2 — k1_rule below;
 // every rank and every shard window of one system computes the same bits) and selects the per-pair rule:
-//   dense (ffar false): f64 weight_far<true> for r2 >= 2^-16, weight<3>() below; f32 weight().
-//   sparse (ffar true): f64 weight_far<false> for r2 >= 4, weight_far<true> in [2^-16, 4), weight<3>() below;
+//   dense (ffar false): f64 weight_far_folded<true> for r2 >= 2^-16, weight<3>() below; f32 weight().
+//   sparse (ffar true): f64 weight_far_folded<false> for r2 >= 4, weight_far_folded<true> in [2^-16, 4), weight<3>() below;
 //                       f32 m y^3 for r2 >= 4, weight() below.
+// f64 takes the sources' constants kc (src_cst: M15, M1875) beside the records.
 // The smallest r2 of the batch (one v_min3_u32 per two pairs on the high words) decides with one wave-uniform branch which code
 // runs; in a mixed batch each lane keeps, pair by pair, what its own r2 asks for.  Under a given rule a pair's term depends on
 // that pair alone, never on which other targets share the wave: results stay bitwise independent of the shard window.
 // (In the dense regime the sparse rule would put every batch on the mixed path: measured 3.20 against 2.62 ms at config 2.)
 template <typename T, int D, int R, int U, bool ffar>
 __device__ __forceinline__ void pair_batch(T (&acc)[R][D], const T (&xi)[R][D], const src_rec<T, D> (&s)[U],
-                                           const pair_consts<T>& pc) {
+                                           const src_cst<T> (&kc)[U], const pair_consts<T>& pc) {
   if constexpr (sizeof(T) == 4) {
     if constexpr (!ffar) {
 #pragma unroll
@@ -409,11 +470,12 @@ __device__ __forceinline__ void pair_batch(T (&acc)[R][D], const T (&xi)[R][D], 
         lowest            = hi < lowest ? hi : lowest;
       }
     if constexpr (!ffar) {
-      // dense system: every pair takes weight_far<true> unless some lane holds one below 2^-16
+      // dense system: every pair takes the eps form unless some lane holds one below 2^-16
 #pragma unroll
       for (int u = 0; u < U; ++u)
 #pragma unroll
-        for (int r = 0; r < R; ++r) w[u][r] = pair_math<T>::template weight_far<true>(r2[u][r], s[u].m, pc.k15, pc.k1875);
+        for (int r = 0; r < R; ++r)
+          w[u][r] = pair_math<T>::template weight_far_folded<true>(r2[u][r], s[u].m, kc[u].m15, kc[u].m1875, pc.keps);
       if (__builtin_expect(__builtin_amdgcn_ballot_w64(lowest < pair_math<T>::near_hi) != 0ull, 0)) {
 #pragma unroll
         for (int u = 0; u < U; ++u)
@@ -429,17 +491,17 @@ __device__ __forceinline__ void pair_batch(T (&acc)[R][D], const T (&xi)[R][D], 
 #pragma unroll
       for (int u = 0; u < U; ++u)
 #pragma unroll
-        for (int r = 0; r < R; ++r) w[u][r] = pair_math<T>::template weight_far<false>(r2[u][r], s[u].m, pc.k15, pc.k1875);
+        for (int r = 0; r < R; ++r) w[u][r] = pair_math<T>::template weight_far_folded<false>(r2[u][r], s[u].m, kc[u].m15, kc[u].m1875);
     } else {
-      // sparse system, some pair is closer: every lane keeps, pair by pair, what ITS r2 asks for — eps or 0 in the far form ...
+      // sparse system, some pair is closer: every lane keeps, pair by pair, what ITS r2 asks for — 2/3 eps or 0 in the far form
+      // (fma(-0, y3, e) == e: a far pair gets the bits of the all-far batch above) ...
 #pragma unroll
       for (int u = 0; u < U; ++u)
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-          const uint32_t hi  = uint32_t(__builtin_bit_cast(unsigned long long, r2[u][r]) >> 32);
-          const uint32_t ehi = hi < pair_math<T>::far_hi ? 0x3CB00000u : 0u;  // high word of DBL_EPSILON (its low word is 0)
-          const T eps        = __builtin_bit_cast(T, (unsigned long long)ehi << 32);
-          w[u][r]            = pair_math<T>::template weight_far<true>(r2[u][r], s[u].m, pc.k15, pc.k1875, eps);
+          const uint32_t hi = uint32_t(__builtin_bit_cast(unsigned long long, r2[u][r]) >> 32);
+          const T mine      = hi < pair_math<T>::far_hi ? pc.keps : T(0);
+          w[u][r]           = pair_math<T>::template weight_far_folded<true>(r2[u][r], s[u].m, kc[u].m15, kc[u].m1875, mine);
         }
       // ... and the guarded reciprocal form below 2^-16 (the self pair, coincident or very close bodies)
       if (__builtin_expect(__builtin_amdgcn_ballot_w64(lowest < pair_math<T>::near_hi) != 0ull, 0)) {
@@ -462,11 +524,20 @@ __device__ __forceinline__ void pair_batch(T (&acc)[R][D], const T (&xi)[R][D], 
   }
 }
 
+// float has no per-source constants: the form K2's compiler-scheduled kernel calls
+template <typename T, int D, int R, int U, bool ffar>
+__device__ __forceinline__ void pair_batch(T (&acc)[R][D], const T (&xi)[R][D], const src_rec<T, D> (&s)[U], const pair_consts<T>& pc) {
+  static_assert(sizeof(T) == 4, "f64 callers pass the sources' constants (src_cst)");
+  const src_cst<T> none[U] = {};
+  pair_batch<T, D, R, U, ffar>(acc, xi, s, none, pc);
+}
+
 // ---- softened pairs (ABI 2.4: nbody_all_pairs_softened_force, the softened octree walk and energies) -----------------------
 // Plummer softening: the pair term is  m_j * (x_j - x_i) / (r2 + e2)^(3/2),  e2 = fl_T(eps * eps) > 0, with r2 + e2 built by the
 // same FMA chain the unsoftened kernels use, seeded with e2 where they seed `tiny`.  q = r2 + e2 >= e2 never reaches 0, so there is
 // no eps term, no near-pair branch and no pair rule: the self pair and coincident bodies add w * 0 = 0 because their difference is 0.
-//   f64: weight_far<false> above, (m y^3)(1 + e(3/2 + 15/8 e)), y = v_rsq_f64(q): 7 full-rate ops + 1 transcendental, <= 2.5 ulp.
+//   f64: weight_far<false> above, (m y^3)(1 + e(3/2 + 15/8 e)), y = v_rsq_f64(q): 7 full-rate ops + 1 transcendental, <= 2.5 ulp
+//        (soft_weight: the octree walk, Hermite); K1's twin takes the same series as weight_far_folded<false>: 6 + 1.
 //   f32: m y^3 from the 1-ulp v_rsq_f32: 3 ops + 1 transcendental, <= ~3 ulp.
 // y^3 = q^(-3/2) must stay finite for q = e2, which bounds e2 from below (check_softening: kSoftMinE2).
 template <typename T>
@@ -480,9 +551,10 @@ __device__ __forceinline__ T soft_weight(T q, T mj, const pair_consts<T>& pc) {
 }
 
 // K1's unit of work in the softened form: U source records against the R targets of a lane, stage by stage like pair_batch.
-template <typename T, int D, int R, int U>
+// SSRC: the records are in SGPRs (the scalar stream).
+template <typename T, int D, int R, int U, bool SSRC = false>
 __device__ __forceinline__ void pair_batch_soft(T (&acc)[R][D], const T (&xi)[R][D], const src_rec<T, D> (&s)[U],
-                                                const pair_consts<T>& pc, T e2) {
+                                                const src_cst<T> (&kc)[U], const pair_consts<T>& pc, T e2) {
   T d[U][R][D], q[U][R], w[U][R];
 #pragma unroll
   for (int u = 0; u < U; ++u)
@@ -498,7 +570,11 @@ __device__ __forceinline__ void pair_batch_soft(T (&acc)[R][D], const T (&xi)[R]
 #pragma unroll
   for (int u = 0; u < U; ++u)
 #pragma unroll
-    for (int r = 0; r < R; ++r) w[u][r] = soft_weight<T>(q[u][r], s[u].m, pc);
+    for (int r = 0; r < R; ++r) {
+      if constexpr (sizeof(T) == 8)
+        w[u][r] = pair_math<T>::template weight_far_folded<false, SSRC && R == 1>(q[u][r], s[u].m, kc[u].m15, kc[u].m1875);
+      else w[u][r] = soft_weight<T>(q[u][r], s[u].m, pc);
+    }
 #pragma unroll
   for (int u = 0; u < U; ++u)
 #pragma unroll
@@ -572,6 +648,35 @@ __device__ __forceinline__ void swait(sgpr16& v, V& tie) {
   asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(v), "+v"(tie));
 }
 
+// The constants of a batch of two f64 sources (cst_batch) on their way into registers, beside the batch's records: m15 by a
+// wave-uniform vector load (every lane reads the same 16 bytes: one cache line, one instruction on the VMEM pipe, no VALU),
+// m1875 by a scalar load.  Requested with the records, a compute phase ahead; completed by cswait, which is swait with vmcnt(0)
+// added — vector loads return in order, and when a batch is waited for the NEXT one has not been requested yet, so 0 is the
+// exact count.  hipcc does not count these loads; its own waits can only become stricter by them (a wait on vmcnt(n) for one of
+// its loads allows n NEWER loads in flight, and there are at least as many as it knows of).
+typedef uint32_t reg4 __attribute__((ext_vector_type(4)));
+struct cst_regs {
+  reg4 v, s;
+};
+template <typename V>
+__device__ __forceinline__ cst_regs cload(const void* p, uint32_t vzero, V& tie) {  // p wave-uniform, 16-byte aligned; vzero: 0 in a VGPR
+  cst_regs r;
+  asm volatile("global_load_dwordx4 %0, %3, %4\n\ts_load_dwordx4 %1, %4, 0x10" : "=&v"(r.v), "=&s"(r.s), "+v"(tie) : "v"(vzero), "s"(p));
+  return r;
+}
+template <typename V>
+__device__ __forceinline__ void cswait(sgpr16& v, cst_regs& c, V& tie) {
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" : "+s"(v), "+v"(c.v), "+s"(c.s), "+v"(tie));
+}
+__device__ __forceinline__ void cst_unpack(const cst_regs& c, src_cst<double> (&kc)[2]) {
+  struct pair_t {
+    double d[2];
+  };
+  const pair_t v = __builtin_bit_cast(pair_t, c.v), s = __builtin_bit_cast(pair_t, c.s);
+  kc[0] = {v.d[0], s.d[0]};
+  kc[1] = {v.d[1], s.d[1]};
+}
+
 // K1 launch shape: validation shared by the process-wide default and the per-context setting
 inline int check_tuning(int split, int tpt, int path) {
   NB_ARG(split == 0 || split == 1 || split == 2 || split == 4 || split == 8, "split must be 0, 1, 2, 4 or 8 (got %d)", split);
@@ -583,7 +688,7 @@ inline int check_tuning(int split, int tpt, int path) {
 // all_pairs.hip: per-(device, stream) packed-source scratch of the scalar-stream K1 (reserved by nbody_create, freed by nbody_destroy)
 int ap_scratch_reserve(hipStream_t st, const nbody_state* view);
 void ap_scratch_release(hipStream_t st);
-int ap_scratch_get(hipStream_t st, int which, size_t bytes, void** out);  // which: 0 packed sources, 1 K1 turn words, 2 energies, 3 the pair rule (k1_rule + the blocks' partial moments), 4 K1 hand-off status, 5 K1 chunk sums of small launches
+int ap_scratch_get(hipStream_t st, int which, size_t bytes, void** out);  // which: 0 packed sources, 1 K1 turn words, 2 energies, 3 the pair rule (k1_rule + the blocks' partial moments), 4 K1 hand-off status, 5 K1 chunk sums of small launches, 6 the packed sources' f64 pair constants
 void ap_status_mark(hipStream_t st);  // a recorded step is being replayed on st: it may hold a turn-passing K1
 int ap_status_read(hipStream_t st, unsigned long long out[6], bool clear);  // waits for the stream; NBODY_ERR_STATE while a K1 hand-off failure is recorded
 int ap_pack_sources(const nbody_state* s, hipStream_t st, void** packed_out);

@@ -1,8 +1,9 @@
 // Body of K1's scalar-stream form, included by all_pairs_force_sgpr_kernel (K1_SOFT false) and by its softened twin
 // all_pairs_softened_sgpr_kernel (K1_SOFT true: pair_batch_soft with e2, no pair rule; slices, chunks, the hand-off and the
 // collect path are this same text).  Included in the kernels' own bodies rather than called as an inlined device function:
-// inlining reorders hipcc's output for the unsoftened kernel, which must stay instruction for instruction what it was.
-// In scope: T, D, R, JS, RULE, packed, x, a, c, sz, first, count, tiles_per_chunk, h, rule, e2.
+// inlining reorders hipcc's output for the unsoftened kernel, whose loop is checked instruction by instruction
+// (tools/check_smem_pipeline.py, tools/check_k1_cst_loads.py).
+// In scope: T, D, R, JS, RULE, packed, cst, x, a, c, sz, first, count, tiles_per_chunk, h, rule, e2.
   using rec_t = src_rec<T, D>;
   constexpr int TG  = kSgprWaves<JS> / JS;
   constexpr int TB  = TG * 64 * R;
@@ -37,29 +38,55 @@
     rec_t r[U];
   };
   auto batch = [&](uint32_t k) { return packed + (uint64_t(t0 + k / SUB) * kTileJ + uint32_t(jpart) * SUB + (k % SUB)); };
+  // f64: the constants of the batch's two sources (cst_batch, 32 bytes beside every 64 bytes of records) travel with it
+  constexpr bool CST = sizeof(T) == 8;
+  auto cbatch = [&](uint32_t k) { return cst + (uint64_t(t0 + k / SUB) * kTileJ + uint32_t(jpart) * SUB + (k % SUB)) / U; };
+  [[maybe_unused]] uint32_t vzero = 0;  // the vector load's lane offset
+  if constexpr (CST) {
+    asm volatile("" : "+v"(vzero));
+    // the targets' positions have landed BEFORE the loop: hipcc otherwise waits for them at their first use inside it, with
+    // vmcnt(0) on every trip — free while the loop held no vector load, a wait for the constants just requested now
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+      for (int k = 0; k < D; ++k) asm volatile("" : "+v"(xi[r][k]));
+  }
   // Two SGPR buffers, each requested (s_load_dwordx16) one compute phase before it is consumed.  Written with inline
   // asm: hipcc folds a loop-carried load from read-only memory back into a load at the loop top and waits for it there.
-  // SMEM returns out of order, so the only usable wait is lgkmcnt(0): wait for X, request Y, consume X.
+  // SMEM returns out of order, so the only usable wait is lgkmcnt(0): wait for X, request Y, consume X.  In f64 every request
+  // is preceded by the request for the batch's constants (cload: M15 into four VGPRs by a wave-uniform vector load, M1875 into
+  // four SGPRs) and every wait also waits for them (cswait: vmcnt(0), exact for the same reason) — a phase is ~340 VALU cycles
+  // of this wave alone, so neither wait stalls in the steady state.  The records' request comes LAST: the hand-off tail begins
+  // behind the last s_load_dwordx16 of the program (tools/check_k1_handoff.py).
   auto run = [&](auto ff) {  // the source stream, once per pair rule (pair_batch)
     constexpr bool FF = decltype(ff)::value;
-    sgpr16 A = sload16(batch(0), xi[0][0]), B;
+    sgpr16 A, B;
+    [[maybe_unused]] cst_regs CA, CB;
+    auto request = [&](sgpr16& S, cst_regs& C, uint32_t k) {
+      if constexpr (CST) C = cload(cbatch(k), vzero, xi[0][0]);
+      S = sload16(batch(k), xi[0][0]);
+    };
+    auto wait = [&](sgpr16& S, cst_regs& C) {
+      if constexpr (CST) cswait(S, C, acc[0][0]);
+      else swait(S, acc[0][0]);
+    };
+    auto consume = [&](const sgpr16& S, const cst_regs& C) {
+      const batch_t b = __builtin_bit_cast(batch_t, S);
+      src_cst<T> kc[U];
+      if constexpr (CST) cst_unpack(C, kc);
+      if constexpr (K1_SOFT) pair_batch_soft<T, D, R, U, true>(acc, xi, b.r, kc, pc, e2);
+      else pair_batch<T, D, R, U, FF>(acc, xi, b.r, kc, pc);
+    };
+    request(A, CA, 0);
     for (uint32_t k = 0; k < nsteps; k += 2 * U) {
-      swait(A, acc[0][0]);
-      B = sload16(batch(k + U), xi[0][0]);
-      {
-        const batch_t ba = __builtin_bit_cast(batch_t, A);
-        if constexpr (K1_SOFT) pair_batch_soft<T, D, R, U>(acc, xi, ba.r, pc, e2);
-        else pair_batch<T, D, R, U, FF>(acc, xi, ba.r, pc);
-      }
-      swait(B, acc[0][0]);
-      A = sload16(batch(k + 2 * U < nsteps ? k + 2 * U : k), xi[0][0]);  // the last iteration re-requests its own batch
-      {
-        const batch_t bb = __builtin_bit_cast(batch_t, B);
-        if constexpr (K1_SOFT) pair_batch_soft<T, D, R, U>(acc, xi, bb.r, pc, e2);
-        else pair_batch<T, D, R, U, FF>(acc, xi, bb.r, pc);
-      }
+      wait(A, CA);
+      request(B, CB, k + U);
+      consume(A, CA);
+      wait(B, CB);
+      request(A, CA, k + 2 * U < nsteps ? k + 2 * U : k);  // the last iteration re-requests its own batch
+      consume(B, CB);
     }
-    swait(A, acc[0][0]);  // nothing in flight when the wave goes on
+    wait(A, CA);  // nothing in flight when the wave goes on
   };
   if constexpr (K1_SOFT) run(std::false_type{});           // one pair form: no rule to choose
   else if constexpr (RULE == 1) run(std::false_type{});  // (experiments: one rule per instantiation, forced from the host)

@@ -68,10 +68,14 @@
 #pragma unroll 2
       for (int jj = 0; jj < SUB; jj += U) {
         rec_t s[U];
+        src_cst<T> kc[U];  // f64: the sources' constants, the multiplies the scalar stream's pre-pass makes (bitwise the same pair)
 #pragma unroll
-        for (int u = 0; u < U; ++u) s[u] = src[jj + u];  // wave-uniform address: LDS broadcast
-        if constexpr (K1_SOFT) pair_batch_soft<T, D, R, U>(acc, xi, s, pc, e2);
-        else pair_batch<T, D, R, U, FF>(acc, xi, s, pc);
+        for (int u = 0; u < U; ++u) {
+          s[u]  = src[jj + u];  // wave-uniform address: LDS broadcast
+          kc[u] = src_cst<T>::of(s[u].m);
+        }
+        if constexpr (K1_SOFT) pair_batch_soft<T, D, R, U>(acc, xi, s, kc, pc, e2);
+        else pair_batch<T, D, R, U, FF>(acc, xi, s, kc, pc);
       }
     }
   };
