@@ -112,12 +112,34 @@ __global__ __launch_bounds__(kBlock) void pack_sources_kernel(const T* __restric
 //   MOMENTS  the first and second moments of all sz positions, relative to body 0 (so that a system far from the origin does not
 //            cancel), summed per block in a fixed order; the LAST block to deliver (a ticket) adds the blocks' sums in index order
 //            and writes the rule (common.hpp: k1_rule) — the same bits whichever block comes last;
+//   BOX      (f64 with PACK and MOMENTS, where the launch asks for it: bpc != 0) the bounding box of every source chunk of the
+//            launch, for K1's far certificate (common.hpp: k1_block_is_far).  A chunk is a whole number of prepare blocks (bpc of
+//            them), so every block stores the box of its 256 records — padding records, at the origin, included; the whole line
+//            on every axis if one of them is not finite, so that nothing K1 compares with such a chunk certifies — and the last
+//            block reduces each chunk's boxes.  Min and max are order-free: the same bits on every rank, whatever the order;
 //   and the last block also hands the turn of every target group back to chunk 0 (the words K1's chunks pass around).
 // One block per 256 bodies of the padded set; the ticket returns to 0, so a recorded launch can be replayed.
+// The kernel's last argument.  Only f64 has boxes, and the f32 kernels keep the argument block (and so the code) they had.
+template <typename T>
+struct k1_prepare_tail {
+  uint32_t turn_words;
+};
+template <>
+struct k1_prepare_tail<double> {
+  uint32_t turn_words;
+  uint32_t bpc;   // prepare blocks per source chunk; 0: no boxes
+  double* cbox;   // [chunk][lo[D], hi[D]]
+  double* pbox;   // the same per prepare block
+};
 template <typename T, int D, bool PACK, bool MOMENTS>
 __global__ __launch_bounds__(kBlock) void k1_prepare_kernel(const T* __restrict__ m, const T* __restrict__ x, src_rec<T, D>* __restrict__ out,
                                                             cst_batch* __restrict__ cst, uint32_t sz, uint32_t padded, k1_rule* rule, double* partial,
-                                                            uint32_t* turn, uint32_t turn_words) {
+                                                            uint32_t* turn, k1_prepare_tail<T> tail) {
+  constexpr bool BOX        = PACK && MOMENTS && sizeof(T) == 8;
+  const uint32_t turn_words = tail.turn_words;
+  [[maybe_unused]] uint32_t bpc = 0;
+  [[maybe_unused]] T *cbox = nullptr, *pbox = nullptr;
+  if constexpr (BOX) bpc = tail.bpc, cbox = tail.cbox, pbox = tail.pbox;
   const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
   T p[D];
 #pragma unroll
@@ -137,6 +159,7 @@ __global__ __launch_bounds__(kBlock) void k1_prepare_kernel(const T* __restrict_
     }
   }
   __shared__ double red[2 * D][kWaves];
+  __shared__ T bred[BOX ? 2 * D : 1][kWaves];
   __shared__ bool last_s;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if constexpr (MOMENTS) {
@@ -160,11 +183,45 @@ __global__ __launch_bounds__(kBlock) void k1_prepare_kernel(const T* __restrict_
         red[D + k][wave] = s2[k];
       }
     }
+    if constexpr (BOX) {
+      if (bpc != 0) {  // the box of this block's records as they are packed: p is 0 for a padding record
+        bool finite = true;
+#pragma unroll
+        for (int k = 0; k < D; ++k) finite = finite && (p[k] - p[k]) == T(0);
+        T lo[D], hi[D];
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+          lo[k] = finite ? p[k] : -T(__builtin_inf());
+          hi[k] = finite ? p[k] : T(__builtin_inf());
+        }
+#pragma unroll
+        for (int k = 0; k < D; ++k)
+          for (int off = 32; off > 0; off >>= 1) {
+            lo[k] = __builtin_fmin(lo[k], __shfl_xor(lo[k], off, 64));
+            hi[k] = __builtin_fmax(hi[k], __shfl_xor(hi[k], off, 64));
+          }
+        if (lane == 0) {
+#pragma unroll
+          for (int k = 0; k < D; ++k) {
+            bred[k][wave]     = lo[k];
+            bred[D + k][wave] = hi[k];
+          }
+        }
+      }
+    }
     __syncthreads();
     if (threadIdx.x < 2 * D) {
       double v = red[threadIdx.x][0];
       for (int w = 1; w < kWaves; ++w) v += red[threadIdx.x][w];
       __hip_atomic_store(partial + size_t(blockIdx.x) * (2 * D) + threadIdx.x, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if constexpr (BOX) {
+      if (bpc != 0 && threadIdx.x >= 64 && threadIdx.x < 64 + 2 * D) {  // (wave 1: wave 0 stores the moments)
+        const int q = int(threadIdx.x) - 64;
+        T v         = bred[q][0];
+        for (int w = 1; w < kWaves; ++w) v = q < D ? __builtin_fmin(v, bred[q][w]) : __builtin_fmax(v, bred[q][w]);
+        __hip_atomic_store(pbox + size_t(blockIdx.x) * (2 * D) + q, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
     }
   }
   // The ticket: the block that draws the last number knows that every other block's partial sums are out.  No __threadfence():
@@ -214,6 +271,52 @@ __global__ __launch_bounds__(kBlock) void k1_prepare_kernel(const T* __restrict_
       }
       rule->volume = vol;
       rule->sparse = vol >= kFarMinVolume<D> ? 1u : 0u;
+    }
+  }
+  if constexpr (BOX) {
+    if (bpc != 0) {
+      // sixteen chunks at a time, sixteen neighbouring lanes per chunk: lane `sub` takes the chunk's blocks sub, sub + 16, ...
+      // (four rows of loads in flight), the sixteen meet by a butterfly inside their group of lanes, lane 0 of the group stores
+      const uint32_t nchunks = (gridDim.x + bpc - 1) / bpc;
+      const uint32_t sub     = threadIdx.x & 15u;
+      for (uint32_t c0 = 0; c0 < nchunks; c0 += kBlock / 16) {
+        const uint32_t c  = c0 + (threadIdx.x >> 4);
+        const uint32_t b1 = c < nchunks ? min(gridDim.x, (c + 1u) * bpc) : 0u;
+        T lo[D], hi[D];
+#pragma unroll
+        for (int k = 0; k < D; ++k) lo[k] = T(__builtin_inf()), hi[k] = -T(__builtin_inf());
+        for (uint32_t b0 = c * bpc + sub; b0 < b1; b0 += 16u * 4u) {
+          T v[4][2 * D];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const uint32_t b = b0 + 16u * uint32_t(u);
+#pragma unroll
+            for (int q = 0; q < 2 * D; ++q)
+              v[u][q] = b < b1 ? __hip_atomic_load(pbox + size_t(b) * (2 * D) + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                               : (q < D ? T(__builtin_inf()) : -T(__builtin_inf()));
+          }
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int k = 0; k < D; ++k) {
+              lo[k] = __builtin_fmin(lo[k], v[u][k]);
+              hi[k] = __builtin_fmax(hi[k], v[u][D + k]);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < D; ++k)
+          for (int off = 8; off > 0; off >>= 1) {
+            lo[k] = __builtin_fmin(lo[k], __shfl_xor(lo[k], off, 64));
+            hi[k] = __builtin_fmax(hi[k], __shfl_xor(hi[k], off, 64));
+          }
+        if (c < nchunks && sub == 0) {
+#pragma unroll
+          for (int k = 0; k < D; ++k) {
+            cbox[size_t(c) * (2 * D) + k]     = lo[k];
+            cbox[size_t(c) * (2 * D) + D + k] = hi[k];
+          }
+        }
+      }
     }
   }
   for (uint32_t w = threadIdx.x; w < turn_words; w += kBlock) turn[w] = 0u;  // chunk 0 holds every turn
@@ -266,14 +369,31 @@ struct k1_handoff {
   uint32_t delay;     // s_sleep(127) rounds before a turn is passed on (0; the experiments build's tests make successors wait)
   uint32_t late;      // s_sleep(127) rounds before chunk 1's waves look at the turn word at all (0; experiments: a block started late)
 };
+// `box` (f64 launches that may take the sparse rule; else nullptr): the source chunks' bounding boxes of the pre-pass, lo[D], hi[D]
+// per chunk, for the far certificate (common.hpp: k1_block_is_far) — a block whose boxes prove every pair far streams its chunk
+// through a third copy of the loop that has no near/far test (pair_batch_far: the bits of an all-far batch).
+constexpr size_t kBoxHeaderBytes = 64;  // in front of the boxes (experiments build: the count of certified blocks)
+// The kernel's last argument: the rule, and in f64 the boxes — the f32 kernels keep the argument block (and so the code) they had.
+template <typename T>
+struct k1_rule_arg {
+  const k1_rule* rule;
+};
+template <>
+struct k1_rule_arg<double> {
+  const k1_rule* rule;
+  const double* box;
+};
 template <typename T, int D, int R, int JS, int RULE = 0>
 __global__ __launch_bounds__(64 * kSgprWaves<JS>) void all_pairs_force_sgpr_kernel(const src_rec<T, D>* __restrict__ packed,
                                                                                    const cst_batch* __restrict__ cst,
                                                                                    const T* __restrict__ x, T* a, T c, uint32_t sz,
                                                                                    uint32_t first, uint32_t count,
                                                                                    uint32_t tiles_per_chunk, k1_handoff h,
-                                                                                   const k1_rule* __restrict__ rule) {
+                                                                                   k1_rule_arg<T> ra) {
   [[maybe_unused]] constexpr T e2 = T(0);
+  const k1_rule* __restrict__ const rule = ra.rule;
+  [[maybe_unused]] const T* __restrict__ box = nullptr;
+  if constexpr (sizeof(T) == 8) box = ra.box;
 #define K1_SOFT false
 #include "k1_sgpr_body.inc"
 #undef K1_SOFT
@@ -288,6 +408,7 @@ __global__ __launch_bounds__(64 * kSgprWaves<JS>) void all_pairs_softened_sgpr_k
                                                                                       uint32_t tiles_per_chunk, k1_handoff h, T e2) {
   constexpr int RULE = 0;
   const k1_rule* const rule = nullptr;
+  [[maybe_unused]] const T* const box = nullptr;  // no pair rule, no test to save: no certificate
 #define K1_SOFT true
 #include "k1_sgpr_body.inc"
 #undef K1_SOFT
@@ -306,7 +427,7 @@ struct scratch_buf {
 struct packed_slot {
   int device;
   hipStream_t stream;
-  scratch_buf buf[7];  // 0: packed sources, 1: K1 turn words, 2: energies work area, 3: the pair rule + partial moments, 4: K1 hand-off status (k1_status), 5: K1 chunk sums of small launches, 6: the packed sources' f64 pair constants (cst_batch)
+  scratch_buf buf[8];  // 0: packed sources, 1: K1 turn words, 2: energies work area, 3: the pair rule + partial moments, 4: K1 hand-off status (k1_status), 5: K1 chunk sums of small launches, 6: the packed sources' f64 pair constants (cst_batch), 7: the source chunks' boxes of the far certificate
   std::vector<void*> retired;
   bool k1_dirty  = false;  // a K1 that passes turns (or a recorded step, which may hold one) has been queued since the status was last read
   bool k1_failed = false;  // the last read found the sticky error set
@@ -338,7 +459,7 @@ int ap_scratch_get(hipStream_t st, int which, size_t bytes, void** out) {
   }
   void* fresh = nullptr;
   NB_HIP(hipMalloc(&fresh, bytes));  // on the stream's device: the caller holds a device_guard
-  if (which == 4 || which == 3) {    // the status block and the rule's ticket start at zero: ordered on the stream that will use
+  if (which == 4 || which == 3 || which == 7) {  // the status block and the rule's ticket start at zero (buffer 7: only for the experiments build's count in its header): ordered on the stream that will use
     // them (every launch that reads them is queued on `st` behind this call) — a synchronous memset would go through the legacy
     // stream, which has no defined order with a non-blocking `st` and would invalidate another thread's global-mode capture
     if (hipError_t e = hipMemsetAsync(fresh, 0, bytes, st); e != hipSuccess) {
@@ -469,12 +590,26 @@ static size_t ap_rule_bytes(uint32_t sz, int dim) {
   return 32 + sizeof(double) * 2 * size_t(dim) * (padded / kBlock);
 }
 
+// Bytes of scratch buffer 7 for a system of sz bodies: a header, a box (lo[dim], hi[dim] in double) per source chunk — there are
+// never more chunks than tiles — then one per prepare block.
+static size_t ap_box_bytes(uint32_t sz, int dim) {
+  const size_t ntiles = (size_t(sz) + kTileJ - 1) / kTileJ;
+  return kBoxHeaderBytes + sizeof(double) * 2 * size_t(dim) * (ntiles + ntiles * (kTileJ / kBlock));
+}
+// The far certificate is attempted by f64 scalar-stream launches that may take the sparse rule and cut their sources into chunks
+// (an explicit split has one chunk, whose box is the whole system: nothing to certify, nothing paid).  The automatic launch has
+// its chunks from sz alone, so this is a function of sz.  Measured, parent against new, at the shortest chunks the sparse rule
+// can meet (N = 32 768: 2048 sources) and at 65 536: profiles/r08/time_far_certificate.txt.
+static bool k1_box_wanted(uint32_t sz, uint32_t chunks) { return sz >= kFarMinBodies && chunks > 1; }
+
 // Everything a K1 launch needs done first, queued as ONE launch (k1_prepare_kernel): the packed records (pack: the scalar-stream
 // form), the pair rule of the whole system (sz >= kFarMinBodies; nullptr = "dense" below) and the turn words handed back to chunk 0.
-// The softened K1 has no pair rule (with_rule false): no moments are summed.
+// The softened K1 has no pair rule (with_rule false): no moments are summed.  box_tpc != 0 (f64, pack): the launch's tiles per
+// source chunk — the chunks' boxes are made too (*box_out; nullptr where the rule is dense by definition).
 template <typename T, int D>
 static int ap_prepare(const nbody_state* s, hipStream_t st, bool pack, src_rec<T, D>** packed_out, const cst_batch** cst_out,
-                      const k1_rule** rule_out, uint32_t* turn, size_t turn_words, bool with_rule = true) {
+                      const k1_rule** rule_out, uint32_t* turn, size_t turn_words, bool with_rule = true, uint32_t box_tpc = 0,
+                      const T** box_out = nullptr) {
   const uint32_t padded = (s->sz + kTileJ - 1) / kTileJ * kTileJ;
   const bool moments    = with_rule && s->sz >= kFarMinBodies;
   void* scratch         = nullptr;
@@ -490,13 +625,26 @@ static int ap_prepare(const nbody_state* s, hipStream_t st, bool pack, src_rec<T
   auto* partial = reinterpret_cast<double*>(static_cast<char*>(q) + 32);
   auto* out     = static_cast<src_rec<T, D>*>(scratch);
   auto* cst     = static_cast<cst_batch*>(consts);
+  T *cbox = nullptr, *pbox = nullptr;
+  uint32_t bpc = 0;  // prepare blocks per source chunk
+  if (sizeof(T) == 8 && pack && moments && box_tpc != 0) {
+    void* b = nullptr;
+    if (int r = ap_scratch_get(st, 7, ap_box_bytes(s->sz, D), &b)) return r;
+    cbox = reinterpret_cast<T*>(static_cast<char*>(b) + kBoxHeaderBytes);
+    pbox = cbox + size_t(2 * D) * (padded / kTileJ);
+    bpc  = box_tpc * (kTileJ / kBlock);
+  }
   const dim3 grid(padded / kBlock), block(kBlock);
   const T *m = static_cast<const T*>(s->m), *x = static_cast<const T*>(s->x);
   const uint32_t words = uint32_t(turn_words);
-  if (pack && moments) hipLaunchKernelGGL((k1_prepare_kernel<T, D, true, true>), grid, block, 0, st, m, x, out, cst, s->sz, padded, rule, partial, turn, words);
-  else if (pack) hipLaunchKernelGGL((k1_prepare_kernel<T, D, true, false>), grid, block, 0, st, m, x, out, cst, s->sz, padded, rule, partial, turn, words);
-  else if (moments) hipLaunchKernelGGL((k1_prepare_kernel<T, D, false, true>), grid, block, 0, st, m, x, out, cst, s->sz, padded, rule, partial, turn, words);
+  k1_prepare_tail<T> tail{};
+  tail.turn_words = words;
+  if constexpr (sizeof(T) == 8) tail.bpc = bpc, tail.cbox = cbox, tail.pbox = pbox;
+  if (pack && moments) hipLaunchKernelGGL((k1_prepare_kernel<T, D, true, true>), grid, block, 0, st, m, x, out, cst, s->sz, padded, rule, partial, turn, tail);
+  else if (pack) hipLaunchKernelGGL((k1_prepare_kernel<T, D, true, false>), grid, block, 0, st, m, x, out, cst, s->sz, padded, rule, partial, turn, tail);
+  else if (moments) hipLaunchKernelGGL((k1_prepare_kernel<T, D, false, true>), grid, block, 0, st, m, x, out, cst, s->sz, padded, rule, partial, turn, tail);
   NB_HIP(hipGetLastError());
+  if (box_out) *box_out = cbox;
   if (packed_out) *packed_out = out;
   if (cst_out) *cst_out = cst;
   *rule_out = moments ? rule : nullptr;
@@ -553,7 +701,12 @@ static int launch_all_pairs_sgpr(const nbody_state* s, const k1_plan& plan, hipS
   src_rec<T, D>* packed = nullptr;
   const cst_batch* cst  = nullptr;  // f64 only
   const k1_rule* rule   = nullptr;
-  if (int r = ap_prepare<T, D>(s, st, true, &packed, &cst, &rule, h.turn, h.turn ? sgpr_turn_words<R, JS>(s->count) : 0, !SOFT)) return r;
+  const T* box          = nullptr;  // f64, unsoftened, from kFarMinBodies on: the chunks' boxes of the far certificate
+  bool certify          = !SOFT && sizeof(T) == 8 && k1_box_wanted(s->sz, plan.chunks);
+  if (const char* e = experiment_env("NBODY_K1_NO_CERT"); e && e[0] == '1') certify = false;  // -DNBODY_EXPERIMENTS builds only
+  if (int r = ap_prepare<T, D>(s, st, true, &packed, &cst, &rule, h.turn, h.turn ? sgpr_turn_words<R, JS>(s->count) : 0, !SOFT,
+                               certify ? plan.tiles_per_chunk : 0u, &box))
+    return r;
   if constexpr (SOFT) {
     hipLaunchKernelGGL((all_pairs_softened_sgpr_kernel<T, D, R, JS>), dim3(blocks, plan.chunks), dim3(64 * kSgprWaves<JS>), 0, st,
                        packed, cst, static_cast<const T*>(s->x), static_cast<T*>(s->a), static_cast<T>(s->c), s->sz, s->first, s->count,
@@ -562,23 +715,26 @@ static int launch_all_pairs_sgpr(const nbody_state* s, const k1_plan& plan, hipS
     if (h.turn != nullptr && h.sums == nullptr) ap_status_mark(st);
     return NBODY_OK;
   }
+  k1_rule_arg<T> ra{};
+  ra.rule = rule;
+  if constexpr (sizeof(T) == 8) ra.box = box;
 #ifdef NBODY_EXPERIMENTS
   if (const char* e = getenv("NBODY_K1_RULE_FORCE"); e && JS == 8 && D == 3) {  // timing experiment: one rule per instantiation
     if (e[0] == '1')
       hipLaunchKernelGGL((all_pairs_force_sgpr_kernel<T, D, R, JS, 1>), dim3(blocks, plan.chunks), dim3(64 * kSgprWaves<JS>), 0, st,
                          packed, cst, static_cast<const T*>(s->x), static_cast<T*>(s->a), static_cast<T>(s->c), s->sz, s->first, s->count,
-                         plan.tiles_per_chunk, h, rule);
+                         plan.tiles_per_chunk, h, ra);
     else
       hipLaunchKernelGGL((all_pairs_force_sgpr_kernel<T, D, R, JS, 2>), dim3(blocks, plan.chunks), dim3(64 * kSgprWaves<JS>), 0, st,
                          packed, cst, static_cast<const T*>(s->x), static_cast<T*>(s->a), static_cast<T>(s->c), s->sz, s->first, s->count,
-                         plan.tiles_per_chunk, h, rule);
+                         plan.tiles_per_chunk, h, ra);
     NB_HIP(hipGetLastError());
     return NBODY_OK;
   }
 #endif
   hipLaunchKernelGGL((all_pairs_force_sgpr_kernel<T, D, R, JS>), dim3(blocks, plan.chunks), dim3(64 * kSgprWaves<JS>), 0, st,
                      packed, cst, static_cast<const T*>(s->x), static_cast<T*>(s->a), static_cast<T>(s->c), s->sz, s->first, s->count,
-                     plan.tiles_per_chunk, h, rule);
+                     plan.tiles_per_chunk, h, ra);
   NB_HIP(hipGetLastError());
   if (h.turn != nullptr && h.sums == nullptr) ap_status_mark(st);  // turns were passed: the next wait for this stream reads the status
   return NBODY_OK;
@@ -656,8 +812,9 @@ static int all_pairs_describe(const nbody_state* s, char* out, size_t len) {
       constexpr int TB = (kSgprWaves<decltype(js)::value> / decltype(js)::value) * 64 * decltype(r)::value;
       collect = k1_collect((s->count + TB - 1) / TB, p.chunks);
     });
-    snprintf(out, len, "all_pairs_force_sgpr_kernel<%s,%d,R=%d,JS=%d> tile=%d chunks=%u%s pair=%s", t, D, p.r, p.js, kTileJ, p.chunks,
-             p.chunks > 1 ? (collect ? "(summed in chunk order by the last to arrive)" : "(summed in turn into a)") : "", pair);
+    snprintf(out, len, "all_pairs_force_sgpr_kernel<%s,%d,R=%d,JS=%d> tile=%d chunks=%u%s pair=%s%s", t, D, p.r, p.js, kTileJ, p.chunks,
+             p.chunks > 1 ? (collect ? "(summed in chunk order by the last to arrive)" : "(summed in turn into a)") : "", pair,
+             sizeof(T) == 8 && k1_box_wanted(s->sz, p.chunks) ? " cert=box-gap>=3[if sparse: blocks proven far skip the r2 test]" : "");
   }
   else
     snprintf(out, len, "all_pairs_force_kernel<%s,%d,R=%d,JS=%d> tile=%d chunks=1 pair=%s", t, D, p.r, p.js, kTileJ, pair);
@@ -675,6 +832,8 @@ int ap_scratch_reserve(hipStream_t st, const nbody_state* s) {
   if (s->dtype == NBODY_F64)
     if (int r = ap_scratch_get(st, 6, ap_cst_bytes(padded), &q)) return r;
   if (int r = ap_scratch_get(st, 3, ap_rule_bytes(s->sz, s->dim), &q)) return r;
+  if (s->dtype == NBODY_F64 && s->sz >= kFarMinBodies)  // (whatever the launch shape turns out to be)
+    if (int r = ap_scratch_get(st, 7, ap_box_bytes(s->sz, s->dim), &q)) return r;
   return dispatch(s->dtype, s->dim, [&](auto tg) {
     using T = typename decltype(tg)::type;
     k1_plan p;
@@ -1434,6 +1593,32 @@ extern "C" int nbody_all_pairs_status(void* stream, uint64_t out[6], int clear) 
     for (int i = 0; i < 6; ++i) out[i] = v[i];
   return rc;
 }
+
+#ifdef NBODY_EXPERIMENTS
+// Experiments build only (tests/test_gpu_far_certificate.py): the number of (target group, source chunk) blocks that K1 launches of
+// this stream have certified far since the count was last cleared.  Waits for the stream.
+extern "C" int nbody_exp_k1_certified(void* stream, uint64_t* out, int clear) {
+  NB_ARG(out != nullptr, "out is NULL");
+  hipStream_t st = as_stream(stream);
+  const int dev  = stream_device(st);
+  device_guard guard(dev);
+  void* dptr = nullptr;
+  {
+    std::lock_guard<std::mutex> lock(g_packed_mu);
+    for (auto& sl : g_packed_slots)
+      if (sl.stream == st && sl.device == dev) dptr = sl.buf[7].ptr;
+  }
+  unsigned long long v = 0;
+  if (dptr) NB_HIP(hipMemcpyAsync(&v, dptr, sizeof v, hipMemcpyDeviceToHost, st));
+  NB_HIP(hipStreamSynchronize(st));
+  if (dptr && clear) {
+    NB_HIP(hipMemsetAsync(dptr, 0, sizeof v, st));
+    NB_HIP(hipStreamSynchronize(st));
+  }
+  *out = v;
+  return NBODY_OK;
+}
+#endif
 
 extern "C" int nbody_all_pairs_collapsed_force(const nbody_state* s, void* stream) {
   if (int r = check_state(s)) return r;

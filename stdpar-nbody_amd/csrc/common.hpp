@@ -524,6 +524,38 @@ __device__ __forceinline__ void pair_batch(T (&acc)[R][D], const T (&xi)[R][D], 
   }
 }
 
+// K1's unit of work in a block whose bounding boxes prove every pair far (k1_sgpr_body.inc: the certificate; f64, sparse rule; the records are in SGPRs).
+// Operation for operation what an all-far batch of pair_batch<ffar = true> executes — the same differences, the same r2 chain
+// seeded with `tiny`, weight_far_folded<false>, the same accumulations in the same order — without the smallest high word, the
+// compare and the branch: a target's sum has the same bits whether or not its blocks were certified.
+template <typename T, int D, int R, int U>
+__device__ __forceinline__ void pair_batch_far(T (&acc)[R][D], const T (&xi)[R][D], const src_rec<T, D> (&s)[U], const src_cst<T> (&kc)[U]) {
+  static_assert(sizeof(T) == 8, "the certified copy exists in f64 only");
+  T d[U][R][D], r2[U][R], w[U][R];
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+#pragma unroll
+      for (int k = 0; k < D; ++k) d[u][r][k] = s[u].p[k] - xi[r][k];
+      T q = pair_math<T>::tiny;
+#pragma unroll
+      for (int k = 0; k < D; ++k) q = __builtin_elementwise_fma(d[u][r][k], d[u][r][k], q);
+      r2[u][r] = q;
+    }
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+#pragma unroll
+    for (int r = 0; r < R; ++r)  // (SMASS at one target per lane, as in the softened twin: the same operation, no v_mov of the mass)
+      w[u][r] = pair_math<T>::template weight_far_folded<false, R == 1>(r2[u][r], s[u].m, kc[u].m15, kc[u].m1875);
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+      for (int k = 0; k < D; ++k) acc[r][k] = __builtin_elementwise_fma(w[u][r], d[u][r][k], acc[r][k]);
+}
+
 // float has no per-source constants: the form K2's compiler-scheduled kernel calls
 template <typename T, int D, int R, int U, bool ffar>
 __device__ __forceinline__ void pair_batch(T (&acc)[R][D], const T (&xi)[R][D], const src_rec<T, D> (&s)[U], const pair_consts<T>& pc) {
@@ -628,6 +660,41 @@ constexpr double kFarMinVolume = D == 3 ? 1.7e5 : 6.4e4;
 __device__ __forceinline__ bool ap_far_mode(const k1_rule* __restrict__ rule) {
   if (rule == nullptr) return false;
   return __builtin_amdgcn_readfirstlane(int(rule->sparse)) != 0;
+}
+
+// ---- the far certificate of a K1 block (f64 scalar stream, sparse rule) ---------------------------------------------------
+// The sparse rule asks every pair whether its computed r2 is >= 4.  For a block — one target group against one source chunk —
+// one comparison of two bounding boxes often answers for all of its pairs: if on some axis the boxes are kFarGap = 3 apart, every
+// pair's true separation is >= 3, r2 >= 9, and the three roundings of the r2 chain cannot bring the computed value below 4 (the
+// slack of 1 in the gap is there so that no rounding analysis is needed).  Such a block runs pair_batch_far.  The chunk's box
+// comes from the pre-pass (all_pairs.hip: k1_prepare_kernel; it covers every record of the chunk, padding included, and is the
+// whole line on every axis if a record is not finite); the targets' side is taken per lane, which is the group's box exactly:
+// fl(t - hi) is monotone in t, so "every lane's gap >= 3" is "the gap from the group's minimum >= 3".  An infinite gap — a target
+// that is not finite — does not count, and a comparison with NaN is false: non-finite positions never certify.  (A defence only:
+// the variances of such a system are NaN, the rule is dense and no certificate is attempted in the first place.)
+constexpr double kFarGap = 3.0;
+// chunk_box: lo[D], hi[D] of the block's source chunk, wave-uniform, through the constant address space — the pre-pass wrote the
+// boxes, nothing writes them while K1 runs, and the loads are scalar ones like those of the records
+template <typename T, int D, int R>
+__device__ __forceinline__ bool k1_block_is_far(const T (&xi)[R][D], const T __attribute__((address_space(4))) * chunk_box) {
+  bool far = false, finite = true;  // a group that holds a target with a coordinate that is not finite certifies on no axis
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+#pragma unroll
+    for (int k = 0; k < D; ++k) finite = finite & ((xi[r][k] - xi[r][k]) == T(0));
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    const T lo = chunk_box[k], hi = chunk_box[D + k];
+    bool above = true, below = true;  // this lane's targets lie above (below) the chunk on axis k, by the gap
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const T ga = xi[r][k] - hi, gb = lo - xi[r][k];
+      above = above & (ga >= T(kFarGap));  // (finite targets against a finite box or the whole line: the gap is finite or -inf)
+      below = below & (gb >= T(kFarGap));
+    }
+    far = far | (__builtin_amdgcn_ballot_w64(!above) == 0ull) | (__builtin_amdgcn_ballot_w64(!below) == 0ull);
+  }
+  return far & (__builtin_amdgcn_ballot_w64(!finite) == 0ull);
 }
 
 // ---- scalar-stream helpers (K1's default form, the energies) ------------------------------------------------

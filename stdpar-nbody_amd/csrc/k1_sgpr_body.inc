@@ -3,7 +3,7 @@
 // collect path are this same text).  Included in the kernels' own bodies rather than called as an inlined device function:
 // inlining reorders hipcc's output for the unsoftened kernel, whose loop is checked instruction by instruction
 // (tools/check_smem_pipeline.py, tools/check_k1_cst_loads.py).
-// In scope: T, D, R, JS, RULE, packed, cst, x, a, c, sz, first, count, tiles_per_chunk, h, rule, e2.
+// In scope: T, D, R, JS, RULE, packed, cst, x, a, c, sz, first, count, tiles_per_chunk, h, rule, e2, box.
   using rec_t = src_rec<T, D>;
   constexpr int TG  = kSgprWaves<JS> / JS;
   constexpr int TB  = TG * 64 * R;
@@ -58,8 +58,20 @@
   // four SGPRs) and every wait also waits for them (cswait: vmcnt(0), exact for the same reason) — a phase is ~340 VALU cycles
   // of this wave alone, so neither wait stalls in the steady state.  The records' request comes LAST: the hand-off tail begins
   // behind the last s_load_dwordx16 of the program (tools/check_k1_handoff.py).
-  auto run = [&](auto ff) {  // the source stream, once per pair rule (pair_batch)
-    constexpr bool FF = decltype(ff)::value;
+  // The far certificate (common.hpp: k1_block_is_far), once per block and wave, f64 launches on the sparse rule only: this
+  // wave's targets against the box of the block's source chunk.  Wave-uniform; the waves of a target group decide alike.
+  [[maybe_unused]] bool cfar = false;
+  if constexpr (!K1_SOFT && CST && RULE == 0) {
+    if (ffar && box != nullptr) {
+      cfar = k1_block_is_far<T, D, R>(xi, (const T __attribute__((address_space(4)))*)(box + size_t(blockIdx.y) * (2 * D)));
+#ifdef NBODY_EXPERIMENTS
+      if (cfar && jpart == 0 && lane == 0)  // certified (target group, chunk) blocks, in the header of the box buffer
+        atomicAdd(reinterpret_cast<unsigned long long*>(const_cast<T*>(box)) - kBoxHeaderBytes / 8, 1ull);
+#endif
+    }
+  }
+  auto run = [&](auto ff) {  // the source stream, once per pair rule (pair_batch: 0 dense, 1 sparse) and once certified far (2)
+    constexpr int FF = int(decltype(ff)::value);
     sgpr16 A, B;
     [[maybe_unused]] cst_regs CA, CB;
     auto request = [&](sgpr16& S, cst_regs& C, uint32_t k) {
@@ -75,7 +87,8 @@
       src_cst<T> kc[U];
       if constexpr (CST) cst_unpack(C, kc);
       if constexpr (K1_SOFT) pair_batch_soft<T, D, R, U, true>(acc, xi, b.r, kc, pc, e2);
-      else pair_batch<T, D, R, U, FF>(acc, xi, b.r, kc, pc);
+      else if constexpr (FF == 2) pair_batch_far<T, D, R, U>(acc, xi, b.r, kc);
+      else pair_batch<T, D, R, U, FF != 0>(acc, xi, b.r, kc, pc);
     };
     request(A, CA, 0);
     for (uint32_t k = 0; k < nsteps; k += 2 * U) {
@@ -91,8 +104,12 @@
   if constexpr (K1_SOFT) run(std::false_type{});           // one pair form: no rule to choose
   else if constexpr (RULE == 1) run(std::false_type{});  // (experiments: one rule per instantiation, forced from the host)
   else if constexpr (RULE == 2) run(std::true_type{});
-  else if (ffar) run(std::true_type{});  // two copies of the loop: inside ONE loop hipcc hoists the rules' common head above the branch
-  else run(std::false_type{});
+  else if (ffar) {  // two copies of the loop: inside ONE loop hipcc hoists the rules' common head above the branch
+    if constexpr (CST) {
+      if (cfar) run(std::integral_constant<int, 2>{});  // and a third: no pair of this block needs the near/far test
+      else run(std::true_type{});
+    } else run(std::true_type{});
+  } else run(std::false_type{});
   if constexpr (JS > 1) {
     if (jpart > 0) {
 #pragma unroll
