@@ -86,7 +86,9 @@ typedef struct nbody_state {
  *      (individual) time steps for it, nbody_hermite_block_start, nbody_hermite_block_step, nbody_hermite_block_advance,
  *      nbody_hermite_block_read.  Additive, same version: block (individual) time steps for the octree leapfrog,
  *      nbody_octree_block_create, nbody_octree_block_create_on, nbody_octree_block_destroy, nbody_octree_block_start,
- *      nbody_octree_block_step, nbody_octree_block_advance, nbody_octree_block_read. */
+ *      nbody_octree_block_step, nbody_octree_block_advance, nbody_octree_block_read.  Additive, same version: the sixth-order
+ *      Hermite integrator for all-pairs, nbody_hermite6_create, nbody_hermite6_create_on, nbody_hermite6_destroy,
+ *      nbody_hermite6_start, nbody_hermite6_step, nbody_hermite6_read. */
 #define NBODY_HIP_ABI_VERSION 2004
 int nbody_abi_version(void);
 
@@ -395,6 +397,50 @@ int  nbody_hermite_block_advance(nbody_hermite* h, const nbody_state* s, double 
 /* Blocking.  what: 0 levels int32[n] | 1 tau_i uint32[n] | 2 the active list of the last block step, uint32[n_active] ascending.
  * bytes must match (NBODY_ERR_ARG). */
 int  nbody_hermite_block_read(nbody_hermite* h, int what, void* host_out, size_t bytes, void* stream);
+
+/* ---- sixth-order Hermite integrator for all-pairs (no reference counterpart) ------------------------------------------------------
+ * The predictor-corrector of Nitadori & Makino (2008) with a fixed step and Plummer softening: one evaluation of the acceleration,
+ * its first time derivative (the jerk) AND its second (the snap) per step, in one pair loop.  With e2 = fl_T(T(eps) * T(eps)),
+ * d = x_j - x_i, u = v_j - v_i, b = a_j - a_i, q = |d|^2 + e2, w = m_j q^(-3/2), alpha = (d.u) / q, gamma = (|u|^2 + d.b) / q:
+ *   a_i = c * sum_j w d,   j_i = c * sum_j w (u - 3 alpha d),   s_i = c * sum_j w (b - 6 alpha u + (15 alpha^2 - 3 gamma) d)
+ * The self pair, and coincident bodies at equal velocity and acceleration, add 0 because d = u = b = 0: no branch, no index test.
+ * w is the softened K1's weight, operation for operation; 1 / q comes from the same reciprocal square root (no divide, no second
+ * transcendental).  eps obeys the rules of the softening section above; eps = 0 is NOT supported (NBODY_ERR_ARG), as in the
+ * fourth-order integrator.  One step of h = T(dt) from (x, v, a0, j0, s0, k0), k0 the crackle kept from the previous step:
+ *   predict   xp = x + h v + h^2/2 a0 + h^3/6 j0 + h^4/24 s0 + h^5/120 k0
+ *             vp = v + h a0 + h^2/2 j0 + h^3/6 s0 + h^4/24 k0,      ap = a0 + h j0 + h^2/2 s0 + h^3/6 k0
+ *   evaluate  (a1, j1, s1) at (xp, vp, ap), all bodies
+ *   correct   v1 = v + h/2 (a0 + a1) + h^2/10 (j0 - j1) + h^3/120 (s0 + s1)
+ *             x1 = x + h/2 (v + v1)  + h^2/10 (a0 - a1) + h^3/120 (j0 + j1)
+ *   crackle   k1 = (60 (a1 - a0) - h (24 j0 + 36 j1) + h^2 (9 s1 - 3 s0)) / h^3     (1 / h^3 is computed once per call, as T)
+ *   then      x <- x1, v <- v1, a <- a1, jerk <- j1, snap <- s1, crackle <- k1                                           (P(EC)^1)
+ * The crackle term of the predictor is what makes the scheme sixth order.  The start evaluates twice, because the snap needs the
+ * accelerations of all bodies: the first pass, with ap = 0, keeps a alone; the second, at (x, v, a), gives a (the same bits: the sum
+ * of a does not read ap), the jerk and the snap; the crackle starts as 0, so the first step is one order lower, once.
+ * The handle owns the jerk, the snap, the crackle, the packed predicted state and the partial sums; everything is allocated by
+ * create, so start and step allocate nothing and may be recorded into a step graph.  A body's sums are added in an order that
+ * follows from sz alone (no atomics, no waiting between blocks): two runs, an eager step and a replayed recorded one give the same
+ * bits.  s->ao is neither read nor written.
+ *  - Whole system only: first = 0, count = sz, else NBODY_ERR_ARG.
+ *  - Argument errors are found before the device is touched, in the order of nbody_hermite_step: s NULL; the state's dtype, dim,
+ *    window, tuning; eps (the message names the softening); h NULL; h made for another dtype, dim or n (all NBODY_ERR_ARG).
+ *  - nbody_hermite6_step before nbody_hermite6_start on that handle: NBODY_ERR_STATE.  A handle used with a stream of another
+ *    device: NBODY_ERR_ARG.  Every entry switches to the handle's device and restores the caller's.
+ *  - nbody_hermite6_read and nbody_hermite6_create(_on) between nbody_graph_begin and nbody_graph_end: NBODY_ERR_STATE.
+ * Block time steps for this scheme are not provided (nbody_hermite_block_* steps the fourth-order scheme). */
+typedef struct nbody_hermite6 nbody_hermite6;
+int  nbody_hermite6_create(nbody_hermite6** out, int dtype, int dim, uint32_t n);                /* on the current device */
+int  nbody_hermite6_create_on(nbody_hermite6** out, int dtype, int dim, uint32_t n, int device); /* device < 0: the current one */
+void nbody_hermite6_destroy(nbody_hermite6* h);                                                  /* NULL: no-op */
+/* a = s->a and the handle's jerk and snap at (s->x, s->v), crackle = 0: starts a run, or restarts it after an upload.  Two
+ * evaluations.  Asynchronous, recordable. */
+int  nbody_hermite6_start(nbody_hermite6* h, const nbody_state* s, double eps, void* stream);
+/* One step as above: reads s->x, s->v, s->a, the jerk, the snap and the crackle, rewrites them.  Asynchronous, recordable. */
+int  nbody_hermite6_step(nbody_hermite6* h, const nbody_state* s, double eps, void* stream);
+/* Blocking.  what: 0 jerk | 1 snap | 2 crackle | 3 predicted x | 4 predicted v | 5 predicted a of the last step (after start: x, v
+ * and a as they were evaluated), each T[n][D].  bytes must be n * D * sizeof(T) (NBODY_ERR_ARG); NBODY_ERR_STATE before the first
+ * start. */
+int  nbody_hermite6_read(nbody_hermite6* h, int what, void* host_out, size_t bytes, void* stream);
 
 /* ---- block (individual) time steps for the octree leapfrog (no reference counterpart) ----------------------------------------
  * A per-body velocity-Verlet (kick-drift-kick) step on the level grid of the Hermite block steps above, with the force from the

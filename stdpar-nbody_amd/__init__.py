@@ -65,6 +65,8 @@ ABI_SYMBOLS = [
     "nbody_hermite_block_start", "nbody_hermite_block_step", "nbody_hermite_block_advance", "nbody_hermite_block_read",
     "nbody_octree_block_create", "nbody_octree_block_create_on", "nbody_octree_block_destroy", "nbody_octree_block_start",
     "nbody_octree_block_step", "nbody_octree_block_advance", "nbody_octree_block_read",
+    "nbody_hermite6_create", "nbody_hermite6_create_on", "nbody_hermite6_destroy", "nbody_hermite6_start", "nbody_hermite6_step",
+    "nbody_hermite6_read",
 ]
 ABI_MAJOR = 2
 COMM_ID_BYTES = 128
@@ -106,6 +108,11 @@ def lib():
         L.nbody_hermite_block_step.argtypes = [vp, vp, d, d, vp, vp, vp]
         L.nbody_hermite_block_advance.argtypes = [vp, vp, d, d, vp, vp, vp]
         L.nbody_hermite_block_read.argtypes = [vp, C.c_int, vp, C.c_size_t, vp]
+        L.nbody_hermite6_destroy.restype = None
+        L.nbody_hermite6_destroy.argtypes = [vp]
+        L.nbody_hermite6_start.argtypes = [vp, vp, d, vp]
+        L.nbody_hermite6_step.argtypes = [vp, vp, d, vp]
+        L.nbody_hermite6_read.argtypes = [vp, C.c_int, vp, C.c_size_t, vp]
         L.nbody_octree_block_destroy.restype = None
         L.nbody_octree_block_destroy.argtypes = [vp]
         L.nbody_octree_block_start.argtypes = [vp, vp, vp, d, d, d, C.c_int, vp]
@@ -494,6 +501,44 @@ class Hermite:
         return out
 
 
+class Hermite6:
+    """Sixth-order Hermite integrator for all-pairs (nbody_hermite6_*): owns the jerk, the snap, the crackle, the packed predicted
+    state and the partial sums."""
+
+    def __init__(self, dtype, dim, n, device=-1):
+        """device: where the handle's buffers live (-1: the calling thread's current device)."""
+        self.h = C.c_void_p()
+        self.dtype, self.dim, self.n = dtype, dim, n
+        _check(lib().nbody_hermite6_create_on(C.byref(self.h), dtype, dim, C.c_uint32(n), device))
+
+    def close(self):
+        if self.h:
+            lib().nbody_hermite6_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def start(self, st, eps, stream=None):
+        """a = st.a, the jerk and the snap at (st.x, st.v), crackle = 0, Plummer softening eps > 0: starts (or restarts) a run."""
+        _check(lib().nbody_hermite6_start(self.h, C.byref(st), eps, stream))
+
+    def step(self, st, eps, stream=None):
+        """One predictor-corrector step of st.dt: rewrites st.x, st.v, st.a, the jerk, the snap and the crackle; st.ao is untouched.
+        Recordable."""
+        _check(lib().nbody_hermite6_step(self.h, C.byref(st), eps, stream))
+
+    def read(self, what, stream=None):
+        """0 the jerk, 1 the snap, 2 the crackle, 3 / 4 / 5 the predicted positions / velocities / accelerations of the last step:
+        (n, dim) of T (blocking)."""
+        out = np.zeros((self.n, self.dim), np_dtype(self.dtype))
+        _check(lib().nbody_hermite6_read(self.h, what, _p(out), out.nbytes, stream))
+        return out
+
+
 class OctreeBlock:
     """Block (individual) time steps for the octree leapfrog (nbody_octree_block_*): owns the levels, tau, the active lists, the
     predicted positions and the scratch of the active set's forces; the tree is the caller's Octree."""
@@ -554,6 +599,7 @@ class DeviceSystem:
         self._octree = None
         self._hermite = None
         self._octree_block = None
+        self._hermite6 = None
 
     @classmethod
     def from_host(cls, hs, device=0):
@@ -574,6 +620,9 @@ class DeviceSystem:
         if self._octree_block is not None:
             self._octree_block.close()
             self._octree_block = None
+        if self._hermite6 is not None:
+            self._hermite6.close()
+            self._hermite6 = None
         if self.h:
             lib().nbody_destroy(self.h)
             self.h = C.c_void_p()
@@ -675,6 +724,27 @@ class DeviceSystem:
     def hermite_block_active(self, n_active):
         """The active list of the last block step (ascending body indices); n_active as hermite_block_step returned it."""
         return self.hermite.block_read(2, self.stream, n_active)
+
+    # sixth-order Hermite (no reference counterpart)
+    @property
+    def hermite6(self):
+        if self._hermite6 is None:
+            self._hermite6 = Hermite6(self.dtype, self.dim, self.n, self.device)
+        return self._hermite6
+
+    def hermite6_start(self, eps):
+        """Acceleration, jerk and snap of the state as it is, crackle = 0 (nbody_hermite6_start): before the first hermite6_step and
+        after an upload."""
+        self.hermite6.start(self.state(), eps, self.stream)
+
+    def hermite6_step(self, eps):
+        """One sixth-order Hermite step of dt (nbody_hermite6_step); a StepGraph may record it (after hermite6_start has been called)."""
+        self.hermite6.step(self.state(), eps, self.stream)
+
+    def hermite6_read(self, what):
+        """0 the jerk, 1 the snap, 2 the crackle, 3 / 4 / 5 the predicted x / v / a of the last hermite6_start / hermite6_step,
+        (n, dim) of T (blocking)."""
+        return self.hermite6.read(what, self.stream)
 
     # block time steps for the octree leapfrog (no reference counterpart)
     @property

@@ -46,6 +46,7 @@ class Device {
   }
   ~Device() {
     if (hermite_) nbody_hermite_destroy(hermite_);
+    if (hermite6_) nbody_hermite6_destroy(hermite6_);
     if (octree_block_) nbody_octree_block_destroy(octree_block_);
     if (octree_) nbody_octree_destroy(octree_);
     if (tree_) nbody_bvh_destroy(tree_);
@@ -111,6 +112,13 @@ class Device {
     backend_check(nbody_hermite_force_jerk(hermite_, &view_[0], eps, stream()), "nbody_hermite_force_jerk");
   }
   void hermite_step(double eps) { backend_check(nbody_hermite_step(hermite_, &view_[0], eps, stream()), "nbody_hermite_step"); }
+  // --hermite-order 6: acceleration, jerk and snap of the uploaded state once (two evaluations), then one call per step
+  void hermite6_start(double eps) {
+    single("--hermite-order 6");
+    if (!hermite6_) backend_check(nbody_hermite6_create_on(&hermite6_, dtype, D, host_.n, 0), "nbody_hermite6_create_on");
+    backend_check(nbody_hermite6_start(hermite6_, &view_[0], eps, stream()), "nbody_hermite6_start");
+  }
+  void hermite6_step(double eps) { backend_check(nbody_hermite6_step(hermite6_, &view_[0], eps, stream()), "nbody_hermite6_step"); }
   // --hermite-eta ETA: block time steps; one call advances the system by dt (as many block steps as its levels ask for)
   void hermite_block_start(double eps, double eta_start, int max_level) {
     single("--hermite-eta");
@@ -229,6 +237,7 @@ class Device {
   nbody_bvh* tree_ = nullptr;
   nbody_octree* octree_ = nullptr;
   nbody_hermite* hermite_ = nullptr;
+  nbody_hermite6* hermite6_ = nullptr;
   nbody_octree_block* octree_block_ = nullptr;
 };
 

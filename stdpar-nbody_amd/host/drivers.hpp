@@ -55,15 +55,19 @@ void run_all_pairs(System<T, D>& sys, Device<T, D>& dev, Options o, char const* 
   // --hermite-eta: block time steps.  One step of the run is one advance of dt; it reads the size of every active set back, so it
   // is not recorded: warm-up and timed steps are plain calls (eta_start = ETA / 2 for the first levels, which have no a2, a3 yet)
   bool const block = hermite && o.hermite_eta > 0.0;
+  // --hermite-order 6: the sixth-order scheme (force + jerk + snap), driven like the fixed-step fourth-order run
+  bool const sixth = hermite && o.hermite_order == 6;
   if (block) {
     dev.hermite_block_start(o.softening, 0.5 * o.hermite_eta, o.hermite_levels);
     dev.sync();
   } else if (hermite) {
-    dev.hermite_start(o.softening);
+    if (sixth) dev.hermite6_start(o.softening);
+    else dev.hermite_start(o.softening);
     dev.sync();
   }
   auto hermite_one = [&] {
     if (block) dev.hermite_block_advance(o.softening, o.hermite_eta);
+    else if (sixth) dev.hermite6_step(o.softening);
     else dev.hermite_step(o.softening);
   };
   if (block && !o.csv_detailed) {
@@ -82,7 +86,7 @@ void run_all_pairs(System<T, D>& sys, Device<T, D>& dev, Options o, char const* 
       }
     });
   } else if (hermite) {
-    nbody_graph* g = dev.record([&] { dev.hermite_step(o.softening); });
+    nbody_graph* g = dev.record(hermite_one);
     for (std::size_t step = 0; step < o.warmup_steps; ++step) dev.replay(g);
     dev.sync();
     t_total = timed([&] {

@@ -50,6 +50,10 @@ struct Options {
   double hermite_eta = 0.0;  // 0: fixed step
   int hermite_levels = 12;
   bool hermite_levels_given = false;
+  // not in the reference either (nor in --help): --hermite-order 4|6 (with --integrator hermite only, default 4).  6: the sixth-order
+  // scheme with force + jerk + snap (nbody_hermite6_*), fixed step only (no --hermite-eta)
+  int hermite_order = 4;
+  bool hermite_order_given = false;
   // not in the reference either (nor in --help): --block-eta ETA (octree with --softening EPS > 0 only, ETA > 0) runs the octree
   // leapfrog with block time steps (nbody_octree_block_*): every step of the run advances the system by dt in as many block steps as
   // the bodies' levels ask for, each body on the power-of-two step its acceleration allows; --block-levels L (0 .. 20, default 12):
@@ -156,6 +160,14 @@ inline Options parse_options(std::vector<std::string> const& argv) {
       }
       o.hermite_levels       = int(v);
       o.hermite_levels_given = true;
+    } else if (f == "--hermite-order") {
+      auto const& r = value();
+      if (r != "4" && r != "6") {
+        std::cerr << "--hermite-order needs 4 or 6, got \"" << r << "\"." << std::endl;
+        std::exit(EXIT_FAILURE);
+      }
+      o.hermite_order       = r == "6" ? 6 : 4;
+      o.hermite_order_given = true;
     } else if (f == "--block-eta") {
       auto const& e = value();
       char* end     = nullptr;
@@ -248,6 +260,14 @@ inline Options parse_options(std::vector<std::string> const& argv) {
   }
   if (o.hermite_levels_given && !(o.hermite_eta > 0.0)) {
     std::cerr << "--hermite-levels needs --hermite-eta ETA." << std::endl;
+    std::exit(EXIT_FAILURE);
+  }
+  if (o.hermite_order_given && o.integrator != Integrator::Hermite) {
+    std::cerr << "--hermite-order needs --integrator hermite." << std::endl;
+    std::exit(EXIT_FAILURE);
+  }
+  if (o.hermite_order == 6 && o.hermite_eta > 0.0) {
+    std::cerr << "--hermite-order 6 takes a fixed step: it cannot be combined with --hermite-eta." << std::endl;
     std::exit(EXIT_FAILURE);
   }
   if (o.softening > 0.0 && (o.algorithm == Algorithm::Bvh || o.algorithm == Algorithm::AllPairsCollapsed)) {
