@@ -9,7 +9,7 @@
 //              compact    the active indices in ascending body order: the strip's offset + the counts of the earlier rows and
 //                         waves of the strip + the lane's rank in its wave's ballot.  No atomics: a slot follows from the levels alone;
 //   predict    ALL bodies to tau_next, h_i = T(tau_next - tau_i) * tick, the packed record of hermite_predict_kernel;
-//   force+jerk the active targets, gathered through the list, against all N records: the pair loop of hermite_pair_body.inc as it is,
+//   force+jerk the active targets, gathered through the list, against all N records: hermite_tile_sum (hermite_tile.hpp) as it is,
 //              launched in the shape of hermite_block_plan_for(sz, n_act);
 //   reduce     only where the active set is cut into more than kSerialChunks chunks (fewer than 2048 active bodies of a large system):
 //              one wave per (slot, component) adds the chunks' sums, each lane a run of consecutive chunks in chunk order, the
@@ -29,7 +29,7 @@ enum { kSchedMin = 0, kSchedCount = 1, kSchedNext = 2, kSchedWords = 4 };
 
 // Launch shape of the active-set force + jerk, from (sz, n_act) alone.  hermite_plan_for's rule with the blocks counted over the
 // ACTIVE targets and no cap of 64 on the chunks: as n_act shrinks the tiles are cut finer over grid.y, down to one tile per chunk,
-// so that about 2048 blocks are in flight whatever n_act is.  With n_act == sz it IS hermite_plan_for(sz) (its cap of 64 binds
+// so that about 2048 blocks are in flight whatever n_act is.  With n_act == sz it IS hermite_plan_for(sz, 1) (its cap of 64 binds
 // below 2048 targets only, where a system has fewer than 8 tiles).
 inline hermite_plan hermite_block_plan_for(uint32_t sz, uint32_t n_act) {
   hermite_plan p;
@@ -218,17 +218,17 @@ __global__ __launch_bounds__(kHBlock) void hermite_block_predict_kernel(const T*
   if (i >= padded) return;
   hsrc_rec<T> r;
 #pragma unroll
-  for (int k = 0; k < 3; ++k) r.p[k] = r.v[k] = T(0);
-  r.m = r.pad = T(0);
+  for (int k = 0; k < 4; ++k) r.g[kRecP][k] = r.g[kRecV][k] = T(0);
   if (i < n) {
     const T dt = T(sched[kSchedNext] - tau[i]) * tick;
-    r.m        = m[i];
+    r.g[kRecP][kRecM] = m[i];
 #pragma unroll
     for (int k = 0; k < D; ++k) {
       const uint64_t e = uint64_t(i) * D + k;
       const T a0 = a[e], j0 = jerk[e], v0 = v[e];
-      r.p[k] = __builtin_elementwise_fma(dt, __builtin_elementwise_fma(dt * T(0.5), __builtin_elementwise_fma(dt * T(1.0 / 3.0), j0, a0), v0), x[e]);
-      r.v[k] = __builtin_elementwise_fma(dt, __builtin_elementwise_fma(dt * T(0.5), j0, a0), v0);
+      r.g[kRecP][k] =
+          __builtin_elementwise_fma(dt, __builtin_elementwise_fma(dt * T(0.5), __builtin_elementwise_fma(dt * T(1.0 / 3.0), j0, a0), v0), x[e]);
+      r.g[kRecV][k] = __builtin_elementwise_fma(dt, __builtin_elementwise_fma(dt * T(0.5), j0, a0), v0);
     }
   }
   recs[i] = r;
@@ -240,10 +240,7 @@ template <typename T, int D, int R>
 __global__ __launch_bounds__(kHBlock) void hermite_block_active_kernel(const hsrc_rec<T>* __restrict__ recs, T* __restrict__ part, T e2,
                                                                        uint32_t n_act, uint32_t ntiles, uint32_t tiles_per_chunk,
                                                                        const uint32_t* __restrict__ act) {
-  const uint32_t n = n_act;
-#define HFJ_GATHER 1
-#include "hermite_pair_body.inc"
-#undef HFJ_GATHER
+  hermite_tile_sum<T, D, R, 2, true>(reinterpret_cast<const T*>(recs), part, e2, n_act, ntiles, tiles_per_chunk, act);
 }
 
 // ---- chunk sums of a small active set ----------------------------------------------------------------------------------------------

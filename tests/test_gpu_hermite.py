@@ -1,7 +1,7 @@
 """GPU: the fourth-order Hermite integrator for all-pairs (nbody_hermite_*) against a NumPy Hermite written here (the reference has no
 Hermite, so there are no fixtures): np.longdouble for single evaluations, float64 for runs.
 
-Launch-shape boundaries of csrc/hermite.hip crossed by the sizes below: the LDS tile of 256 records (255 / 256 / 257: one tile, then two
+Launch-shape boundaries of the fourth order (hermite_plan_for(sz, 1) of csrc/hermite_tile.hpp) crossed by the sizes below: the LDS tile of 256 records (255 / 256 / 257: one tile, then two
 tiles and two chunks), two targets per lane from 65536 bodies on (65535 / 65536 / 65537), one chunk from 2048 blocks of 128 targets on
 (262016: two chunks, 262017: one).
 

@@ -2,7 +2,7 @@
 (ref_ajs, ref_step6, ref_run6; the reference has no Hermite, so there are no fixtures): np.longdouble for single evaluations, float64 for
 runs.  Conventions (maxrel, e2_of, random_system, cluster, TOL) are those of tests/test_gpu_hermite.py, restated.
 
-Launch-shape boundaries of csrc/hermite6.hip (hermite6_plan_for), each with a size on either side: one LDS tile of 256 records and one
+Launch-shape boundaries of the sixth order (hermite_plan_for(sz, 2) of csrc/hermite_tile.hpp), each with a size on either side: one LDS tile of 256 records and one
 chunk | two tiles, two chunks (256 / 257); one tile per chunk | several (5888 / 5889); one target per lane | two (65535 / 65536, and
 65537: a ragged last tile in that regime).  Inside a regime the chunk count varies with the size, but the code path does not (a loop
 over the chunk's tiles, a ragged last chunk: 4097, 5889 and 65537 have one), and the plan never goes back to one chunk.
