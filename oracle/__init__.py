@@ -117,8 +117,31 @@ def calc_energies(s):
     return ke[0], pe[0]
 
 
+def all_pairs_force_wide(s, targets=None):
+    """The all-pairs force of the T arrays of `s` with every operation in a wider type (double for float, long double for double)
+    and the reference's eps(T) kept: a_i = c sum_{j != i} m_j d / (r2 sqrt(r2) + eps(T)).  Returns (a, scale) as float64 for the
+    bodies in `targets` (an index array; None = all): a[len(targets)][D] and scale_i = c sum_j |m_j| r / (r^3 + eps(T)), the sum
+    of the magnitudes of target i's terms."""
+    t = np.arange(s.n, dtype=np.uint32) if targets is None else np.ascontiguousarray(targets, dtype=np.uint32)
+    assert t.ndim == 1 and (t.size == 0 or int(t.max()) < s.n)
+    a, scale = np.zeros((t.size, s.dim), np.float64), np.zeros(t.size, np.float64)
+    r = lib().oracle_all_pairs_force_wide(s.dtype, s.dim, _p(s.m), _p(s.x), C.c_double(s.c), C.c_uint32(s.n), _p(t),
+                                          C.c_uint32(t.size), _p(a), _p(scale))
+    assert r == 0
+    return a, scale
+
+
+def potential_wide(s):
+    """The potential energy with the terms formed wide as well: -c/2 sum_i sum_{j != i} m_i m_j / (sqrt(r2) + eps(T)) on the T
+    arrays of `s`, self pair excluded by index, as float64."""
+    pe = C.c_double()
+    r = lib().oracle_potential_wide(s.dtype, s.dim, _p(s.m), _p(s.x), C.c_double(s.c), C.c_uint32(s.n), C.byref(pe))
+    assert r == 0
+    return pe.value
+
+
 def calc_energies_wide(s):
-    """calc_energies with the same terms (formed in T) summed in double: the yardstick for float systems."""
+    """calc_energies with the same terms (formed in T) summed in long double: the yardstick for float systems."""
     ke, pe = C.c_double(), C.c_double()
     r = lib().oracle_calc_energies_wide(s.dtype, s.dim, _p(s.m), _p(s.x), _p(s.v), C.c_double(s.c), C.c_uint32(s.n), C.byref(ke),
                                         C.byref(pe))

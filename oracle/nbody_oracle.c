@@ -170,6 +170,23 @@ int oracle_calc_energies_wide(int dtype, int dim, const void* m, const void* x, 
   return 0;
 }
 
+int oracle_all_pairs_force_wide(int dtype, int dim, const void* m, const void* x, double c, uint32_t sz, const uint32_t* targets,
+                                uint32_t nt, double* a, double* scale) {
+  for (uint32_t t = 0; t < nt; ++t)
+    if (targets[t] >= sz) return -2;
+#define CALL(TT, S) all_pairs_force_wide_##S((const TT*)m, (const TT*)x, (TT)c, sz, targets, nt, a, scale)
+  DISPATCH(dtype, dim, CALL);
+#undef CALL
+  return 0;
+}
+
+int oracle_potential_wide(int dtype, int dim, const void* m, const void* x, double c, uint32_t sz, double* pe) {
+#define CALL(TT, S) potential_wide_##S((const TT*)m, (const TT*)x, (TT)c, sz, pe)
+  DISPATCH(dtype, dim, CALL);
+#undef CALL
+  return 0;
+}
+
 int oracle_bounding_box(int dtype, int dim, const void* x, uint32_t sz, void* xmin, void* xmax) {
 #define CALL(TT, S) bounding_box_##S((const TT*)x, sz, (TT*)xmin, (TT*)xmax)
   DISPATCH(dtype, dim, CALL);

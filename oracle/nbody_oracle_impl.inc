@@ -24,7 +24,13 @@
   #define T_SIN sinf
   #define T_COS cosf
   #define T_ACOS acosf
+  #define W double /* the wider type of the *_wide references below */
+  #define W_SQRT sqrt
+  #define W_FABS fabs
 #else
+  #define W long double
+  #define W_SQRT sqrtl
+  #define W_FABS fabsl
   #define T_EPS DBL_EPSILON
   #define T_POW pow
   #define T_SQRT sqrt
@@ -146,28 +152,80 @@ static void FN(calc_energies)(const T* m, const T* x, const T* v, T c, uint32_t 
   *pe_out = -(T)0.5 * c * pe;
 }
 
-/* system.h:62-79 with every term formed exactly as above (in T) but both sums carried in double: the yardstick for a float
+/* system.h:62-79 with every term formed exactly as above (in T) but both sums carried in long double: the yardstick for a float
  * system, whose single float accumulator (what the serial backend produces, calc_energies above) drifts by itself — 3e-5 over
- * 3.6e7 terms — while a tree-shaped sum of the same terms does not. */
+ * 3.6e7 terms — while a tree-shaped sum of the same terms does not; in double the sums add nothing to the terms' own rounding. */
 static void FN(calc_energies_wide)(const T* m, const T* x, const T* v, T c, uint32_t sz, double* ke_out, double* pe_out) {
-  double ke = 0.;
+  long double ke = 0.L;
   for (uint32_t i = 0; i < sz; ++i) {
     T n2 = (T)0.;
     for (int k = 0; k < D; ++k) n2 += v[(uint64_t)i * D + k] * v[(uint64_t)i * D + k];
-    ke += (double)(m[i] * n2);
+    ke += (long double)(m[i] * n2);
   }
-  double pe = 0.;
+  long double pe = 0.L;
 #pragma omp parallel for schedule(static) reduction(+ : pe)
   for (int64_t i_ = 0; i_ < (int64_t)sz; ++i_) {
-    uint32_t i   = (uint32_t)i_;
-    double total = 0.;
-    T mi         = m[i];
+    uint32_t i        = (uint32_t)i_;
+    long double total = 0.L;
+    T mi              = m[i];
     for (uint32_t j = 0; j < sz; ++j)
-      if (j != i) total += (double)(mi * m[j] / FN(dist)(&x[(uint64_t)i * D], &x[(uint64_t)j * D]));
+      if (j != i) total += (long double)(mi * m[j] / FN(dist)(&x[(uint64_t)i * D], &x[(uint64_t)j * D]));
     pe += total;
   }
-  *ke_out = 0.5 * ke;
-  *pe_out = -0.5 * (double)c * pe;
+  *ke_out = (double)(0.5L * ke);
+  *pe_out = (double)(-0.5L * (long double)c * pe);
+}
+
+/* The all-pairs force of include/nbody_hip.h restated with every operation in the wider type W (double for T = float, long double
+ * for T = double) on the T inputs, the reference's eps(T) kept:
+ *   a_i = c * sum_{j != i} m_j d / (r2 * sqrt(r2) + eps(T)),  d = x_j - x_i,  r2 = |d|^2
+ * (a coincident pair adds d = 0, as src/all_pairs.h does), and beside it the sum of the terms' magnitudes
+ *   scale_i = c * sum_{j != i} |m_j| r / (r^3 + eps(T)),
+ * the yardstick a rounding error of target i is measured against.  targets[nt]: the bodies evaluated; outputs converted to double. */
+static void FN(all_pairs_force_wide)(const T* m, const T* x, T c, uint32_t sz, const uint32_t* targets, uint32_t nt, double* a_out,
+                                     double* scale_out) {
+#pragma omp parallel for schedule(dynamic, 16)
+  for (int64_t t = 0; t < (int64_t)nt; ++t) {
+    const uint32_t i = targets[t];
+    W xi[D], acc[D], sc = 0;
+    for (int k = 0; k < D; ++k) { xi[k] = (W)x[(uint64_t)i * D + k]; acc[k] = 0; }
+    for (uint32_t j = 0; j < sz; ++j) {
+      if (j == i) continue;
+      W d[D], r2 = 0;
+      for (int k = 0; k < D; ++k) {
+        d[k] = (W)x[(uint64_t)j * D + k] - xi[k];
+        r2 += d[k] * d[k];
+      }
+      const W r = W_SQRT(r2);
+      const W w = (W)m[j] / (r2 * r + (W)T_EPS);
+      for (int k = 0; k < D; ++k) acc[k] += w * d[k];
+      sc += W_FABS(w) * r;
+    }
+    for (int k = 0; k < D; ++k) a_out[(uint64_t)t * D + k] = (double)((W)c * acc[k]);
+    scale_out[t] = (double)(W_FABS((W)c) * sc);
+  }
+}
+
+/* The potential of include/nbody_hip.h with the terms formed in W as well: -c/2 sum_i sum_{j != i} m_i m_j / (sqrt(r2) + eps(T)),
+ * self pair excluded by index, summed in long double.  The term is symmetric in (i, j), so each unordered pair is formed once. */
+static void FN(potential_wide)(const T* m, const T* x, T c, uint32_t sz, double* pe_out) {
+  long double pe = 0.L;
+#pragma omp parallel for schedule(dynamic, 64) reduction(+ : pe)
+  for (int64_t i_ = 0; i_ < (int64_t)sz; ++i_) {
+    const uint32_t i = (uint32_t)i_;
+    W xi[D], total = 0;
+    for (int k = 0; k < D; ++k) xi[k] = (W)x[(uint64_t)i * D + k];
+    for (uint32_t j = i + 1; j < sz; ++j) {
+      W r2 = 0;
+      for (int k = 0; k < D; ++k) {
+        const W d = (W)x[(uint64_t)j * D + k] - xi[k];
+        r2 += d * d;
+      }
+      total += (W)m[j] / (W_SQRT(r2) + (W)T_EPS);
+    }
+    pe += (long double)((W)m[i] * total);
+  }
+  *pe_out = (double)(-(long double)c * pe);
 }
 
 /* bvh.h:17-22 + vec.h:382-405  bounding box: init = AABB of the origin (+-10 eps), each point padded
@@ -747,6 +805,9 @@ static void FN(model_plummer)(uint32_t n, T* m, T* x, T* v, double* dt, double* 
 #undef T_SIN
 #undef T_COS
 #undef T_ACOS
+#undef W
+#undef W_SQRT
+#undef W_FABS
 #undef FN
 #undef CAT
 #undef CAT_

@@ -5,6 +5,8 @@
 // streamed through the scalar cache into SGPRs two batches deep, the 512-record tile is cut into 8 slices (one per
 // wave of the block, combined through LDS in wave order) and the tile sequence into the same source chunks K1 uses
 // (grid.y; combined in chunk order by the reduction kernel), so the sum is deterministic.
+// In f32 a lane sums the 64 terms of a tile's slice by themselves and adds the tile sums up (potential_body.inc): one chain over a
+// chunk lets a single large term swallow the later ones below half its ulp (8.4e-6 of the potential at N = 65 537, galaxy).
 // Pair term  m_j / (s + eps),  s = sqrt(r2):
 //   far  (r2 >= 2^-48 in f64, 2^-20 in f32):  m_j * y * (1 - eps*y),  y = 1/s from the v_rsq seed polished to third
 //        order in f64 (y*(1 + e/2 + 3/8 e^2), e = 1 - r2*y^2), the 1-ulp v_rsq_f32 in f32; dropping (eps*y)^2 <= 2^-56

@@ -632,9 +632,15 @@ def test_sparse_system_pair_rules_with_planted_pairs(nb, oracle, dim):
         i, j = 101 + 977 * k, 101 + 977 * k + 4099 + 1033 * k   # another source tile, another slice, usually another chunk
         d = np.zeros(dim)
         d[k % dim] = gap
-        hs.x[i] = np.round(hs.x[i])          # exact coordinates: the planted r^2 is what it says
+        hs.x[i] = np.round(hs.x[i])          # exact coordinates ...
+        hs.x[i, k % dim] = 0                 # ... and 0 on the gap axis (|x| up to 1250 would round the ulp away): r^2 is what it says
         hs.x[j] = hs.x[i] + d
         planted += [i, j]
+    r2 = [float(((hs.x[j] - hs.x[i]) ** 2).sum()) for i, j in zip(planted[0::2], planted[1::2])]
+    # the squares of 2 + ulp and 2 - ulp are two steps above and two below 4; of 2^-8 - ulp, two below 2^-16 (the guarded form)
+    assert r2[0] == 4.0 and r2[1] == 4.0 + 2.0 ** -49 and r2[2] == 4.0 - 2.0 ** -50, r2[:3]
+    assert r2[1] <= np.nextafter(np.nextafter(4.0, 5.0), 5.0) and r2[2] >= np.nextafter(np.nextafter(4.0, 3.0), 3.0)
+    assert r2[5] == 2.0 ** -16 and r2[6] == 2.0 ** -16 - 2.0 ** -68 and r2[6] >= np.nextafter(np.nextafter(2.0 ** -16, 0.0), 0.0), r2[5:7]
     hs.x[300] = hs.x[29000]                  # coincident, distinct bodies
     hs.x[400] = 0
     hs.x[31000] = 0
@@ -683,6 +689,16 @@ def test_sparse_system_pair_rules_with_planted_pairs(nb, oracle, dim):
         w = dev.download().a[first:first + count]
         assert np.array_equal(w, a[first:first + count].astype(w.dtype)), (first, count)
     dev.close()
+    res = []                                 # at the explicit split 4 the LDS-tile form and the scalar stream: the same bits
+    for path in (1, 2):
+        d2 = nb.DeviceSystem.from_host(hs)
+        d2.configure_all_pairs(4, 0, path)
+        assert nb.all_pairs_pair_rule(d2.state(), d2.stream)[0] is True and "JS=4" in nb.describe_all_pairs(d2.state())
+        d2.all_pairs_force()
+        d2.sync()
+        res.append(d2.download().a.copy())
+        d2.close()
+    assert np.all(np.isfinite(res[0])) and np.array_equal(res[0], res[1])
 
 
 def test_config2_as_written_100_steps(nb, oracle):
