@@ -259,9 +259,11 @@ int nbody_octree_read_counters(nbody_octree* t, uint32_t* host_out, size_t bytes
 /* Quadrupole moments (no reference counterpart): the next term of the expansion of an accepted cell.  For a cell with centre of mass
  * p, Q = sum over its children c (child order, empty ones skipped) of Q_c + m_c (3 d d^T - |d|^2 I), d = p_c - p; a body leaf has
  * Q = 0.  NQ = 6 values in 3D (xx, xy, xz, yy, yz, zz), 3 in 2D (xx, xy, yy: the 3D tensor restricted to the plane, not traceless).
- * Both build forms give the same Q bit for bit.
- * compute_quadrupoles: after compute_tree; children before parents, on the stream.  The first call allocates the array (NQ values
- *   of T per node of the pool: 384 B per body in double 3D), so it must not be recorded: under stream capture it returns
+ * A child's stored p is its centre of mass rounded to T, so about p it keeps a dipole P_c of rounding size (a body's is 0); the sum
+ * also takes 3 (P_c d^T + d P_c^T) - 2 (P_c . d) I, which keeps Q that of the cell's bodies about p to rounding level wherever the
+ * cell lies (without it the error is eps(T) |p| / |d| of Q).  Both build forms give the same Q bit for bit.
+ * compute_quadrupoles: after compute_tree; children before parents, on the stream.  The first call allocates the array (NQ + dim
+ *   values of T per node of the pool: 576 B per body in double 3D), so it must not be recorded: under stream capture it returns
  *   NBODY_ERR_STATE.
  * compute_quadrupole_force: compute_force whose accepted cells also add -c (Q d) y^5 + (5/2) c (d^T Q d) d y^7, d = p - x[i],
  *   y = 1/|d|.  The opening tests, their order, the monopole terms and the counters are compute_force's bit for bit; honours the

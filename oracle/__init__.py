@@ -245,6 +245,55 @@ def octree_step_force(s, theta, want_counts=False):
     return counts, size.value, root_mass[0]
 
 
+KEY_LEVELS = {3: 21, 2: 32}  # the depth below which the product's cells are finer than its path keys (kMaxLevels)
+
+
+class WideWalk:
+    """What octree_walk_wide returns, all float64 (counts uint32), one row per target: a_mono, a_soft, a_quad, a_quad_deep (nt, D);
+    s_mono, s_soft, s_quad (nt,); scale_a_mono, scale_a_soft, scale_a_quad, scale_s_mono, scale_s_soft, scale_s_quad (nt,); counts
+    (nt, 2); root_q (the root's Q: xx, xy, xz, yy, yz, zz in 3D, xx, xy, yy in 2D).  a_soft, s_soft and their scales are None
+    without softening."""
+
+
+def octree_walk_wide(s, theta, softening=0.0, split_level=None, targets=None):
+    """The walk of octree_step_force — the same tree, node monopoles (T) and opening decisions, children in the same order — with
+    everything a body accumulates formed and summed in the wider type (double for float, long double for double), for the bodies in
+    `targets` (an index array; None = all).  With d = p - x_i, r = sqrt(|d|^2), eps(T) the reference's and e2 = fl_T(T(softening)^2):
+      a_mono = c sum m d / (r + eps(T))^3                 s_mono = sum m / (r + eps(T))
+      a_soft = c sum m d / (|d|^2 + e2)^(3/2)             s_soft = sum m / sqrt(|d|^2 + e2)            (softening > 0 only)
+      a_quad = a_mono + c sum_cells -(Q d) / r^5 + 5/2 (d^T Q d) d / r^7        s_quad = s_mono + sum_cells 1/2 (d^T Q d) / r^5
+    Q of a cell = sum over the bodies it holds of m (3 s s^T - |s|^2 I), s = x_b - p_cell, summed directly (no child-to-parent
+    shift); a_quad_deep = the share of accepted cells at depth >= split_level (default: the key depth of the dimension) in the
+    quadrupole term.  The s sums leave out the body's own leaf.  scale_* = the sum of the magnitudes of the terms of each sum (|c|
+    included for the forces).  counts = octree_step_force's {nodes examined, terms}."""
+    L = lib()
+    try:
+        fn = L.oracle_octree_walk_wide
+    except AttributeError:
+        raise RuntimeError(f"{LIB_PATH} has no oracle_octree_walk_wide: the library is older than oracle/nbody_oracle.c; "
+                           "rebuild it (make -C oracle oracle)") from None
+    t = np.arange(s.n, dtype=np.uint32) if targets is None else np.ascontiguousarray(targets, dtype=np.uint32)
+    assert t.ndim == 1 and (t.size == 0 or int(t.max()) < s.n)
+    split = KEY_LEVELS[s.dim] if split_level is None else int(split_level)
+    soft = softening > 0
+    nt, nq = t.size, 6 if s.dim == 3 else 3
+    vec = lambda: np.zeros((nt, s.dim), np.float64)
+    sca = lambda: np.zeros(nt, np.float64)
+    w = WideWalk()
+    w.a_mono, w.a_quad, w.a_quad_deep, w.s_mono, w.s_quad = vec(), vec(), vec(), sca(), sca()
+    w.a_soft, w.s_soft = (vec(), sca()) if soft else (None, None)
+    scales = np.zeros((nt, 6), np.float64)
+    w.counts, w.root_q = np.zeros((nt, 2), np.uint32), np.zeros(nq, np.float64)
+    r = fn(s.dtype, s.dim, _p(s.m), _p(s.x), C.c_double(s.c), C.c_uint32(s.n), C.c_double(theta), C.c_double(softening),
+           C.c_uint32(split), _p(t), C.c_uint32(nt), _p(w.a_mono), _p(w.a_soft), _p(w.a_quad), _p(w.a_quad_deep), _p(w.s_mono),
+           _p(w.s_soft), _p(w.s_quad), _p(scales), _p(w.counts), _p(w.root_q))
+    if r != 0:
+        raise RuntimeError(f"oracle_octree_walk_wide failed ({r})")
+    w.scale_a_mono, w.scale_a_quad, w.scale_s_mono, w.scale_s_quad = (scales[:, k].copy() for k in (0, 2, 3, 5))
+    w.scale_a_soft, w.scale_s_soft = (scales[:, 1].copy(), scales[:, 4].copy()) if soft else (None, None)
+    return w
+
+
 def executed_steps(steps, csv_detailed, warmup=10):
     """default mode runs max(steps, warmup) steps; --csv-detailed runs exactly `steps`
     (all_pairs.h:72-97, bvh.h:356-403, arguments.h:26)."""

@@ -69,6 +69,15 @@ static double oracle_uniform(oracle_rng* g, double a, double b) {
   return ret * (b - a) + a;
 }
 
+/* Outputs of the wide octree walk (octree_walk_wide in the .inc); any pointer may be NULL. */
+typedef struct {
+  double *a_mono, *a_soft, *a_quad, *a_quad_deep; /* nt * D */
+  double *s_mono, *s_soft, *s_quad;               /* nt */
+  double* scales;                                 /* nt * 6 */
+  uint32_t* counts;                               /* nt * 2 */
+  double* root_q;                                 /* 6 (3D) or 3 (2D) */
+} oracle_wide_out;
+
 /* ---- instantiate the algorithms ----------------------------------------------------------- */
 #define T float
 #define IS_F32 1
@@ -318,6 +327,24 @@ int oracle_octree_step_force(int dtype, int dim, const void* m, const void* x, v
                              uint32_t* counts, uint32_t* tree_size, void* root_mass) {
   int rc = 0;
 #define CALL(TT, S) rc = octree_step_force_##S((const TT*)m, (const TT*)x, (TT*)a, (TT)c, sz, (TT)theta, counts, tree_size, (TT*)root_mass)
+  DISPATCH(dtype, dim, CALL);
+#undef CALL
+  return rc < 0 ? -2 : 0;
+}
+
+/* The octree walk of oracle_octree_step_force (same tree, same T monopoles, same opening decisions) with everything a body
+ * accumulates formed and summed in the wider type, for the bodies in targets[nt]: see octree_walk_wide in the .inc.  Outputs are
+ * float64 and may be NULL.  Returns -2 on overflow, -3 on a target out of range. */
+int oracle_octree_walk_wide(int dtype, int dim, const void* m, const void* x, double c, uint32_t sz, double theta, double softening,
+                            uint32_t split_level, const uint32_t* targets, uint32_t nt, double* a_mono, double* a_soft,
+                            double* a_quad, double* a_quad_deep, double* s_mono, double* s_soft, double* s_quad, double* scales,
+                            uint32_t* counts, double* root_q) {
+  for (uint32_t t = 0; t < nt; ++t)
+    if (targets[t] >= sz) return -3;
+  const oracle_wide_out o = {a_mono, a_soft, a_quad, a_quad_deep, s_mono, s_soft, s_quad, scales, counts, root_q};
+  int rc = 0;
+#define CALL(TT, S) \
+  rc = octree_step_walk_wide_##S((const TT*)m, (const TT*)x, (TT)c, sz, (TT)theta, softening, split_level, targets, nt, &o)
   DISPATCH(dtype, dim, CALL);
 #undef CALL
   return rc < 0 ? -2 : 0;

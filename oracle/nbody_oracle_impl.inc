@@ -645,35 +645,220 @@ static void FN(octree_force)(const FN(octree_t) * t, const T* x, T* a, T c, uint
   }
 }
 
+/* clear, bounds, insert, multipoles (octree.h:321-325) into a freshly allocated tree; <0 on overflow (the tree is freed). */
+static int FN(octree_build)(FN(octree_t) * t, const T* m, const T* x, uint32_t sz) {
+  size_t cap = (size_t)OT_CHILDREN * sz;
+  if (cap < 1000) cap = 1000; /* system.h:30 max_tree_node_size */
+  t->capacity    = (uint32_t)cap;
+  t->first_child = (uint32_t*)malloc(sizeof(uint32_t) * cap);
+  t->parent      = (uint32_t*)malloc(sizeof(uint32_t) * (1 + cap / OT_CHILDREN));
+  t->m           = (T*)calloc(cap * (D + 1), sizeof(T));
+  for (size_t i = 0; i < cap; ++i) t->first_child[i] = OT_EMPTY;
+  for (size_t i = 0; i < 1 + cap / OT_CHILDREN; ++i) t->parent[i] = OT_EMPTY;
+  t->next_free = 1;
+  FN(octree_bounds)(t, x, sz);
+  int rc = 0;
+  for (uint32_t i = 0; i < sz && rc == 0; ++i) rc = FN(octree_insert)(t, m[i], &x[(uint64_t)i * D]);
+  if (rc == 0) FN(octree_multipoles)(t);
+  return rc;
+}
+
+static void FN(octree_free)(FN(octree_t) * t) {
+  free(t->first_child);
+  free(t->parent);
+  free(t->m);
+}
+
 /* One force phase of run_octree (octree.h:321-326): clear, bounds, insert, multipoles, force.
  * info[0] = tree size (next_free_child_group), root monopole mass written to *root_mass. Returns <0 on overflow. */
 static int FN(octree_step_force)(const T* m, const T* x, T* a, T c, uint32_t sz, T theta, uint32_t* counts, uint32_t* tree_size,
                                  T* root_mass) {
   FN(octree_t) t;
-  size_t cap = (size_t)OT_CHILDREN * sz;
-  if (cap < 1000) cap = 1000; /* system.h:30 max_tree_node_size */
-  t.capacity    = (uint32_t)cap;
-  t.first_child = (uint32_t*)malloc(sizeof(uint32_t) * cap);
-  t.parent      = (uint32_t*)malloc(sizeof(uint32_t) * (1 + cap / OT_CHILDREN));
-  t.m           = (T*)calloc(cap * (D + 1), sizeof(T));
-  for (size_t i = 0; i < cap; ++i) t.first_child[i] = OT_EMPTY;
-  for (size_t i = 0; i < 1 + cap / OT_CHILDREN; ++i) t.parent[i] = OT_EMPTY;
-  t.next_free = 1;
-  FN(octree_bounds)(&t, x, sz);
-  int rc = 0;
-  for (uint32_t i = 0; i < sz && rc == 0; ++i) rc = FN(octree_insert)(&t, m[i], &x[(uint64_t)i * D]);
+  int rc = FN(octree_build)(&t, m, x, sz);
   if (rc == 0) {
-    FN(octree_multipoles)(&t);
     FN(octree_force)(&t, x, a, c, sz, theta, counts);
     if (tree_size) *tree_size = t.next_free;
     if (root_mass) *root_mass = t.m[D];
   }
-  free(t.first_child);
-  free(t.parent);
-  free(t.m);
+  FN(octree_free)(&t);
   return rc;
 }
 
+/* ---- the wide octree walk: the yardstick of the softened, quadrupole and potential walks of include/nbody_hip.h ----------------
+ * The tree, its monopoles (T) and every opening decision are the ones above, operation for operation; what a body accumulates from
+ * the nodes it accepts is formed and summed in W.  Written here from the formulas of include/nbody_hip.h; no reference counterpart. */
+#define OT_NQ (D == 3 ? 6 : 3)
+
+/* Q of every cell straight from the bodies it holds: Q = sum_b m_b (3 s s^T - |s|^2 I), s = x_b - p_cell (p_cell the T monopole,
+ * widened), components xx, xy, (xz,) yy(, yz, zz).  Every body leaf walks up its parent chain and adds itself to each ancestor; no
+ * child-to-parent shift is used.  Body leaves and empty slots keep Q = 0. */
+static W* FN(octree_quadrupoles_wide)(const FN(octree_t) * t) {
+  W* quad = (W*)calloc((size_t)t->next_free * OT_NQ, sizeof(W));
+  for (uint32_t i = 1; i < t->next_free; ++i) {
+    if (t->first_child[i] != OT_BODY) continue;
+    const T* b = &t->m[(uint64_t)i * (D + 1)];
+    const W mb = (W)b[D];
+    uint32_t idx = i;
+    while (idx != 0) {
+      idx = t->parent[(idx - 1) / OT_CHILDREN];
+      const T* p = &t->m[(uint64_t)idx * (D + 1)];
+      W s[D], s2 = 0;
+      for (int k = 0; k < D; ++k) {
+        s[k] = (W)b[k] - (W)p[k];
+        s2 += s[k] * s[k];
+      }
+      W* q  = &quad[(uint64_t)idx * OT_NQ];
+      int e = 0;
+      for (int u = 0; u < D; ++u)
+        for (int v = u; v < D; ++v) q[e++] += mb * ((W)3 * s[u] * s[v] - (u == v ? s2 : (W)0));
+    }
+  }
+  return quad;
+}
+
+/* compute_force's loop (octree.h:226-263, octree_force above) for the bodies in targets[nt], the accepted terms in W.  With
+ * d = p - x_i, r = sqrt(|d|^2), eps = eps(T), e2 a number of T (both widened), per accepted node (cell or leaf):
+ *   a_mono += m d / (r + eps)^3            s_mono += m / (r + eps)
+ *   a_soft += m d / (|d|^2 + e2)^(3/2)     s_soft += m / sqrt(|d|^2 + e2)               (soft != 0 only)
+ * and per accepted CELL, Q from octree_quadrupoles_wide:
+ *   a_quad += -(Q d) / r^5 + 5/2 (d^T Q d) d / r^7     s_quad += 1/2 (d^T Q d) / r^5
+ * a_quad_deep: the share of the cells at depth >= split_level (the root is depth 0) in that quadrupole term.  The s sums leave out
+ * the body's own leaf (d == 0 in every coordinate).  Outputs: a_* = c * (a_mono, a_soft, a_mono + a_quad, a_quad_deep), s_* =
+ * (s_mono, s_soft, s_mono + s_quad), and beside each of the six sums the sum of the magnitudes of its terms (|c| included for the
+ * forces), scales[t][6] = {a_mono, a_soft, a_quad, s_mono, s_soft, s_quad}; counts[t][2] as octree_force's. */
+static void FN(octree_walk_wide)(const FN(octree_t) * t, const W* quad, const T* x, T c, T theta, int soft, T e2t, uint32_t split_level,
+                                 const uint32_t* targets, uint32_t nt, const oracle_wide_out* o) {
+  const W eps = (W)T_EPS, e2 = (W)e2t, cw = (W)c, ca = W_FABS((W)c);
+#pragma omp parallel for schedule(dynamic, 64)
+  for (int64_t tt = 0; tt < (int64_t)nt; ++tt) {
+    const T* xi  = &x[(uint64_t)targets[tt] * D];
+    uint32_t idx = 0, depth = 0;
+    T side = t->root_side;
+    W am[D], as[D], aq[D], aqd[D];
+    W sm = 0, ss = 0, sq = 0, k_am = 0, k_as = 0, k_aq = 0, k_sm = 0, k_ss = 0, k_sq = 0;
+    for (int k = 0; k < D; ++k) am[k] = as[k] = aq[k] = aqd[k] = 0;
+    int fwd = 1;
+    uint32_t c_nodes = 0, c_terms = 0;
+    while (idx != OT_EMPTY) {
+      uint32_t next;
+      if (idx == 0) next = OT_EMPTY;
+      else {
+        uint32_t sg = (idx - 1) / OT_CHILDREN, cp = (idx - 1) % OT_CHILDREN;
+        next = cp == (OT_CHILDREN - 1) ? t->parent[sg] : idx + 1;
+      }
+      if (fwd) {
+        const T* mj = &t->m[(uint64_t)idx * (D + 1)];
+        uint32_t fc = t->first_child[idx];
+        T dx = FN(dist)(xi, mj); /* the decision, in T, on the unsoftened distance */
+        ++c_nodes;
+        const int leaf = fc == OT_EMPTY || fc == OT_BODY;
+        if (leaf || side / dx < theta) {
+          W d[D], r2 = 0;
+          int self = 1;
+          for (int k = 0; k < D; ++k) {
+            d[k] = (W)mj[k] - (W)xi[k];
+            r2 += d[k] * d[k];
+            self = self && d[k] == (W)0;
+          }
+          const W r = W_SQRT(r2), mass = (W)mj[D], re = r + eps;
+          const W w = mass / (re * re * re);
+          for (int k = 0; k < D; ++k) am[k] += w * d[k];
+          k_am += W_FABS(w) * r;
+          if (!self) {
+            sm += mass / re;
+            k_sm += W_FABS(mass) / re;
+          }
+          if (soft) {
+            const W q = r2 + e2, rq = W_SQRT(q);
+            const W ws = mass / (q * rq);
+            for (int k = 0; k < D; ++k) as[k] += ws * d[k];
+            k_as += W_FABS(ws) * r;
+            if (!self) {
+              ss += mass / rq;
+              k_ss += W_FABS(mass) / rq;
+            }
+          }
+          if (!leaf) {
+            const W* qq = &quad[(uint64_t)idx * OT_NQ];
+            W Q[D][D], qd[D], dqd = 0, tn = 0;
+            int e = 0;
+            for (int u = 0; u < D; ++u)
+              for (int v = u; v < D; ++v) Q[u][v] = Q[v][u] = qq[e++];
+            for (int u = 0; u < D; ++u) {
+              qd[u] = 0;
+              for (int v = 0; v < D; ++v) qd[u] += Q[u][v] * d[v];
+              dqd += d[u] * qd[u];
+            }
+            const W r5 = r2 * r2 * r, r7 = r5 * r2;
+            for (int k = 0; k < D; ++k) {
+              const W term = -qd[k] / r5 + (W)2.5 * dqd * d[k] / r7;
+              aq[k] += term;
+              if (depth >= split_level) aqd[k] += term;
+              tn += term * term;
+            }
+            k_aq += W_SQRT(tn);
+            const W st = (W)0.5 * dqd / r5;
+            sq += st;
+            k_sq += W_FABS(st);
+          }
+          ++c_terms;
+        } else {
+          next = fc;
+          side /= (T)2;
+          ++depth;
+        }
+      }
+      fwd = next > idx;
+      side *= fwd ? (T)1 : (T)2;
+      depth -= fwd ? 0u : 1u;
+      idx = next;
+    }
+    for (int k = 0; k < D; ++k) {
+      const uint64_t e = (uint64_t)tt * D + k;
+      if (o->a_mono) o->a_mono[e] = (double)(cw * am[k]);
+      if (o->a_soft) o->a_soft[e] = (double)(cw * as[k]);
+      if (o->a_quad) o->a_quad[e] = (double)(cw * (am[k] + aq[k]));
+      if (o->a_quad_deep) o->a_quad_deep[e] = (double)(cw * aqd[k]);
+    }
+    if (o->s_mono) o->s_mono[tt] = (double)sm;
+    if (o->s_soft) o->s_soft[tt] = (double)ss;
+    if (o->s_quad) o->s_quad[tt] = (double)(sm + sq);
+    if (o->scales) {
+      double* sc = &o->scales[(uint64_t)tt * 6];
+      sc[0] = (double)(ca * k_am);
+      sc[1] = (double)(ca * k_as);
+      sc[2] = (double)(ca * (k_am + k_aq));
+      sc[3] = (double)k_sm;
+      sc[4] = (double)k_ss;
+      sc[5] = (double)(k_sm + k_sq);
+    }
+    if (o->counts) {
+      o->counts[(uint64_t)tt * 2 + 0] = c_nodes;
+      o->counts[(uint64_t)tt * 2 + 1] = c_terms;
+    }
+  }
+}
+
+/* The tree of octree_step_force, then the wide walk.  softening > 0: e2 = fl_T(T(softening) * T(softening)); root_q (optional): the
+ * root's OT_NQ values of Q as double.  Returns <0 on overflow. */
+static int FN(octree_step_walk_wide)(const T* m, const T* x, T c, uint32_t sz, T theta, double softening, uint32_t split_level,
+                                     const uint32_t* targets, uint32_t nt, const oracle_wide_out* o) {
+  FN(octree_t) t;
+  int rc = FN(octree_build)(&t, m, x, sz);
+  if (rc == 0) {
+    const T e   = (T)softening;
+    const T e2t = e * e;
+    W* quad     = FN(octree_quadrupoles_wide)(&t);
+    FN(octree_walk_wide)(&t, quad, x, c, theta, softening > 0.0, e2t, split_level, targets, nt, o);
+    if (o->root_q)
+      for (int k = 0; k < OT_NQ; ++k) o->root_q[k] = (double)quad[k];
+    free(quad);
+  }
+  FN(octree_free)(&t);
+  return rc;
+}
+
+#undef OT_NQ
 #undef OT_EMPTY
 #undef OT_BODY
 #undef OT_CHILDREN

@@ -1849,10 +1849,19 @@ __global__ __launch_bounds__(64) void ot_force_softened_kernel(const ot_node<T>*
 // ---- quadrupole moments (nbody_octree_compute_quadrupoles, nbody_octree_compute_quadrupole_force; no reference counterpart) ----
 // Q(cell) = sum over its children c, in child order, empty ones skipped, of Q_c + m_c (3 d d^T - |d|^2 I), d = p_c - p(cell); a body
 // leaf has Q = 0.  2D takes the same formula in the plane (the 3D tensor restricted to z = 0: not traceless, and it need not be).
-// Stored per node beside the tree, node index order (node 0 = the root, node 1 + g * 2^D + c = slot c of sibling group g), kOtNQ<D>
-// values each: xx, xy, xz, yy, yz, zz in 3D, xx, xy, yy in 2D.  Body leaves and empty slots are never written nor read.
+// Stored per node beside the tree, node index order (node 0 = the root, node 1 + g * 2^D + c = slot c of sibling group g), kOtQS<D>
+// values each: the kOtNQ<D> of Q — xx, xy, xz, yy, yz, zz in 3D, xx, xy, yy in 2D —, which is all a walk reads, then the D of the
+// cell's residual dipole (below).  Body leaves and empty slots are never written nor read.
+// The residual dipole.  The shift above is exact for children expanded about their own centres of mass, but a cell's stored p is that
+// centre rounded to T (the reference's bits), a distance ~ eps |p| off: about p the child keeps a dipole P_c = sum_b m_b (x_b - p_c),
+// and the shift owes 3 (P_c d^T + d P_c^T) - 2 (P_c . d) I.  Relative to m_c |d|^2 that is eps |p| / |d| — rounding level for a
+// system around the origin, 1e-4 of Q in float for a cluster of size 1e-4 |p| (found by the per-body comparison with Q summed from
+// the bodies: tests/test_gpu_octree_wide.py, the deep system).  So each cell also carries P = sum_c (P_c + m_c d_c), a body's own
+// being 0, and adds the owed term; where it does not matter P is rounding noise times eps.
 template <int D>
 constexpr int kOtNQ = D == 3 ? 6 : 3;
+template <int D>
+constexpr int kOtQS = kOtNQ<D> + D;
 
 // One cell, after its monopole and the quadrupoles of its child cells: the same children, the same order and the same operations
 // whichever build form numbered the cells, so both forms give the same bits.
@@ -1861,24 +1870,33 @@ __device__ __forceinline__ void ot_quadrupole_cell(ot_tree<T, D> tree, T* __rest
 #pragma clang fp contract(off)
   constexpr uint32_t NCH = 1u << D;
   constexpr int NQ       = kOtNQ<D>;
+  constexpr int QS       = kOtQS<D>;
   const ot_node<T> pn = tree.get(node);
   if (pn.fc >= kOtBody) return;  // only after an overflow flag
-  T q[NQ];
+  T q[NQ], dip[D];
 #pragma unroll
   for (int i = 0; i < NQ; ++i) q[i] = T(0);
+#pragma unroll
+  for (int k = 0; k < D; ++k) dip[k] = T(0);
   for (uint32_t c = 0; c < NCH; ++c) {
     const uint32_t ci   = pn.fc + c;
     const ot_node<T> ch = tree.get(ci);
     if (ch.fc == kOtEmpty) continue;
+    T pc[D];  // the child's residual dipole about its stored p
+#pragma unroll
+    for (int k = 0; k < D; ++k) pc[k] = T(0);
     if (ch.fc != kOtBody) {
 #pragma unroll
-      for (int i = 0; i < NQ; ++i) q[i] += quad[uint64_t(ci) * NQ + i];
+      for (int i = 0; i < NQ; ++i) q[i] += quad[uint64_t(ci) * QS + i];
+#pragma unroll
+      for (int k = 0; k < D; ++k) pc[k] = quad[uint64_t(ci) * QS + NQ + k];
     }
-    T d[D], r2 = T(0);
+    T d[D], r2 = T(0), pd = T(0);
 #pragma unroll
     for (int k = 0; k < D; ++k) {
       d[k] = ch.p[k] - pn.p[k];
       r2   = r2 + d[k] * d[k];
+      pd   = pd + pc[k] * d[k];
     }
     int i = 0;
 #pragma unroll
@@ -1886,13 +1904,21 @@ __device__ __forceinline__ void ot_quadrupole_cell(ot_tree<T, D> tree, T* __rest
 #pragma unroll
       for (int v = u; v < D; ++v, ++i) {
         T e = T(3) * d[u] * d[v];
-        if (u == v) e = e - r2;
-        q[i] += ch.m * e;
+        T f = T(3) * (pc[u] * d[v] + d[u] * pc[v]);
+        if (u == v) {
+          e = e - r2;
+          f = f - T(2) * pd;
+        }
+        q[i] += ch.m * e + f;
       }
     }
+#pragma unroll
+    for (int k = 0; k < D; ++k) dip[k] += pc[k] + ch.m * d[k];
   }
 #pragma unroll
-  for (int i = 0; i < NQ; ++i) quad[uint64_t(node) * NQ + i] = q[i];
+  for (int i = 0; i < NQ; ++i) quad[uint64_t(node) * QS + i] = q[i];
+#pragma unroll
+  for (int k = 0; k < D; ++k) quad[uint64_t(node) * QS + NQ + k] = dip[k];
 }
 
 // build form 1: one launch per level over that level's cell list, deepest first (the lists of ot_multipole_level_kernel)
@@ -3076,7 +3102,7 @@ static int ot_quad_run(nbody_octree* t, hipStream_t st) {
   const ot_tree<T, D> tree{static_cast<ot_group<T, D>*>(t->groups), static_cast<ot_node<T>*>(t->rootrec)};
   T* quad              = static_cast<T*>(t->quad);
   const bool one_pass  = t->build == 0 || t->build == 3;
-  NB_HIP(hipMemsetAsync(quad, 0, sizeof(T) * kOtNQ<D>, st));
+  NB_HIP(hipMemsetAsync(quad, 0, sizeof(T) * kOtQS<D>, st));
   hipLaunchKernelGGL((ot_quadrupole_deep_kernel<T, D>), dim3(64), dim3(64), 0, st, tree, quad, t->cells,
                      one_pass ? t->tops : static_cast<const ot_cell*>(nullptr), t->lvl_count, t->capacity);
   NB_HIP(hipGetLastError());
@@ -3431,8 +3457,8 @@ extern "C" int nbody_octree_compute_quadrupoles(nbody_octree* t, void* stream) {
                 "(outside nbody_graph_begin/end)");
       return NBODY_ERR_STATE;
     }
-    const size_t nq = t->dim == 3 ? 6 : 3;  // every node the groups can hold, and the root
-    NB_HIP(hipMalloc(&t->quad, t->tsz * nq * (size_t(t->max_cells) * (size_t(1) << t->dim) + 1)));
+    const size_t qs = (t->dim == 3 ? 6 : 3) + size_t(t->dim);  // kOtQS: every node the groups can hold, and the root
+    NB_HIP(hipMalloc(&t->quad, t->tsz * qs * (size_t(t->max_cells) * (size_t(1) << t->dim) + 1)));
   }
   int r = dispatch(t->dtype, t->dim, [&](auto tg) {
     using TG = decltype(tg);

@@ -109,10 +109,10 @@
       const bool qon = take && !leaf;
 #ifdef OT_POT
       if (__builtin_amdgcn_ballot_w64(qon) != 0ull)
-        ot_potential_quad<T, D>(qon, pot, di, d2f, y0, quad + (uint64_t(1u + cur * NCH + cc) * uint32_t(kOtNQ<D>)));
+        ot_potential_quad<T, D>(qon, pot, di, d2f, y0, quad + (uint64_t(1u + cur * NCH + cc) * uint32_t(kOtQS<D>)));
 #else
       if (__builtin_amdgcn_ballot_w64(qon) != 0ull)
-        ot_accumulate_quad<T, D>(qon, acc, di, d2f, y0, quad + (uint64_t(1u + cur * NCH + cc) * uint32_t(kOtNQ<D>)));
+        ot_accumulate_quad<T, D>(qon, acc, di, d2f, y0, quad + (uint64_t(1u + cur * NCH + cc) * uint32_t(kOtQS<D>)));
 #endif
     }
 #endif

@@ -232,7 +232,7 @@ def test_softened_trajectory_against_numpy_leapfrog(nb):
 
 
 @pytest.mark.parametrize("dtype", [1, 0])
-def test_softened_octree(nb, dtype):
+def test_softened_octree(nb, oracle, dtype):
     eps = 0.1
     for dim in (3, 2):
         hs = nb.build_model(dtype, dim, "galaxy", 3000)
@@ -250,6 +250,14 @@ def test_softened_octree(nb, dtype):
         soft = t.read_counters(dev.stream)
         assert np.array_equal(plain, soft)
         whole = dev.download().a.copy()
+        # its value: per body against the oracle's wide walk (the same decisions: the counters are the oracle's, test_gpu_octree.py)
+        ref = oracle.State(dtype, dim, hs.n)
+        ref.m[:], ref.x[:], ref.c, ref.dt = hs.m, hs.x, hs.c, hs.dt
+        w = oracle.octree_walk_wide(ref, 0.5, eps)
+        assert np.array_equal(soft, w.counts), dim
+        err = (np.abs(whole.astype(np.float64) - w.a_soft).max(axis=1) / w.scale_a_soft).max()
+        print(f"softened octree {dim}D dtype {dtype}: max err_i {err:.3g}")
+        assert err <= TOL[dtype], (dim, err)
         for parts in (2, 7):
             for p in range(parts):
                 f, e = nb.shard_range(hs.n, p, parts)
