@@ -102,7 +102,12 @@ int nbody_device_info(int device, char* arch_out, size_t arch_len, int* cu_count
 
 /* K1. Replaces all_pairs_force (src/all_pairs.h:14-27):
  *   a[i] = c * sum_{j != i} m[j] * (x[j] - x[i]) / (pow(|x[j]-x[i]|^2, 3/2) + eps(T))
- * for owned bodies i; sources j = 0..sz-1 staged through LDS tiles. */
+ * for owned bodies i; sources j = 0..sz-1 staged through LDS tiles.
+ * In double, from 262 144 bodies on, the automatic launch is ORDERED: sources and the window's targets are sorted by a space key
+ * (the Morton code of the body's cell of side 1) before the kernel runs and `a` is scattered back afterwards — 11 launches per call
+ * (18 for a shard window) and about 48 + 24 + 16 dim bytes of stream scratch per body, reserved with the packed records (so a
+ * context's recorded step never allocates).  The sum of a target then runs in key order: a function of all sz positions, so the
+ * rows of any shard window equal the whole launch's bit for bit; systems on the dense pair rule keep the index order. */
 int nbody_all_pairs_force(const nbody_state* s, void* stream);
 
 /* K1's in-kernel chunk hand-off, and how it fails.  From 2048 bodies on, the source range is cut into >= 16 chunks over grid.y;

@@ -26,6 +26,9 @@
 //   Measured: N = 2^20 galaxy 602-633 ms per pass by the clock the box sustains = 44-46.5 % of the 78.6 TF FP64 vector peak with
 //   the 16 + rsq form (profiles/r05/bench_n1.json; VALU 98 % busy: 97 % of what 16 + rsq allow); the folded form against it,
 //   alternating on one box: profiles/r07/time_folded_weight.txt.
+//   Space order (f64 scalar stream from 262 144 bodies on; see k1_order_wanted below): the packed sources and the window's targets
+//   are sorted by a Morton key of their cells before K1 runs, so that source chunks and target groups are compact in space and
+//   most blocks take the far certificate; K1 itself is the same code.  profiles/r09/time_space_order.txt.
 //
 // K2 (replaces src/all_pairs.h:29-50, intended semantics).  Lanes run along the SOURCE axis (one
 // ordered pair per lane and step), each wave owns 64 targets whose positions it broadcasts with
@@ -37,6 +40,8 @@
 // K3 (replaces src/system.h:52-60).  Pure HBM stream (7*D*sizeof(T) bytes/body), flat elementwise
 // over count*D scalars, FP contraction off so it is bit-identical to the reference's x86 -O2 build.
 #include "common.hpp"
+#include "k1_order_key.hpp"
+#include "radix_sort.hpp"
 
 #include <atomic>
 #include <cstdlib>
@@ -427,7 +432,7 @@ struct scratch_buf {
 struct packed_slot {
   int device;
   hipStream_t stream;
-  scratch_buf buf[8];  // 0: packed sources, 1: K1 turn words, 2: energies work area, 3: the pair rule + partial moments, 4: K1 hand-off status (k1_status), 5: K1 chunk sums of small launches, 6: the packed sources' f64 pair constants (cst_batch), 7: the source chunks' boxes of the far certificate
+  scratch_buf buf[9];  // 0: packed sources, 1: K1 turn words, 2: energies work area, 3: the pair rule + partial moments, 4: K1 hand-off status (k1_status), 5: K1 chunk sums of small launches, 6: the packed sources' f64 pair constants (cst_batch), 7: the source chunks' boxes of the far certificate, 8: the space order's work area (k1_order_layout)
   std::vector<void*> retired;
   bool k1_dirty  = false;  // a K1 that passes turns (or a recorded step, which may hold one) has been queued since the status was last read
   bool k1_failed = false;  // the last read found the sticky error set
@@ -602,6 +607,247 @@ static size_t ap_box_bytes(uint32_t sz, int dim) {
 // can meet (N = 32 768: 2048 sources) and at 65 536: profiles/r08/time_far_certificate.txt.
 static bool k1_box_wanted(uint32_t sz, uint32_t chunks) { return sz >= kFarMinBodies && chunks > 1; }
 
+// ---- space order (f64, unsoftened, scalar stream, sz >= kOrderMinBodies) ------------------------------------------------------------
+// What the far certificate can prove depends on the ORDER of the bodies, not on physics: a source chunk is a run of consecutive
+// records and a target group a run of consecutive targets, and where a generator lays the bodies of a disc out in random order
+// every chunk's box is the whole disc — only blocks that set one disc against the other certify (half of the flagship's), and
+// in the rest 12 % of the batches hold a close pair although 0.05 % of the pairs are close.  An ordered launch therefore sorts
+// the packed sources, and the window's own targets, by a space key (k1_order_key.hpp: the Morton code of the body's cell on a
+// fixed grid of side 1) before K1 runs:
+//   1. k1_prepare_kernel as ever (records, constants, the rule, the turn words; no boxes);
+//   2. k1_order_key_kernel: the key of every body — 0 for all of them on the DENSE rule (known on the device only), so that the
+//      order below is the identity and a dense launch sums bit for bit as it did unordered;
+//   3. radix_sort_pairs: bodies by (key, index) — a total order, so the permutation is a function of the sz positions alone and
+//      every rank, window and run has the same one;
+//   4. k1_order_gather_kernel: records and constants into that order (padding records stay at the end; huge coordinates
+//      clamped, see kOrderSafe), the box of every 256 of
+//      them, and — for a window that is the whole system — the targets' positions, which are the records';
+//      k1_order_box_kernel: the chunks' boxes from those;
+//   5. for any other window: its own bodies' keys, their sort, k1_order_targets_kernel (positions into window order);
+//   6. K1 itself, unchanged, on the ordered records with the ordered targets as its `x` (first = 0) and a contiguous scratch
+//      array as its `a` — the hand-off reads and writes that array exactly as it did `a`;
+//   7. k1_order_scatter_kernel: row k of the scratch array to a[perm[k]] (bit copies: the NaN of a failed hand-off passes).
+// A target's sum runs over the sources in key order: other last bits than the natural order gives, the same on every shard.
+// The gate is a function of sz and the launch kind, so every rank and window takes it alike.  Measured: profiles/r09/time_space_order.txt.
+// Huge coordinates.  K1's pair form is not made for a squared distance that overflows: r2 = +inf, v_rsq_f64 gives 0 and the polish
+// 1 - r2 y^2 is inf * 0 = NaN — in EVERY target's sum, since every target meets that source.  A system with such a body has
+// infinite variances, which the rule reads as "sparse", so it is ordered; the ordered copies that K1 reads (records and targets,
+// never the caller's x) therefore hold every coordinate clamped to +-kOrderSafe = 1e150: no difference of two of them squares
+// beyond 1.2e301, and a pair of a body that far out with one of the bulk gets the weight y^3 <= 1e-450 = 0 — its true term is
+// below 1.3e-300 m for any body within 1e149 of the origin, so 0 is what the sum would have kept of it anyway (bodies that lie
+// beyond 1e150 AND near each other are moved relative to each other: not a system this library serves).  NaN stays NaN (a comparison with it is false), and nothing is clamped on the dense
+// rule, where the launch must keep the bits of the unordered one.  No coordinate of an ordinary system is touched.
+constexpr double kOrderSafe = 1e150;
+__device__ __forceinline__ double k1_order_safe(double p, bool on) { return on && p > kOrderSafe ? kOrderSafe : (on && p < -kOrderSafe ? -kOrderSafe : p); }
+constexpr uint32_t kOrderMinBodies = 262144;
+static bool k1_order_wanted(uint32_t sz, uint32_t chunks) {
+  if (const char* e = experiment_env("NBODY_K1_NO_ORDER"); e && e[0] == '1') return false;  // -DNBODY_EXPERIMENTS builds only
+  uint32_t least = kOrderMinBodies;
+  if (const char* e = experiment_env("NBODY_K1_ORDER_MIN")) least = uint32_t(strtoul(e, nullptr, 10));  // -DNBODY_EXPERIMENTS builds only (tests)
+  return k1_box_wanted(sz, chunks) && sz >= least;
+}
+
+// Scratch buffer 8 of an ordered launch of `count` targets out of sz bodies, D-dimensional: byte offsets, 256-byte aligned.
+struct k1_order_layout {
+  size_t recs, cst, keys[2], idx[2], hist, xs, as, bytes;
+};
+static k1_order_layout k1_order_layout_of(uint32_t sz, uint32_t count, int dim) {
+  const size_t padded = (size_t(sz) + kTileJ - 1) / kTileJ * kTileJ;
+  size_t at           = 0;
+  auto take = [&](size_t bytes) {
+    const size_t here = at;
+    at += (bytes + 255) / 256 * 256;
+    return here;
+  };
+  k1_order_layout l;
+  l.recs = take(32 * padded);
+  l.cst  = take(ap_cst_bytes(padded));
+  for (int b = 0; b < 2; ++b) l.keys[b] = take(sizeof(uint64_t) * sz);
+  for (int b = 0; b < 2; ++b) l.idx[b] = take(sizeof(uint32_t) * sz);
+  const size_t words = radix_sort_scratch_words(sz) > radix_sort_scratch_words(count) ? radix_sort_scratch_words(sz) : radix_sort_scratch_words(count);
+  l.hist  = take(sizeof(uint32_t) * words);
+  l.xs    = take(sizeof(double) * size_t(dim) * count);
+  l.as    = take(sizeof(double) * size_t(dim) * count);
+  l.bytes = at;
+  return l;
+}
+
+template <int D>
+__global__ __launch_bounds__(kBlock) void k1_order_key_kernel(const double* __restrict__ x, uint32_t first, uint32_t n,
+                                                              const k1_rule* __restrict__ rule, uint64_t* __restrict__ keys) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  double p[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) p[k] = x[(uint64_t(first) + i) * D + k];
+  keys[i] = rule->sparse ? k1_order_key<D>(p) : 0ull;
+}
+
+// One thread per packed record (grid: padded / 256 blocks).  pbox: [block][lo[D], hi[D]], as k1_prepare_kernel makes them.
+template <int D>
+__global__ __launch_bounds__(kBlock) void k1_order_gather_kernel(const src_rec<double, D>* __restrict__ in, const cst_batch* __restrict__ cin,
+                                                                 const uint32_t* __restrict__ perm, src_rec<double, D>* __restrict__ out,
+                                                                 cst_batch* __restrict__ cout, uint32_t sz, double* __restrict__ pbox,
+                                                                 double* __restrict__ xs, const k1_rule* __restrict__ rule) {
+  const uint32_t j   = blockIdx.x * kBlock + threadIdx.x;  // < padded
+  const uint32_t src = j < sz ? perm[j] : j;               // (a padding record stays where it is)
+  const bool safe    = rule->sparse != 0u;
+  src_rec<double, D> r = in[src];
+#pragma unroll
+  for (int k = 0; k < D; ++k) r.p[k] = k1_order_safe(r.p[k], safe);
+  out[j] = r;
+  cout[j / 2].m15[j % 2]     = cin[src / 2].m15[src % 2];
+  cout[j / 2].m1875[j % 2]   = cin[src / 2].m1875[src % 2];
+  if (xs != nullptr && j < sz) {
+#pragma unroll
+    for (int k = 0; k < D; ++k) xs[uint64_t(j) * D + k] = r.p[k];
+  }
+  bool finite = true;
+#pragma unroll
+  for (int k = 0; k < D; ++k) finite = finite && (r.p[k] - r.p[k]) == 0.0;
+  double lo[D], hi[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    lo[k] = finite ? r.p[k] : -__builtin_inf();
+    hi[k] = finite ? r.p[k] : __builtin_inf();
+  }
+#pragma unroll
+  for (int k = 0; k < D; ++k)
+    for (int off = 32; off > 0; off >>= 1) {
+      lo[k] = __builtin_fmin(lo[k], __shfl_xor(lo[k], off, 64));
+      hi[k] = __builtin_fmax(hi[k], __shfl_xor(hi[k], off, 64));
+    }
+  __shared__ double bred[2 * D][kWaves];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      bred[k][wave]     = lo[k];
+      bred[D + k][wave] = hi[k];
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < 2 * D) {
+    const int q = int(threadIdx.x);
+    double v    = bred[q][0];
+    for (int w = 1; w < kWaves; ++w) v = q < D ? __builtin_fmin(v, bred[q][w]) : __builtin_fmax(v, bred[q][w]);
+    pbox[size_t(blockIdx.x) * (2 * D) + q] = v;
+  }
+}
+
+// One block per source chunk: the chunk's box from the boxes of its bpc gather blocks (the last chunk may have fewer).
+template <int D>
+__global__ __launch_bounds__(kBlock) void k1_order_box_kernel(const double* __restrict__ pbox, uint32_t nblk, uint32_t bpc, double* __restrict__ cbox) {
+  const uint32_t b0 = blockIdx.x * bpc, b1 = min(nblk, b0 + bpc);
+  double lo[D], hi[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) lo[k] = __builtin_inf(), hi[k] = -__builtin_inf();
+  for (uint32_t b = b0 + threadIdx.x; b < b1; b += kBlock) {
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      lo[k] = __builtin_fmin(lo[k], pbox[size_t(b) * (2 * D) + k]);
+      hi[k] = __builtin_fmax(hi[k], pbox[size_t(b) * (2 * D) + D + k]);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < D; ++k)
+    for (int off = 32; off > 0; off >>= 1) {
+      lo[k] = __builtin_fmin(lo[k], __shfl_xor(lo[k], off, 64));
+      hi[k] = __builtin_fmax(hi[k], __shfl_xor(hi[k], off, 64));
+    }
+  __shared__ double bred[2 * D][kWaves];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      bred[k][wave]     = lo[k];
+      bred[D + k][wave] = hi[k];
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < 2 * D) {
+    const int q = int(threadIdx.x);
+    double v    = bred[q][0];
+    for (int w = 1; w < kWaves; ++w) v = q < D ? __builtin_fmin(v, bred[q][w]) : __builtin_fmax(v, bred[q][w]);
+    cbox[size_t(blockIdx.x) * (2 * D) + q] = v;
+  }
+}
+
+// xs[k] = x[first + perm[k]], k < count (a window that is not the whole system)
+template <int D>
+__global__ __launch_bounds__(kBlock) void k1_order_targets_kernel(const double* __restrict__ x, uint32_t first, uint32_t count,
+                                                                  const uint32_t* __restrict__ perm, double* __restrict__ xs,
+                                                                  const k1_rule* __restrict__ rule) {
+  const uint32_t k = blockIdx.x * kBlock + threadIdx.x;
+  if (k >= count) return;
+  const uint64_t i = uint64_t(first) + perm[k];
+  const bool safe  = rule->sparse != 0u;
+#pragma unroll
+  for (int d = 0; d < D; ++d) xs[uint64_t(k) * D + d] = k1_order_safe(x[i * D + d], safe);
+}
+
+// a[perm[k]] = as[k], k < count, as 64-bit words: whatever K1 left there — a NaN of a failed hand-off too — arrives bit for bit
+template <int D>
+__global__ __launch_bounds__(kBlock) void k1_order_scatter_kernel(const uint64_t* __restrict__ as, uint32_t count, const uint32_t* __restrict__ perm,
+                                                                  uint64_t* __restrict__ a) {
+  const uint32_t k = blockIdx.x * kBlock + threadIdx.x;
+  if (k >= count) return;
+  const uint64_t i = perm[k];
+#pragma unroll
+  for (int d = 0; d < D; ++d) a[i * D + d] = as[uint64_t(k) * D + d];
+}
+
+// What an ordered launch hands to K1 in place of the packed records, the boxes, x and a.
+template <int D>
+struct k1_ordered {
+  src_rec<double, D>* packed;
+  const cst_batch* cst;
+  const double* box;
+  const double* xs;
+  double* as;
+  const uint32_t* tperm;  // the window's targets in launch order, as indices into the window
+};
+
+// Steps 2 to 5 above, queued behind the pre-pass.  `packed`, `cst`, `rule`: what ap_prepare made; tpc: tiles per source chunk.
+template <int D>
+static int k1_order_queue(const nbody_state* s, hipStream_t st, const src_rec<double, D>* packed, const cst_batch* cst, const k1_rule* rule,
+                          uint32_t tpc, k1_ordered<D>* out) {
+  const uint32_t padded = (s->sz + kTileJ - 1) / kTileJ * kTileJ, nblk = padded / kBlock, bpc = tpc * (kTileJ / kBlock);
+  const k1_order_layout l = k1_order_layout_of(s->sz, s->count, D);
+  void *w = nullptr, *b = nullptr;
+  if (int r = ap_scratch_get(st, 8, l.bytes, &w)) return r;
+  if (int r = ap_scratch_get(st, 7, ap_box_bytes(s->sz, D), &b)) return r;
+  char* base = static_cast<char*>(w);
+  uint64_t* keys[2] = {reinterpret_cast<uint64_t*>(base + l.keys[0]), reinterpret_cast<uint64_t*>(base + l.keys[1])};
+  uint32_t* idx[2]  = {reinterpret_cast<uint32_t*>(base + l.idx[0]), reinterpret_cast<uint32_t*>(base + l.idx[1])};
+  uint32_t* hist    = reinterpret_cast<uint32_t*>(base + l.hist);
+  auto* recs        = reinterpret_cast<src_rec<double, D>*>(base + l.recs);
+  auto* csts        = reinterpret_cast<cst_batch*>(base + l.cst);
+  double* xs        = reinterpret_cast<double*>(base + l.xs);
+  double* cbox      = reinterpret_cast<double*>(static_cast<char*>(b) + kBoxHeaderBytes);
+  double* pbox      = cbox + size_t(2 * D) * (padded / kTileJ);
+  const double* x   = static_cast<const double*>(s->x);
+  const bool whole  = s->first == 0 && s->count == s->sz;
+  int fin           = 0;
+  hipLaunchKernelGGL((k1_order_key_kernel<D>), dim3((s->sz + kBlock - 1) / kBlock), dim3(kBlock), 0, st, x, 0u, s->sz, rule, keys[0]);
+  NB_HIP(hipGetLastError());
+  if (int r = radix_sort_pairs(keys, idx, s->sz, kOrderKeyBits, hist, st, &fin)) return r;
+  hipLaunchKernelGGL((k1_order_gather_kernel<D>), dim3(nblk), dim3(kBlock), 0, st, packed, cst, idx[fin], recs, csts, s->sz, pbox,
+                     whole ? xs : static_cast<double*>(nullptr), rule);
+  NB_HIP(hipGetLastError());
+  hipLaunchKernelGGL((k1_order_box_kernel<D>), dim3((nblk + bpc - 1) / bpc), dim3(kBlock), 0, st, pbox, nblk, bpc, cbox);
+  NB_HIP(hipGetLastError());
+  if (!whole) {  // the window's own order (the sources' permutation is spent: its buffers are reused)
+    hipLaunchKernelGGL((k1_order_key_kernel<D>), dim3((s->count + kBlock - 1) / kBlock), dim3(kBlock), 0, st, x, s->first, s->count, rule, keys[0]);
+    NB_HIP(hipGetLastError());
+    if (int r = radix_sort_pairs(keys, idx, s->count, kOrderKeyBits, hist, st, &fin)) return r;
+    hipLaunchKernelGGL((k1_order_targets_kernel<D>), dim3((s->count + kBlock - 1) / kBlock), dim3(kBlock), 0, st, x, s->first, s->count, idx[fin], xs, rule);
+    NB_HIP(hipGetLastError());
+  }
+  *out = {recs, csts, cbox, xs, reinterpret_cast<double*>(base + l.as), idx[fin]};
+  return NBODY_OK;
+}
+
 // Everything a K1 launch needs done first, queued as ONE launch (k1_prepare_kernel): the packed records (pack: the scalar-stream
 // form), the pair rule of the whole system (sz >= kFarMinBodies; nullptr = "dense" below) and the turn words handed back to chunk 0.
 // The softened K1 has no pair rule (with_rule false): no moments are summed.  box_tpc != 0 (f64, pack): the launch's tiles per
@@ -704,8 +950,10 @@ static int launch_all_pairs_sgpr(const nbody_state* s, const k1_plan& plan, hipS
   const T* box          = nullptr;  // f64, unsoftened, from kFarMinBodies on: the chunks' boxes of the far certificate
   bool certify          = !SOFT && sizeof(T) == 8 && k1_box_wanted(s->sz, plan.chunks);
   if (const char* e = experiment_env("NBODY_K1_NO_CERT"); e && e[0] == '1') certify = false;  // -DNBODY_EXPERIMENTS builds only
+  // the space order (see k1_order_wanted): the boxes are then made from the ordered records, not by the pre-pass
+  [[maybe_unused]] const bool ordered = certify && plan.chunks > 1 && k1_order_wanted(s->sz, plan.chunks);
   if (int r = ap_prepare<T, D>(s, st, true, &packed, &cst, &rule, h.turn, h.turn ? sgpr_turn_words<R, JS>(s->count) : 0, !SOFT,
-                               certify ? plan.tiles_per_chunk : 0u, &box))
+                               certify && !ordered ? plan.tiles_per_chunk : 0u, &box))
     return r;
   if constexpr (SOFT) {
     hipLaunchKernelGGL((all_pairs_softened_sgpr_kernel<T, D, R, JS>), dim3(blocks, plan.chunks), dim3(64 * kSgprWaves<JS>), 0, st,
@@ -732,6 +980,21 @@ static int launch_all_pairs_sgpr(const nbody_state* s, const k1_plan& plan, hipS
     return NBODY_OK;
   }
 #endif
+  if constexpr (sizeof(T) == 8) {
+    if (ordered) {
+      k1_ordered<D> o{};
+      if (int r = k1_order_queue<D>(s, st, packed, cst, rule, plan.tiles_per_chunk, &o)) return r;
+      ra.box = o.box;
+      hipLaunchKernelGGL((all_pairs_force_sgpr_kernel<T, D, R, JS>), dim3(blocks, plan.chunks), dim3(64 * kSgprWaves<JS>), 0, st,
+                         o.packed, o.cst, o.xs, o.as, static_cast<T>(s->c), s->sz, 0u, s->count, plan.tiles_per_chunk, h, ra);
+      NB_HIP(hipGetLastError());
+      hipLaunchKernelGGL((k1_order_scatter_kernel<D>), dim3((s->count + kBlock - 1) / kBlock), dim3(kBlock), 0, st,
+                         reinterpret_cast<const uint64_t*>(o.as), s->count, o.tperm, static_cast<uint64_t*>(s->a));
+      NB_HIP(hipGetLastError());
+      if (h.turn != nullptr && h.sums == nullptr) ap_status_mark(st);
+      return NBODY_OK;
+    }
+  }
   hipLaunchKernelGGL((all_pairs_force_sgpr_kernel<T, D, R, JS>), dim3(blocks, plan.chunks), dim3(64 * kSgprWaves<JS>), 0, st,
                      packed, cst, static_cast<const T*>(s->x), static_cast<T*>(s->a), static_cast<T>(s->c), s->sz, s->first, s->count,
                      plan.tiles_per_chunk, h, ra);
@@ -814,7 +1077,10 @@ static int all_pairs_describe(const nbody_state* s, char* out, size_t len) {
     });
     snprintf(out, len, "all_pairs_force_sgpr_kernel<%s,%d,R=%d,JS=%d> tile=%d chunks=%u%s pair=%s%s", t, D, p.r, p.js, kTileJ, p.chunks,
              p.chunks > 1 ? (collect ? "(summed in chunk order by the last to arrive)" : "(summed in turn into a)") : "", pair,
-             sizeof(T) == 8 && k1_box_wanted(s->sz, p.chunks) ? " cert=box-gap>=3[if sparse: blocks proven far skip the r2 test]" : "");
+             sizeof(T) == 8 && k1_box_wanted(s->sz, p.chunks)
+                 ? (k1_order_wanted(s->sz, p.chunks) ? " cert=box-gap>=3[if sparse: blocks proven far skip the r2 test] order=morton30[if sparse]"
+                                                    : " cert=box-gap>=3[if sparse: blocks proven far skip the r2 test]")
+                 : "");
   }
   else
     snprintf(out, len, "all_pairs_force_kernel<%s,%d,R=%d,JS=%d> tile=%d chunks=1 pair=%s", t, D, p.r, p.js, kTileJ, pair);
@@ -834,6 +1100,12 @@ int ap_scratch_reserve(hipStream_t st, const nbody_state* s) {
   if (int r = ap_scratch_get(st, 3, ap_rule_bytes(s->sz, s->dim), &q)) return r;
   if (s->dtype == NBODY_F64 && s->sz >= kFarMinBodies)  // (whatever the launch shape turns out to be)
     if (int r = ap_scratch_get(st, 7, ap_box_bytes(s->sz, s->dim), &q)) return r;
+  if (s->dtype == NBODY_F64) {  // the space order's work area, where this view's launch is an ordered one
+    k1_plan p;
+    if (int rc = plan_all_pairs<double>(s, &p)) return rc;
+    if (p.scalar && k1_order_wanted(s->sz, p.chunks))
+      if (int r = ap_scratch_get(st, 8, k1_order_layout_of(s->sz, s->count, s->dim).bytes, &q)) return r;
+  }
   return dispatch(s->dtype, s->dim, [&](auto tg) {
     using T = typename decltype(tg)::type;
     k1_plan p;
