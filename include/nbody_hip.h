@@ -88,7 +88,8 @@ typedef struct nbody_state {
  *      nbody_octree_block_create, nbody_octree_block_create_on, nbody_octree_block_destroy, nbody_octree_block_start,
  *      nbody_octree_block_step, nbody_octree_block_advance, nbody_octree_block_read.  Additive, same version: the sixth-order
  *      Hermite integrator for all-pairs, nbody_hermite6_create, nbody_hermite6_create_on, nbody_hermite6_destroy,
- *      nbody_hermite6_start, nbody_hermite6_step, nbody_hermite6_read. */
+ *      nbody_hermite6_start, nbody_hermite6_step, nbody_hermite6_read.  Additive, same version: block (individual) time steps
+ *      for it, nbody_hermite6_block_start, nbody_hermite6_block_step, nbody_hermite6_block_advance, nbody_hermite6_block_read. */
 #define NBODY_HIP_ABI_VERSION 2004
 int nbody_abi_version(void);
 
@@ -434,7 +435,7 @@ int  nbody_hermite_block_read(nbody_hermite* h, int what, void* host_out, size_t
  *  - nbody_hermite6_step before nbody_hermite6_start on that handle: NBODY_ERR_STATE.  A handle used with a stream of another
  *    device: NBODY_ERR_ARG.  Every entry switches to the handle's device and restores the caller's.
  *  - nbody_hermite6_read and nbody_hermite6_create(_on) between nbody_graph_begin and nbody_graph_end: NBODY_ERR_STATE.
- * Block time steps for this scheme are not provided (nbody_hermite_block_* steps the fourth-order scheme). */
+ * Block time steps for this scheme: nbody_hermite6_block_* below (nbody_hermite_block_* steps the fourth-order scheme). */
 typedef struct nbody_hermite6 nbody_hermite6;
 int  nbody_hermite6_create(nbody_hermite6** out, int dtype, int dim, uint32_t n);                /* on the current device */
 int  nbody_hermite6_create_on(nbody_hermite6** out, int dtype, int dim, uint32_t n, int device); /* device < 0: the current one */
@@ -448,6 +449,55 @@ int  nbody_hermite6_step(nbody_hermite6* h, const nbody_state* s, double eps, vo
  * and a as they were evaluated), each T[n][D].  bytes must be n * D * sizeof(T) (NBODY_ERR_ARG); NBODY_ERR_STATE before the first
  * start. */
 int  nbody_hermite6_read(nbody_hermite6* h, int what, void* host_out, size_t bytes, void* stream);
+
+/* ---- block (individual) time steps for the sixth-order Hermite integrator: NBODY_F64 only ---------------------------------------
+ * Levels, ticks, tau, the active set and the level rule are those of nbody_hermite_block_* above, word for word: dt_max = s->dt,
+ * L = max_level (0 .. 20), tick = dt_max / 2^L, a level l_i in [0, L], a step of 2^(L - l_i) ticks and an integer tau_i per body; the
+ * active list in ascending body order, built by a stable compaction; deeper if want < h, one doubling at most and only onto the
+ * coarser level's grid if want >= 2 h, a zero denominator means no limit.  What differs from the fourth order:
+ *   start       nbody_hermite6_start's two evaluations: a, the jerk and the snap of all bodies, crackle = 0;
+ *               want_i = eta_start |a_i| / |j_i| (|j_i| = 0: level 0), the fourth order's rule; tau_i = 0.
+ *   predict     ALL bodies to tau_next with h_i = T(tau_next - tau_i) * T(tick): the three chains of nbody_hermite6_step's predictor
+ *               (x to h^5 with the crackle, v to h^4, a to h^3) with h_i in place of h.
+ *   evaluate    (a1, j1, s1) of the ACTIVE bodies only, against all N predicted bodies (a target's own x, v, a are its predicted ones).
+ *   correct     per active body with h = step_i * tick: v1, x1 and the crackle k1 by nbody_hermite6_step's expressions, 1 / h^3 =
+ *               2^(3 l_i) * fl_T(1 / (dt_max dt_max dt_max)) (an exact scaling); then a <- a1, jerk <- j1, snap <- s1, crackle <- k1,
+ *               tau_i = tau_next (0 at 2^L).  Inactive bodies are not written.
+ *   criterion   (Nitadori & Makino 2008) the derivatives at the new time of the quintic through (a0, j0, s0) at 0 and (a1, j1, s1) at h:
+ *                 a3 = k1 = (60 (a1 - a0) - h (24 j0 + 36 j1) + h^2 (9 s1 - 3 s0)) / h^3
+ *                 a4 = (360 (a1 - a0) - h (168 j0 + 192 j1) + h^2 (36 s1 - 24 s0)) / h^4
+ *                 a5 = (720 (a1 - a0) - 360 h (j0 + j1) + 60 h^2 (s1 - s0)) / h^5
+ *                 want = eta ((|a1| |s1| + |j1|^2) / (|a3| |a5| + |a4|^2))^(1/6), evaluated in T as eta * cbrt(sqrt(num / den))
+ *               (1 / h is 2^l_i * fl_T(1 / T(dt_max)), 1 / h^4 and 1 / h^5 products of it with 1 / h^3).
+ * float is refused.  a5 is a fifth difference of the force, of size (h / t)^5 |a| for a body whose force changes on the time scale t;
+ * float force sums carry about 1e-6 |a| of rounding, which inflates a5, shrinks want, shrinks h and so grows 32-fold per halving: a
+ * float run falls to the deepest level within one interval.  Use the fixed step or the fourth-order block steps in float.
+ * With max_level = 0 a block step is nbody_hermite6_step: the launch shape of the active set's kernel follows from (sz, n_active)
+ * alone by nbody_hermite_block_*'s rule with at least two chunks once there are two source tiles, which with every body active is the
+ * fixed step's shape for every sz; chunks are added in chunk order.  Two runs from the same state give the same bits.  The schedule
+ * arrays are allocated by the first block_start on a handle.
+ *  - Argument errors before the device is touched, in this order: s NULL; the state's dtype, dim, window, tuning; the whole-system
+ *    rule; dtype other than NBODY_F64 (the message names the fifth difference and float's rounding); eps; eta / eta_start (finite,
+ *    > 0); max_level (0 .. 20); h NULL; h made for another dtype, dim or n; s->dt (finite, > 0; tick, 1 / dt and 2^(3 L) / dt^3
+ *    normal and finite); for a step, s->dt other than block_start's (all NBODY_ERR_ARG).
+ *  - Then a stream of another device (NBODY_ERR_ARG).  block_start allocates on first use and block_step / block_advance read the
+ *    size of the active set back (8 bytes, blocking): all of them, and block_read, return NBODY_ERR_STATE between nbody_graph_begin
+ *    and nbody_graph_end, and leave the capture usable.
+ *  - block_step / block_advance / block_read before block_start on that handle, or after a later nbody_hermite6_start (which ends the
+ *    block run): NBODY_ERR_STATE.  nbody_hermite6_step may follow a completed block_advance (the system is synchronous).
+ *  - A schedule read back out of range (n_active, tau_next) ends the block run with NBODY_ERR_STATE. */
+int  nbody_hermite6_block_start(nbody_hermite6* h, const nbody_state* s, double eps, double eta_start, int max_level, void* stream);
+/* One block step.  *n_active: the size of its active set, *tau: its tau_next in ticks (2^max_level: the interval is complete);
+ * either may be NULL.  Blocking for the schedule, asynchronous for the evaluation and the corrector. */
+int  nbody_hermite6_block_step(nbody_hermite6* h, const nbody_state* s, double eps, double eta, void* stream, uint32_t* n_active,
+                               uint32_t* tau);
+/* Block steps until the system is synchronous at t + s->dt.  *block_steps: how many, *body_steps: the sum of their active sets
+ * (the force + jerk + snap evaluations made); either may be NULL. */
+int  nbody_hermite6_block_advance(nbody_hermite6* h, const nbody_state* s, double eps, double eta, void* stream, uint64_t* block_steps,
+                                  uint64_t* body_steps);
+/* Blocking.  what: 0 levels int32[n] | 1 tau_i uint32[n] | 2 the active list of the last block step, uint32[n_active] ascending.
+ * bytes must match (NBODY_ERR_ARG). */
+int  nbody_hermite6_block_read(nbody_hermite6* h, int what, void* host_out, size_t bytes, void* stream);
 
 /* ---- block (individual) time steps for the octree leapfrog (no reference counterpart) ----------------------------------------
  * A per-body velocity-Verlet (kick-drift-kick) step on the level grid of the Hermite block steps above, with the force from the

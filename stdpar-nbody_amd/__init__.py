@@ -67,6 +67,7 @@ ABI_SYMBOLS = [
     "nbody_octree_block_step", "nbody_octree_block_advance", "nbody_octree_block_read",
     "nbody_hermite6_create", "nbody_hermite6_create_on", "nbody_hermite6_destroy", "nbody_hermite6_start", "nbody_hermite6_step",
     "nbody_hermite6_read",
+    "nbody_hermite6_block_start", "nbody_hermite6_block_step", "nbody_hermite6_block_advance", "nbody_hermite6_block_read",
 ]
 ABI_MAJOR = 2
 COMM_ID_BYTES = 128
@@ -113,6 +114,10 @@ def lib():
         L.nbody_hermite6_start.argtypes = [vp, vp, d, vp]
         L.nbody_hermite6_step.argtypes = [vp, vp, d, vp]
         L.nbody_hermite6_read.argtypes = [vp, C.c_int, vp, C.c_size_t, vp]
+        L.nbody_hermite6_block_start.argtypes = [vp, vp, d, d, C.c_int, vp]
+        L.nbody_hermite6_block_step.argtypes = [vp, vp, d, d, vp, vp, vp]
+        L.nbody_hermite6_block_advance.argtypes = [vp, vp, d, d, vp, vp, vp]
+        L.nbody_hermite6_block_read.argtypes = [vp, C.c_int, vp, C.c_size_t, vp]
         L.nbody_octree_block_destroy.restype = None
         L.nbody_octree_block_destroy.argtypes = [vp]
         L.nbody_octree_block_start.argtypes = [vp, vp, vp, d, d, d, C.c_int, vp]
@@ -538,6 +543,30 @@ class Hermite6:
         _check(lib().nbody_hermite6_read(self.h, what, _p(out), out.nbytes, stream))
         return out
 
+    # block (individual) time steps: double only
+    def block_start(self, st, eps, eta_start, max_level, stream=None):
+        """a, the jerk, the snap, crackle = 0 and the first levels (nbody_hermite6_block_start): st.dt is the largest step,
+        st.dt / 2^max_level the smallest.  A float handle is refused."""
+        _check(lib().nbody_hermite6_block_start(self.h, C.byref(st), eps, eta_start, max_level, stream))
+
+    def block_step(self, st, eps, eta, stream=None):
+        """One block step: (n_active, tau_next in ticks).  Blocking for the schedule."""
+        na, tau = C.c_uint32(), C.c_uint32()
+        _check(lib().nbody_hermite6_block_step(self.h, C.byref(st), eps, eta, stream, C.byref(na), C.byref(tau)))
+        return na.value, tau.value
+
+    def block_advance(self, st, eps, eta, stream=None):
+        """Block steps until the system is synchronous at t + st.dt: (block steps, body steps)."""
+        bs, bod = C.c_uint64(), C.c_uint64()
+        _check(lib().nbody_hermite6_block_advance(self.h, C.byref(st), eps, eta, stream, C.byref(bs), C.byref(bod)))
+        return bs.value, bod.value
+
+    def block_read(self, what, stream=None, count=None):
+        """0 the levels (int32), 1 tau_i in ticks (uint32), 2 the active list of the last block step (uint32, `count` of them)."""
+        out = np.zeros(self.n if what != 2 else count, np.int32 if what == 0 else np.uint32)
+        _check(lib().nbody_hermite6_block_read(self.h, what, _p(out), out.nbytes, stream))
+        return out
+
 
 class OctreeBlock:
     """Block (individual) time steps for the octree leapfrog (nbody_octree_block_*): owns the levels, tau, the active lists, the
@@ -745,6 +774,27 @@ class DeviceSystem:
         """0 the jerk, 1 the snap, 2 the crackle, 3 / 4 / 5 the predicted x / v / a of the last hermite6_start / hermite6_step,
         (n, dim) of T (blocking)."""
         return self.hermite6.read(what, self.stream)
+
+    def hermite6_block_start(self, eps, eta_start=0.01, max_level=12):
+        """Starts a sixth-order run with block time steps (nbody_hermite6_block_start): dt is the largest step, dt / 2^max_level the
+        smallest.  Double only."""
+        self.hermite6.block_start(self.state(), eps, eta_start, max_level, self.stream)
+
+    def hermite6_block_step(self, eps, eta):
+        """One block step (nbody_hermite6_block_step): (n_active, tau_next in ticks)."""
+        return self.hermite6.block_step(self.state(), eps, eta, self.stream)
+
+    def hermite6_block_advance(self, eps, eta):
+        """Block steps until the system is synchronous at t + dt (nbody_hermite6_block_advance): (block steps, body steps)."""
+        return self.hermite6.block_advance(self.state(), eps, eta, self.stream)
+
+    def hermite6_block_levels(self):
+        """The levels (int32) and tau_i in ticks (uint32) of all bodies (blocking)."""
+        return self.hermite6.block_read(0, self.stream), self.hermite6.block_read(1, self.stream)
+
+    def hermite6_block_active(self, n_active):
+        """The active list of the last block step (ascending body indices); n_active as hermite6_block_step returned it."""
+        return self.hermite6.block_read(2, self.stream, n_active)
 
     # block time steps for the octree leapfrog (no reference counterpart)
     @property
