@@ -89,7 +89,10 @@ typedef struct nbody_state {
  *      nbody_octree_block_step, nbody_octree_block_advance, nbody_octree_block_read.  Additive, same version: the sixth-order
  *      Hermite integrator for all-pairs, nbody_hermite6_create, nbody_hermite6_create_on, nbody_hermite6_destroy,
  *      nbody_hermite6_start, nbody_hermite6_step, nbody_hermite6_read.  Additive, same version: block (individual) time steps
- *      for it, nbody_hermite6_block_start, nbody_hermite6_block_step, nbody_hermite6_block_advance, nbody_hermite6_block_read. */
+ *      for it, nbody_hermite6_block_start, nbody_hermite6_block_step, nbody_hermite6_block_advance, nbody_hermite6_block_read.
+ *      Additive, same version: all-pairs per-body potentials, nearest neighbours and the closest pair, nbody_neighbours_create,
+ *      nbody_neighbours_create_on, nbody_neighbours_destroy, nbody_neighbours_compute, nbody_neighbours_read,
+ *      nbody_neighbours_closest_pair. */
 #define NBODY_HIP_ABI_VERSION 2004
 int nbody_abi_version(void);
 
@@ -557,6 +560,50 @@ int  nbody_octree_block_advance(nbody_octree_block* h, nbody_octree* t, const nb
  * body order | 3 the predicted positions xp of the last block step, T[n][D].  bytes must match (NBODY_ERR_ARG); 2 and 3 before the
  * first block step: NBODY_ERR_STATE. */
 int  nbody_octree_block_read(nbody_octree_block* h, int what, void* host_out, size_t bytes, void* stream);
+
+/* ---- all-pairs per-body potentials, nearest neighbours and the closest pair (no reference counterpart) --------------------------
+ * What a direct-sum code reports beside the force: how deep body i sits in the potential, and who its nearest neighbour is.  Reads a
+ * state's (m, x) and changes nothing in it, so it works after any algorithm or integrator, also at the synchronous end of a
+ * block-step advance.  With T the state's type, D its dimension, e2 = fl_T(T(eps) * T(eps)) and d = x_j - x_i:
+ *   d2_ij      the UNSOFTENED squared distance, computed as one FMA chain in component order: t = d_0 * d_0, then t = fma(d_k, d_k, t).
+ *              Bitwise symmetric in (i, j), because x_i - x_j is the exact negation of x_j - x_i.
+ *   q_ij       d2_ij + e2.
+ *   potential  phi_i = -c * S_i, S_i = sum_{j != i} m_j / sqrt(q_ij): the sign and scaling of the octree potentials above and the pair
+ *              form of nbody_calc_energies_softened.  The self pair is excluded BY INDEX (its term would be m_i / eps, not 0);
+ *              coincident distinct bodies contribute m_j / eps.  One reciprocal square root per pair (v_rsq_f64 polished to third
+ *              order in double, the bare v_rsq_f32 in float, as the softened energies take it); no divide, no sqrt.
+ *   neighbour  nn_i = the j != i with the smallest computed d2_ij, the LOWEST index among equal computed values; nnd2_i = that d2.
+ *              Selection is on the unsoftened d2, so nn and nnd2 do not depend on eps: the same bits for any valid eps.
+ *              n = 1: nn_0 = 0xffffffff, nnd2_0 = +inf, phi_0 = 0.
+ *   closest    the pair (i, j), i < j, with the smallest d2; ties to the lowest i, then the lowest j.  Because d2 is symmetric this
+ *              is the body of lowest index among those with minimal nnd2, together with its nn.  n = 1: (0xffffffff, 0xffffffff, +inf).
+ * eps obeys the rules of the softening section above; eps = 0 is NOT supported (NBODY_ERR_ARG): the unsoftened potential's pair is the
+ * reference's m / (|d| + eps(T)), a different form.
+ * The rounding order of S_i follows from sz alone (the terms of 64 consecutive sources summed by themselves, those sums added per
+ * wave, tile by tile, the block's waves in wave order, the chunks of the source range in chunk order): no atomics, no waiting between
+ * blocks, nothing read from the device or the CU count; nn has an exact tie rule.  Two runs give the same bits for every output, and
+ * so do an eager call and a replayed recorded one, and a handle destroyed and made again.
+ *  - create allocates everything (packed records, the chunks' partial arrays, the three result arrays, the closest-pair record); the
+ *    handle owns the results.  create(_on) between nbody_graph_begin and nbody_graph_end: NBODY_ERR_STATE.
+ *  - compute reads s->m and s->x only: s->v, s->a and s->ao may be NULL or garbage.  Asynchronous, allocates nothing, may be recorded
+ *    into a step graph; four launches, the last a small one that produces the closest-pair record.  Whole system only (first = 0,
+ *    count = sz).
+ *  - Argument errors of compute are found before the device is touched, in the order of nbody_hermite_step: s NULL; the state's
+ *    dtype, dim, window, tuning; the whole-system rule; eps (the message names the softening); h NULL; h made for another dtype, dim
+ *    or n (all NBODY_ERR_ARG).  Then a stream of another device (NBODY_ERR_ARG).
+ *  - read and closest_pair are blocking; NBODY_ERR_STATE before the first compute on that handle and between nbody_graph_begin and
+ *    nbody_graph_end (the capture stays usable).  Every entry switches to the handle's device and restores the caller's. */
+typedef struct nbody_neighbours nbody_neighbours;
+int  nbody_neighbours_create(nbody_neighbours** out, int dtype, int dim, uint32_t n);                /* on the current device */
+int  nbody_neighbours_create_on(nbody_neighbours** out, int dtype, int dim, uint32_t n, int device); /* device < 0: the current one */
+void nbody_neighbours_destroy(nbody_neighbours* h);                                                  /* NULL: no-op */
+/* phi, nn, nnd2 of all bodies and the closest pair at (s->m, s->x), into the handle.  Asynchronous, recordable. */
+int  nbody_neighbours_compute(nbody_neighbours* h, const nbody_state* s, double eps, void* stream);
+/* Blocking.  what: 0 phi T[n] | 1 nn uint32[n] | 2 nnd2 T[n] of the last compute.  bytes must match (NBODY_ERR_ARG; what and
+ * bytes = 0 are refused before the handle is looked at). */
+int  nbody_neighbours_read(nbody_neighbours* h, int what, void* host_out, size_t bytes, void* stream);
+/* Blocking.  The closest pair of the last compute: *i < *j and its d2 as one T; any of the three may be NULL. */
+int  nbody_neighbours_closest_pair(nbody_neighbours* h, uint32_t* i, uint32_t* j, void* d2_out, void* stream);
 
 /* ---- owning context (device mirrors of a host System), used by the C++ CLI host ------------------ */
 

@@ -68,6 +68,8 @@ ABI_SYMBOLS = [
     "nbody_hermite6_create", "nbody_hermite6_create_on", "nbody_hermite6_destroy", "nbody_hermite6_start", "nbody_hermite6_step",
     "nbody_hermite6_read",
     "nbody_hermite6_block_start", "nbody_hermite6_block_step", "nbody_hermite6_block_advance", "nbody_hermite6_block_read",
+    "nbody_neighbours_create", "nbody_neighbours_create_on", "nbody_neighbours_destroy", "nbody_neighbours_compute",
+    "nbody_neighbours_read", "nbody_neighbours_closest_pair",
 ]
 ABI_MAJOR = 2
 COMM_ID_BYTES = 128
@@ -124,6 +126,13 @@ def lib():
         L.nbody_octree_block_step.argtypes = [vp, vp, vp, d, d, d, vp, vp, vp]
         L.nbody_octree_block_advance.argtypes = [vp, vp, vp, d, d, d, vp, vp, vp]
         L.nbody_octree_block_read.argtypes = [vp, C.c_int, vp, C.c_size_t, vp]
+        L.nbody_neighbours_create.argtypes = [vp, C.c_int, C.c_int, C.c_uint32]
+        L.nbody_neighbours_create_on.argtypes = [vp, C.c_int, C.c_int, C.c_uint32, C.c_int]
+        L.nbody_neighbours_destroy.restype = None
+        L.nbody_neighbours_destroy.argtypes = [vp]
+        L.nbody_neighbours_compute.argtypes = [vp, vp, d, vp]
+        L.nbody_neighbours_read.argtypes = [vp, C.c_int, vp, C.c_size_t, vp]
+        L.nbody_neighbours_closest_pair.argtypes = [vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -568,6 +577,45 @@ class Hermite6:
         return out
 
 
+class Neighbours:
+    """All-pairs per-body potentials, nearest neighbours and the closest pair (nbody_neighbours_*): owns the packed records, the
+    chunks' partial arrays and the results."""
+
+    def __init__(self, dtype, dim, n, device=-1):
+        """device: where the handle's buffers live (-1: the calling thread's current device)."""
+        self.h = C.c_void_p()
+        self.dtype, self.dim, self.n = dtype, dim, n
+        _check(lib().nbody_neighbours_create_on(C.byref(self.h), dtype, dim, C.c_uint32(n), device))
+
+    def close(self):
+        if self.h:
+            lib().nbody_neighbours_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def compute(self, st, eps, stream=None):
+        """phi, nn, nnd2 and the closest pair at (st.m, st.x), Plummer softening eps > 0, into the handle.  Asynchronous, recordable."""
+        _check(lib().nbody_neighbours_compute(self.h, C.byref(st), eps, stream))
+
+    def read(self, what, stream=None):
+        """0 phi (n,) of T, 1 nn (n,) uint32, 2 nnd2 (n,) of T of the last compute (blocking)."""
+        out = np.zeros(self.n, np.uint32 if what == 1 else np_dtype(self.dtype))
+        _check(lib().nbody_neighbours_read(self.h, what, _p(out), out.nbytes, stream))
+        return out
+
+    def closest_pair(self, stream=None):
+        """(i, j, d2) of the last compute: i < j, d2 of T (blocking)."""
+        i, j = C.c_uint32(), C.c_uint32()
+        d2 = np.zeros(1, np_dtype(self.dtype))
+        _check(lib().nbody_neighbours_closest_pair(self.h, C.byref(i), C.byref(j), _p(d2), stream))
+        return i.value, j.value, d2[0]
+
+
 class OctreeBlock:
     """Block (individual) time steps for the octree leapfrog (nbody_octree_block_*): owns the levels, tau, the active lists, the
     predicted positions and the scratch of the active set's forces; the tree is the caller's Octree."""
@@ -629,6 +677,7 @@ class DeviceSystem:
         self._hermite = None
         self._octree_block = None
         self._hermite6 = None
+        self._neighbours = None
 
     @classmethod
     def from_host(cls, hs, device=0):
@@ -652,6 +701,9 @@ class DeviceSystem:
         if self._hermite6 is not None:
             self._hermite6.close()
             self._hermite6 = None
+        if self._neighbours is not None:
+            self._neighbours.close()
+            self._neighbours = None
         if self.h:
             lib().nbody_destroy(self.h)
             self.h = C.c_void_p()
@@ -827,6 +879,30 @@ class DeviceSystem:
     def octree_block_predicted(self):
         """The predicted positions of the last block step, (n, dim) of T (blocking)."""
         return self.octree_block.read(3, self.stream)
+
+    # per-body potentials, nearest neighbours, closest pair (no reference counterpart)
+    @property
+    def neighbours_handle(self):
+        if self._neighbours is None:
+            self._neighbours = Neighbours(self.dtype, self.dim, self.n, self.device)
+        return self._neighbours
+
+    def neighbours_compute(self, eps):
+        """nbody_neighbours_compute on the state as it is; a StepGraph may record it."""
+        self.neighbours_handle.compute(self.state(), eps, self.stream)
+
+    def neighbours(self, eps):
+        """(phi, nn, nnd2) of the state as it is: phi_i = -c sum_{j != i} m_j / sqrt(|x_i - x_j|^2 + eps^2) (n,) of T, nn_i the nearest
+        neighbour (n,) uint32, nnd2_i its unsoftened squared distance (n,) of T (blocking)."""
+        h = self.neighbours_handle
+        h.compute(self.state(), eps, self.stream)
+        return h.read(0, self.stream), h.read(1, self.stream), h.read(2, self.stream)
+
+    def closest_pair(self, eps):
+        """(i, j, d2), i < j: the closest pair of the state as it is (blocking)."""
+        h = self.neighbours_handle
+        h.compute(self.state(), eps, self.stream)
+        return h.closest_pair(self.stream)
 
     def calc_energies(self, softening=0.0):
         """(kinetic, potential) as in System::calc_energies (src/system.h:62-79); blocking.  softening > 0: the potential of the

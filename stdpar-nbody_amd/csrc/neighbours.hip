@@ -1,0 +1,532 @@
+// All-pairs per-body potentials, nearest neighbours and the closest pair: nbody_neighbours_* of include/nbody_hip.h.
+// No reference counterpart.  Reads a state's (m, x), changes nothing in it; Plummer softening required for the potential (eps = 0 is
+// refused: the unsoftened potential's pair is the reference's m / (|d| + eps(T)), a different form).
+//
+// Definitions (T the state's type, D its dimension, e2 = fl_T(T(eps) * T(eps)), d = x_j - x_i):
+//   d2_ij   the UNSOFTENED squared distance as one FMA chain in component order: t = d_0 d_0, then t = fma(d_k, d_k, t).  Bitwise
+//           symmetric in (i, j): x_i - x_j is the exact negation of x_j - x_i.
+//   q_ij    d2_ij + e2 (one rounding).
+//   phi_i   -c S_i, S_i = sum_{j != i} m_j / sqrt(q_ij).  The self pair is excluded BY INDEX (its term would be m_i / eps, not 0);
+//           coincident distinct bodies contribute m_j / eps.  One reciprocal square root per pair: v_rsq_f64 polished to third order
+//           (y (1 + e/2 + 3/8 e^2), e = 1 - q y^2) in double, the bare 1-ulp v_rsq_f32 in float — energy.hip's softened pair,
+//           operation for operation.  No divide, no sqrt.
+//   nn_i    the j != i with the smallest computed d2_ij, the LOWEST index among equal values; nnd2_i that d2.  Selection is on the
+//           unsoftened d2, so nn and nnd2 have the same bits for every valid eps.  n = 1: nn = 0xffffffff, nnd2 = +inf, phi = 0.
+//   closest pair   the (i, j), i < j, with the smallest d2, ties to the lowest i, then the lowest j: by the symmetry of d2 the body
+//           of lowest index among those with minimal nnd2, with its nn.  n = 1: (0xffffffff, 0xffffffff, +inf).
+//
+// Four launches per compute, all on the caller's stream, nothing allocated after nbody_neighbours_create:
+//   pack     one lane per record: {x[3], m} (4 T; 2D zero-fills component 2), padded with zero-mass records at the origin to whole
+//            tiles.  A padding record adds m y = 0 to S; it never becomes a neighbour because of an INDEX BOUND: every slice of 64
+//            records that reaches past n runs the checked batch body below, which replaces the d2 of a record j >= n by +inf.
+//   sweep    the hot path, the Hermite sweeps' shape (hermite_tile.hpp): R targets per lane in registers, records staged through LDS
+//            tiles of kHTile and read as wave-uniform broadcasts, every tile cut over the four waves of the block, the tiles cut over
+//            grid.y chunks by hermite_plan_for(sz, 2) — the sixth order's plan: a function of sz alone.  A lane carries S, the
+//            running minimum of d2 and its index.  The terms of a slice (64 records) are summed by themselves, in U interleaved
+//            chains joined pairwise, and the slice sums added up: one chain over a chunk lets a large term swallow the later ones
+//            (energy.hip: 8.4e-6 of the potential at N = 65 537 in float).
+//            Selection: a batch of U records takes U - 1 v_min and ONE compare of the batch's minimum against the running one per
+//            target; only if some lane of the wave found a closer record (one scalar branch; a lane's minimum falls about ln(n)
+//            times in all) do the lanes walk the batch in index order, min and 32-bit select under the compare's mask.  The result
+//            is the same whichever way the branch goes.  The source index is wave-uniform (the wave number is read with
+//            v_readfirstlane), so the walk compares against and selects from a scalar.
+//            Two batch bodies, chosen per slice (wave-uniform): the CHECKED one masks the self pair (term 0, d2 +inf) and the padding
+//            (d2 +inf) by index and runs only for slices that overlap the block's own targets or reach past n — at most two of a
+//            wave's slices per chunk; every other slice runs the plain body, which has no index test at all.
+//            The block's waves merge through LDS: S added in wave order, (d2, index) lexicographically — a wave's slice of a later
+//            tile holds higher indices than another wave's slice of an earlier tile, so `<` on d2 alone would not keep the lowest
+//            index.  The chunk's raw results go to the partial arrays.
+//   finish   one lane per body: the chunks' S added IN CHUNK ORDER and scaled by -c, the chunks' (d2, index) merged by the same
+//            rule; writes phi, nn, nnd2.
+//   closest  one block: the lexicographic minimum of (nnd2, i) over the bodies, strided per lane, then across the wave and the
+//            block — a minimum does not depend on the order it is taken in, no atomics — into the handle's record.
+// The rounding order of S_i (chains of a slice, slices of a tile by wave, tiles in order, waves in order, chunks in order) follows
+// from sz alone — nothing is read from the device or the CU count, no atomics, no waiting between blocks — and nn has an exact tie
+// rule: two runs, an eager call and a replayed recorded one, and a handle destroyed and made again give the same bits.
+// Bound: FP64 / FP32 VALU issue, like the Hermite sweeps; per pair D subtractions, D chain operations, one add, the weight (5 + rsq
+// in double, 1 + rsq in float), one add into the slice sum and (U - 1) / U min + 1 / U compare.
+#include "hermite_tile.hpp"
+
+// every product that is meant to be fused below is written as an fma: m y in float rounds before it is added, whichever batch body
+// (with or without the self pair's select between the two) a slice runs
+#pragma clang fp contract(off)
+
+namespace nbody {
+
+constexpr uint32_t kNoNeighbour = 0xffffffffu;
+constexpr int kNbClosestBlock   = 1024;
+
+// Source record of the sweep: {x[3], m}, D components used.  32 B in double (two ds_read_b128), 16 B in float (one).
+template <typename T>
+struct alignas(sizeof(T) * 4) nb_rec {
+  T p[3];
+  T m;
+};
+
+template <typename T>
+struct nb_closest_rec {  // the handle's closest-pair record
+  T d2;
+  uint32_t i, j;
+};
+
+template <typename T>
+struct nb_consts {
+  T k0375;
+  __device__ __forceinline__ nb_consts() : k0375(T(0.375)) { asm volatile("" : "+s"(k0375)); }  // not an inline constant
+};
+
+template <typename T>
+__device__ __forceinline__ T nb_inf() {
+  return __builtin_huge_val();
+}
+
+// (d2, j) < (best, idx) lexicographically
+template <typename T>
+__device__ __forceinline__ void nb_merge(T& best, uint32_t& idx, T d2, uint32_t j) {
+  const bool take = d2 < best || (d2 == best && j < idx);
+  best            = take ? d2 : best;
+  idx             = take ? j : idx;
+}
+
+// ---- pack ----------------------------------------------------------------------------------------------------------------------
+template <typename T, int D>
+__global__ __launch_bounds__(kHBlock) void neighbours_pack_kernel(const T* __restrict__ m, const T* __restrict__ x, nb_rec<T>* __restrict__ recs,
+                                                                  uint32_t n, uint32_t padded) {
+  const uint32_t i = blockIdx.x * kHBlock + threadIdx.x;
+  if (i >= padded) return;
+  nb_rec<T> r;
+  r.p[0] = r.p[1] = r.p[2] = r.m = T(0);  // padding: zero mass at the origin (kept out of nn by the index bound of the checked slices)
+  if (i < n) {
+    r.m = m[i];
+#pragma unroll
+    for (int k = 0; k < D; ++k) r.p[k] = x[uint64_t(i) * D + k];
+  }
+  recs[i] = r;
+}
+
+// ---- the pair batch ------------------------------------------------------------------------------------------------------------
+// U records (global indices j0 ...) against the R targets of a lane (global indices ti[r]).  ls[b][r]: the slice's U sum chains.
+// CHECK: the self pair and the records j >= n are masked by index; without it the slice holds neither.
+template <typename T, int D, int R, int U, bool CHECK>
+__device__ __forceinline__ void nb_pair_batch(T (&ls)[U][R], T (&best)[R], uint32_t (&idx)[R], const T (&xi)[R][D], const uint32_t (&ti)[R],
+                                              const nb_rec<T> (&s)[U], uint32_t j0, uint32_t n, const nb_consts<T>& pc, T e2) {
+  T d2[U][R], w[U][R];
+#pragma unroll
+  for (int b = 0; b < U; ++b)
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      T d[D];
+#pragma unroll
+      for (int k = 0; k < D; ++k) d[k] = s[b].p[k] - xi[r][k];
+      T t = d[0] * d[0];
+#pragma unroll
+      for (int k = 1; k < D; ++k) t = __builtin_elementwise_fma(d[k], d[k], t);
+      d2[b][r] = t;
+    }
+#pragma unroll
+  for (int b = 0; b < U; ++b)
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const T q = d2[b][r] + e2;
+      if constexpr (sizeof(T) == 8) {  // y (1 + e/2 + 3/8 e^2), e = 1 - q y^2: the 2^-24 seed to third order
+        const T y  = __builtin_amdgcn_rsq(q);
+        const T e  = __builtin_fma(-q, y * y, 1.0);
+        const T p  = __builtin_fma(e, pc.k0375, 0.5);
+        const T my = s[b].m * y;
+        w[b][r]    = __builtin_fma(my, p * e, my);
+      } else {
+        w[b][r] = s[b].m * __builtin_amdgcn_rsqf(q);
+      }
+    }
+  if constexpr (CHECK) {
+#pragma unroll
+    for (int b = 0; b < U; ++b) {
+      const uint32_t j = j0 + uint32_t(b);
+      const bool real  = j < n;  // wave-uniform
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const bool self = j == ti[r];
+        w[b][r]         = self ? T(0) : w[b][r];
+        d2[b][r]        = (real && !self) ? d2[b][r] : nb_inf<T>();
+      }
+    }
+  }
+#pragma unroll
+  for (int b = 0; b < U; ++b)
+#pragma unroll
+    for (int r = 0; r < R; ++r) ls[b][r] += w[b][r];
+  // the batch's minimum against the running one: one compare per target, the walk only where some lane found a closer record
+  bool closer = false;
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    T mn = d2[0][r];
+#pragma unroll
+    for (int b = 1; b < U; ++b) mn = __builtin_elementwise_min(mn, d2[b][r]);
+    closer = closer | (mn < best[r]);
+  }
+  if (__builtin_expect(__builtin_amdgcn_ballot_w64(closer) != 0ull, 0)) {
+#pragma unroll
+    for (int b = 0; b < U; ++b)  // index order: `<` keeps the lowest index among equal values
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const bool take = d2[b][r] < best[r];
+        best[r]         = __builtin_elementwise_min(best[r], d2[b][r]);
+        idx[r]          = take ? j0 + uint32_t(b) : idx[r];
+      }
+  }
+}
+
+// One wave's slice of a tile: SUB records from src (LDS, wave-uniform addresses), global indices j0 ...; adds the slice's sum to S.
+template <typename T, int D, int R, int U, bool CHECK>
+__device__ __forceinline__ void nb_slice(T (&S)[R], T (&best)[R], uint32_t (&idx)[R], const T (&xi)[R][D], const uint32_t (&ti)[R],
+                                         const nb_rec<T>* src, uint32_t j0, uint32_t n, const nb_consts<T>& pc, T e2) {
+  constexpr int SUB = kHTile / kHWaves;
+  T ls[U][R];
+#pragma unroll
+  for (int b = 0; b < U; ++b)
+#pragma unroll
+    for (int r = 0; r < R; ++r) ls[b][r] = T(0);
+#pragma unroll 1
+  for (int jj = 0; jj < SUB; jj += U) {
+    nb_rec<T> s[U];  // field by field: a struct copy may be left in private memory by the compiler
+#pragma unroll
+    for (int b = 0; b < U; ++b) {
+#pragma unroll
+      for (int k = 0; k < D; ++k) s[b].p[k] = src[jj + b].p[k];
+      s[b].m = src[jj + b].m;
+    }
+    nb_pair_batch<T, D, R, U, CHECK>(ls, best, idx, xi, ti, s, j0 + uint32_t(jj), n, pc, e2);
+  }
+  // the U chains pairwise: (0 + 1) + (2 + 3)
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    T t;
+    if constexpr (U == 4) t = (ls[0][r] + ls[1][r]) + (ls[2][r] + ls[3][r]);
+    else if constexpr (U == 2) t = ls[0][r] + ls[1][r];
+    else t = ls[0][r];
+    S[r] += t;
+  }
+}
+
+// ---- sweep ---------------------------------------------------------------------------------------------------------------------
+// grid (blocks of 64 R targets, chunks).  part_s, part_d: T[chunk][n], part_j: uint32[chunk][n] — a chunk's raw S, minimum and index.
+template <typename T, int D, int R>
+__global__ __launch_bounds__(kHBlock) void neighbours_sweep_kernel(const nb_rec<T>* __restrict__ recs, T* __restrict__ part_s,
+                                                                   T* __restrict__ part_d, uint32_t* __restrict__ part_j, T e2, uint32_t n,
+                                                                   uint32_t ntiles, uint32_t tiles_per_chunk) {
+  constexpr int SUB = kHTile / kHWaves;              // records of a tile one wave takes
+  constexpr int U   = (sizeof(T) == 8 ? 2 : 4) / R;  // records a batch: 2 pairs in flight per lane in double, 4 in float
+  constexpr int NH  = (kHWaves - 1) * R * 64;        // the other waves' results, handed over through LDS
+  constexpr size_t kTileBytes = sizeof(nb_rec<T>) * kHTile, kHandBytes = (2 * sizeof(T) + sizeof(uint32_t)) * NH;
+  __shared__ __attribute__((aligned(64))) unsigned char smem[kTileBytes > kHandBytes ? kTileBytes : kHandBytes];
+  const nb_rec<T>* tile = reinterpret_cast<const nb_rec<T>*>(smem);
+  T* tflat              = reinterpret_cast<T*>(smem);
+  T* hand_s             = reinterpret_cast<T*>(smem);  // after the last tile has been consumed
+  T* hand_d             = hand_s + NH;
+  uint32_t* hand_j      = reinterpret_cast<uint32_t*>(hand_d + NH);
+
+  const int lane      = threadIdx.x & 63;
+  const uint32_t wave = uint32_t(__builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)));  // in an SGPR: source indices stay scalar
+
+  T xi[R][D], S[R], best[R];
+  uint32_t ti[R], idx[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    ti[r]            = blockIdx.x * (64 * R) + r * 64 + lane;
+    const uint32_t i = ti[r] < n ? ti[r] : 0u;  // clamp: out-of-range lanes compute, never store
+#pragma unroll
+    for (int k = 0; k < D; ++k) xi[r][k] = recs[i].p[k];
+    S[r]    = T(0);
+    best[r] = nb_inf<T>();
+    idx[r]  = kNoNeighbour;
+  }
+  const uint32_t own0 = blockIdx.x * (64 * R), own1 = own0 + 64 * R;  // the block's own targets
+
+  const uint32_t t0 = blockIdx.y * tiles_per_chunk;
+  const uint32_t t1 = t0 + tiles_per_chunk < ntiles ? t0 + tiles_per_chunk : ntiles;
+  const nb_consts<T> pc;
+
+  const T* flat = reinterpret_cast<const T*>(recs);
+  T stage[4];  // one record per lane, value by value
+  auto stage_load = [&](uint32_t t) {  // the record array is padded to whole tiles
+#pragma unroll
+    for (int k = 0; k < 4; ++k) stage[k] = flat[(uint64_t(t) * kHTile + threadIdx.x) * 4 + k];
+  };
+  stage_load(t0);
+  for (uint32_t t = t0; t < t1; ++t) {
+    __syncthreads();  // every wave is done reading the previous tile
+#pragma unroll
+    for (int k = 0; k < 4; ++k) tflat[threadIdx.x * 4 + k] = stage[k];
+    __syncthreads();
+    if (t + 1 < t1) stage_load(t + 1);  // in flight while this tile is consumed
+
+    const nb_rec<T>* src = &tile[wave * SUB];
+    const uint32_t j0    = t * kHTile + wave * SUB;
+    // wave-uniform: does the slice hold a target of this block (the self pair) or a record past n (padding)?
+    const bool checked = (j0 + SUB > n) | ((j0 < own1) & (j0 + SUB > own0));
+    if (checked) nb_slice<T, D, R, U, true>(S, best, idx, xi, ti, src, j0, n, pc, e2);
+    else nb_slice<T, D, R, U, false>(S, best, idx, xi, ti, src, j0, n, pc, e2);
+  }
+
+  // the four slices: S in wave order, (d2, index) lexicographically
+  __syncthreads();
+  if (wave > 0) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int slot = ((int(wave) - 1) * R + r) * 64 + lane;
+      hand_s[slot]   = S[r];
+      hand_d[slot]   = best[r];
+      hand_j[slot]   = idx[r];
+    }
+  }
+  __syncthreads();
+  if (wave == 0) {
+#pragma unroll
+    for (int p = 1; p < kHWaves; ++p)
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const int slot = ((p - 1) * R + r) * 64 + lane;
+        S[r] += hand_s[slot];
+        nb_merge<T>(best[r], idx[r], hand_d[slot], hand_j[slot]);
+      }
+    const uint64_t row = uint64_t(blockIdx.y) * n;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      if (ti[r] < n) {
+        part_s[row + ti[r]] = S[r];
+        part_d[row + ti[r]] = best[r];
+        part_j[row + ti[r]] = idx[r];
+      }
+    }
+  }
+}
+
+// ---- finish --------------------------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(kHBlock) void neighbours_finish_kernel(const T* __restrict__ part_s, const T* __restrict__ part_d,
+                                                                    const uint32_t* __restrict__ part_j, T* __restrict__ phi,
+                                                                    uint32_t* __restrict__ nn, T* __restrict__ nnd2, T c, uint32_t n,
+                                                                    uint32_t chunks) {
+  const uint32_t i = blockIdx.x * kHBlock + threadIdx.x;
+  if (i >= n) return;
+  T S = part_s[i], best = part_d[i];
+  uint32_t idx = part_j[i];
+  for (uint32_t ch = 1; ch < chunks; ++ch) {
+    const uint64_t e = uint64_t(ch) * n + i;
+    S += part_s[e];
+    nb_merge<T>(best, idx, part_d[e], part_j[e]);
+  }
+  phi[i]  = -c * S;
+  nn[i]   = idx;
+  nnd2[i] = best;
+}
+
+// ---- closest -------------------------------------------------------------------------------------------------------------------
+// One block.  The lexicographic minimum of (nnd2_i, i); its body's nn is the pair's j.  A body without a neighbour (n = 1) gives
+// (0xffffffff, 0xffffffff, +inf).
+template <typename T>
+__global__ __launch_bounds__(kNbClosestBlock) void neighbours_closest_kernel(const T* __restrict__ nnd2, const uint32_t* __restrict__ nn,
+                                                                             nb_closest_rec<T>* __restrict__ out, uint32_t n) {
+  __shared__ T red_d[kNbClosestBlock / 64];
+  __shared__ uint32_t red_i[kNbClosestBlock / 64];
+  T best       = nb_inf<T>();
+  uint32_t idx = kNoNeighbour;
+  for (uint32_t i = threadIdx.x; i < n; i += kNbClosestBlock) nb_merge<T>(best, idx, nnd2[i], i);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const T od        = __shfl_xor(best, off, 64);
+    const uint32_t oi = __shfl_xor(idx, off, 64);
+    nb_merge<T>(best, idx, od, oi);
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+    red_d[wave] = best;
+    red_i[wave] = idx;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < kNbClosestBlock / 64; ++w) nb_merge<T>(best, idx, red_d[w], red_i[w]);
+    nb_closest_rec<T> r;
+    const uint32_t j = idx < n ? nn[idx] : kNoNeighbour;
+    r.d2             = best;
+    r.i              = j == kNoNeighbour ? kNoNeighbour : idx;
+    r.j              = j;
+    *out             = r;
+  }
+}
+
+}  // namespace nbody
+
+using namespace nbody;
+
+// started: nbody_neighbours_compute has run (host call order, which a recorded step replays).  recs: nb_rec<T>[padded]; part: the
+// chunks' S, T[chunks][n].
+struct nbody_neighbours : hermite_handle {
+  void* part_d     = nullptr;  // T[chunks][n]: the chunks' minimum d2
+  uint32_t* part_j = nullptr;  // [chunks][n]: its index
+  void* phi        = nullptr;  // T[n]
+  uint32_t* nn     = nullptr;  // [n]
+  void* nnd2       = nullptr;  // T[n]
+  void* closest    = nullptr;  // nb_closest_rec<T>
+};
+
+namespace nbody {
+
+// check_state without the arrays this call never reads: v, a and ao may be NULL
+static int neighbours_check_state(const nbody_state* s, const char* who) {
+  NB_ARG(s != nullptr, "nbody_state is NULL");
+  NB_ARG(s->dtype == NBODY_F32 || s->dtype == NBODY_F64, "bad dtype %d", s->dtype);
+  NB_ARG(s->dim == 2 || s->dim == 3, "bad dim %d (must be 2 or 3)", s->dim);
+  NB_ARG(s->m && s->x, "nbody_state has a NULL array pointer (m, x)");
+  NB_ARG(uint64_t(s->first) + uint64_t(s->count) <= uint64_t(s->sz), "shard [%u, %u+%u) exceeds sz=%u", s->first, s->first, s->count,
+         s->sz);
+  if (s->tuning != 0) {
+    NB_ARG((s->tuning & ~0x1ffu) == 0 && (s->tuning & 0x100u) != 0, "nbody_state.tuning = 0x%x is not 0 or an NBODY_TUNING(...) value",
+           s->tuning);
+    if (int r = check_tuning(int(s->tuning & 15u), int((s->tuning >> 4) & 3u), int((s->tuning >> 6) & 3u))) return r;
+  }
+  NB_ARG(s->first == 0 && s->count == s->sz, "%s needs the whole system (first = 0, count = sz), got [%u, %u+%u) of %u", who, s->first,
+         s->first, s->count, s->sz);
+  return NBODY_OK;
+}
+
+template <typename T, int D, int R>
+static int neighbours_launch(nbody_neighbours* h, const nbody_state* s, T e2, hipStream_t st) {
+  const hermite_plan& p = h->plan;
+  auto* recs            = static_cast<nb_rec<T>*>(h->recs);
+  T* part_s             = static_cast<T*>(h->part);
+  T* part_d             = static_cast<T*>(h->part_d);
+  T* nnd2               = static_cast<T*>(h->nnd2);
+  hipLaunchKernelGGL((neighbours_pack_kernel<T, D>), dim3(h->padded / kHBlock), dim3(kHBlock), 0, st, static_cast<const T*>(s->m),
+                     static_cast<const T*>(s->x), recs, h->n, h->padded);
+  NB_HIP(hipGetLastError());
+  hipLaunchKernelGGL((neighbours_sweep_kernel<T, D, R>), dim3(p.blocks, p.chunks), dim3(kHBlock), 0, st, recs, part_s, part_d, h->part_j,
+                     e2, h->n, p.ntiles, p.tiles_per_chunk);
+  NB_HIP(hipGetLastError());
+  hipLaunchKernelGGL((neighbours_finish_kernel<T>), dim3((h->n + kHBlock - 1) / kHBlock), dim3(kHBlock), 0, st, part_s, part_d, h->part_j,
+                     static_cast<T*>(h->phi), h->nn, nnd2, static_cast<T>(s->c), h->n, p.chunks);
+  NB_HIP(hipGetLastError());
+  hipLaunchKernelGGL((neighbours_closest_kernel<T>), dim3(1), dim3(kNbClosestBlock), 0, st, nnd2, h->nn,
+                     static_cast<nb_closest_rec<T>*>(h->closest), h->n);
+  NB_HIP(hipGetLastError());
+  return NBODY_OK;
+}
+
+// the tail of the two blocking reads, after their argument checks: the device, then the state rules
+static int neighbours_read_ready(const nbody_neighbours* h, const char* who, hipStream_t st) {
+  if (int r = check_same_device(h->device, st, "nbody_neighbours")) return r;
+  if (capture_id(st) != 0) {
+    set_error("%s is blocking: it cannot be recorded (call it outside nbody_graph_begin/end)", who);
+    return NBODY_ERR_STATE;
+  }
+  if (!h->started) {
+    set_error("%s before nbody_neighbours_compute on this handle", who);
+    return NBODY_ERR_STATE;
+  }
+  return NBODY_OK;
+}
+
+}  // namespace nbody
+
+extern "C" int nbody_neighbours_create(nbody_neighbours** out, int dtype, int dim, uint32_t n) {
+  return nbody_neighbours_create_on(out, dtype, dim, n, -1);
+}
+
+extern "C" int nbody_neighbours_create_on(nbody_neighbours** out, int dtype, int dim, uint32_t n, int device) {
+  if (int r = hermite_create_check(out, dtype, dim, n, &device, "neighbours")) return r;
+  device_guard guard(device);
+  auto* h   = new nbody_neighbours;
+  h->device = device;
+  h->dtype  = dtype;
+  h->dim    = dim;
+  h->n      = n;
+  h->tsz    = dtype == NBODY_F32 ? 4 : 8;
+  h->plan   = hermite_plan_for(n, 2);
+  h->padded = h->plan.ntiles * uint32_t(kHTile);
+  const size_t rows = size_t(h->plan.chunks) * size_t(n);
+  // nothing is cleared: every compute writes all of it before it reads it
+  hipError_t e = hipMalloc(&h->recs, h->tsz * 4 * size_t(h->padded));
+  if (e == hipSuccess) e = hipMalloc(&h->part, h->tsz * rows);
+  if (e == hipSuccess) e = hipMalloc(&h->part_d, h->tsz * rows);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->part_j), sizeof(uint32_t) * rows);
+  if (e == hipSuccess) e = hipMalloc(&h->phi, h->tsz * size_t(n));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->nn), sizeof(uint32_t) * size_t(n));
+  if (e == hipSuccess) e = hipMalloc(&h->nnd2, h->tsz * size_t(n));
+  if (e == hipSuccess) e = hipMalloc(&h->closest, 16);
+  if (e != hipSuccess) {
+    int r = hip_fail(e, "nbody_neighbours_create allocation", __FILE__, __LINE__);
+    nbody_neighbours_destroy(h);
+    return r;
+  }
+  *out = h;
+  return NBODY_OK;
+}
+
+extern "C" void nbody_neighbours_destroy(nbody_neighbours* h) {
+  if (!h) return;
+  device_guard guard(h->device);
+  (void)hipFree(h->recs);
+  (void)hipFree(h->part);
+  (void)hipFree(h->part_d);
+  (void)hipFree(h->part_j);
+  (void)hipFree(h->phi);
+  (void)hipFree(h->nn);
+  (void)hipFree(h->nnd2);
+  (void)hipFree(h->closest);
+  delete h;
+}
+
+extern "C" int nbody_neighbours_compute(nbody_neighbours* h, const nbody_state* s, double eps, void* stream) {
+  if (int r = neighbours_check_state(s, "nbody_neighbours_compute")) return r;
+  return dispatch(s->dtype, s->dim, [&](auto tg) {
+    using T         = typename decltype(tg)::type;
+    constexpr int D = decltype(tg)::dim;
+    T e2;
+    if (int r = hermite_check_call<T>(h, s, eps, as_stream(stream), "nbody_neighbours", "nbody_neighbours_compute", nullptr, &e2)) return r;
+    device_guard guard(h->device);
+    const int r = h->plan.R == 2 ? neighbours_launch<T, D, 2>(h, s, e2, as_stream(stream)) : neighbours_launch<T, D, 1>(h, s, e2, as_stream(stream));
+    if (r == NBODY_OK) h->started = true;
+    return r;
+  });
+}
+
+extern "C" int nbody_neighbours_read(nbody_neighbours* h, int what, void* host_out, size_t bytes, void* stream) {
+  NB_ARG(what >= 0 && what <= 2, "what must be 0 (phi), 1 (nn) or 2 (nnd2), got %d", what);
+  NB_ARG(bytes != 0, "nbody_neighbours_read(what = %d): bytes is 0, it must be n elements", what);
+  NB_ARG(h != nullptr, "nbody_neighbours is NULL");
+  NB_ARG(host_out != nullptr, "host_out is NULL");
+  const size_t need = (what == 1 ? sizeof(uint32_t) : h->tsz) * size_t(h->n);
+  NB_ARG(bytes == need, "nbody_neighbours_read(what = %d) needs %zu bytes, got %zu", what, need, bytes);
+  const hipStream_t st = as_stream(stream);
+  if (int r = neighbours_read_ready(h, "nbody_neighbours_read", st)) return r;
+  device_guard guard(h->device);
+  const void* src = what == 0 ? h->phi : what == 1 ? static_cast<const void*>(h->nn) : h->nnd2;
+  NB_HIP(hipMemcpyAsync(host_out, src, bytes, hipMemcpyDeviceToHost, st));
+  NB_HIP(hipStreamSynchronize(st));
+  return NBODY_OK;
+}
+
+extern "C" int nbody_neighbours_closest_pair(nbody_neighbours* h, uint32_t* i, uint32_t* j, void* d2_out, void* stream) {
+  NB_ARG(h != nullptr, "nbody_neighbours is NULL");
+  const hipStream_t st = as_stream(stream);
+  if (int r = neighbours_read_ready(h, "nbody_neighbours_closest_pair", st)) return r;
+  device_guard guard(h->device);
+  unsigned char raw[16];
+  NB_HIP(hipMemcpyAsync(raw, h->closest, sizeof raw, hipMemcpyDeviceToHost, st));
+  NB_HIP(hipStreamSynchronize(st));
+  uint32_t ij[2];
+  if (h->dtype == NBODY_F64) {
+    nb_closest_rec<double> r;
+    memcpy(&r, raw, sizeof r);
+    ij[0] = r.i, ij[1] = r.j;
+    if (d2_out) *static_cast<double*>(d2_out) = r.d2;
+  } else {
+    nb_closest_rec<float> r;
+    memcpy(&r, raw, sizeof r);
+    ij[0] = r.i, ij[1] = r.j;
+    if (d2_out) *static_cast<float*>(d2_out) = r.d2;
+  }
+  if (i) *i = ij[0];
+  if (j) *j = ij[1];
+  return NBODY_OK;
+}

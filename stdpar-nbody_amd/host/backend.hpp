@@ -45,6 +45,7 @@ class Device {
     push();
   }
   ~Device() {
+    if (neighbours_) nbody_neighbours_destroy(neighbours_);
     if (hermite_) nbody_hermite_destroy(hermite_);
     if (hermite6_) nbody_hermite6_destroy(hermite6_);
     if (octree_block_) nbody_octree_block_destroy(octree_block_);
@@ -137,6 +138,20 @@ class Device {
     if (softening > 0.0) backend_check(nbody_calc_energies_softened(&view_[0], softening, &ke, &pe, stream()), "nbody_calc_energies_softened");
     else backend_check(nbody_calc_energies(&view_[0], &ke, &pe, stream()), "nbody_calc_energies");
     return {ke, pe};
+  }
+
+  // --save-neighbours: per-body potentials, nearest neighbours and their squared distances of the current (m, x), into the host
+  // vectors (nbody_neighbours_*; the reads are blocking)
+  void neighbours(double eps, std::vector<T>& phi, std::vector<std::uint32_t>& nn, std::vector<T>& nnd2) {
+    single("--save-neighbours");
+    if (!neighbours_) backend_check(nbody_neighbours_create_on(&neighbours_, dtype, D, host_.n, 0), "nbody_neighbours_create_on");
+    backend_check(nbody_neighbours_compute(neighbours_, &view_[0], eps, stream()), "nbody_neighbours_compute");
+    phi.resize(host_.n);
+    nn.resize(host_.n);
+    nnd2.resize(host_.n);
+    backend_check(nbody_neighbours_read(neighbours_, 0, phi.data(), phi.size() * sizeof(T), stream()), "nbody_neighbours_read");
+    backend_check(nbody_neighbours_read(neighbours_, 1, nn.data(), nn.size() * sizeof(std::uint32_t), stream()), "nbody_neighbours_read");
+    backend_check(nbody_neighbours_read(neighbours_, 2, nnd2.data(), nnd2.size() * sizeof(T), stream()), "nbody_neighbours_read");
   }
 
   // Record the phase calls issued by `step` once and return a replayable graph of them (one submission per step).
@@ -239,6 +254,7 @@ class Device {
   nbody_hermite* hermite_ = nullptr;
   nbody_hermite6* hermite6_ = nullptr;
   nbody_octree_block* octree_block_ = nullptr;
+  nbody_neighbours* neighbours_ = nullptr;
 };
 
 }  // namespace nb

@@ -61,6 +61,10 @@ struct Options {
   double block_eta = 0.0;  // 0: one shared step
   int block_levels = 12;
   bool block_levels_given = false;
+  // not in the reference either (nor in --help): --save-neighbours, at every frame the run's Saver records, the per-body potentials,
+  // nearest neighbours and their squared distances (nbody_neighbours_*) are appended to neighbours.bin; independent of --save; one
+  // GPU, with --softening EPS > 0 (the potential's softening length)
+  bool save_neighbours = false;
 };
 
 namespace detail {
@@ -191,6 +195,8 @@ inline Options parse_options(std::vector<std::string> const& argv) {
       o.quadrupole = true;
     } else if (f == "--tree-energy") {
       o.tree_energy = true;
+    } else if (f == "--save-neighbours") {
+      o.save_neighbours = true;
     } else if (f == "--print-state") {
       o.print_state = true;
     } else if (f == "--print-info") {
@@ -213,6 +219,16 @@ inline Options parse_options(std::vector<std::string> const& argv) {
   if (o.csv_detailed && o.csv_total) {
     std::cerr << "Cannot capture a CSV detailed and coarse trace in the same run. Specify one or the other." << std::endl;
     std::exit(EXIT_FAILURE);
+  }
+  if (o.save_neighbours) {
+    if (!(o.softening > 0.0)) {
+      std::cerr << "--save-neighbours needs --softening EPS with EPS > 0." << std::endl;
+      std::exit(EXIT_FAILURE);
+    }
+    if (o.gpus_given) {
+      std::cerr << "--save-neighbours runs on one GPU: it cannot be combined with --gpus." << std::endl;
+      std::exit(EXIT_FAILURE);
+    }
   }
   if (o.block_levels_given && !(o.block_eta > 0.0)) {
     std::cerr << "--block-levels needs --block-eta ETA." << std::endl;

@@ -1,11 +1,14 @@
 // positions.bin / energy.bin writers in the reference's on-disk format (src/saving.h:85-122):
 //   positions.bin: u32 nbodies, u32 steps, u32 sizeof(T), u32 dim, then one frame of x per save_all
 //   energy.bin:    u32 steps, u32 sizeof(T), then (kinetic, potential) per save_all
+// and, with --save-neighbours (no reference counterpart), in the same style
+//   neighbours.bin: u32 nbodies, u32 steps, u32 sizeof(T), u32 dim, then per save_all phi T[n], nn u32[n], nnd2 T[n]
 #pragma once
 #include <cstdint>
 #include <cstdlib>
 #include <fstream>
 #include <iostream>
+#include <vector>
 
 #include "backend.hpp"
 #include "options.hpp"
@@ -17,7 +20,7 @@ class Saver {
  public:
   explicit Saver(Options const& o)
    : pos_(o.save_pos), energy_(o.save_energy), tree_energy_(o.tree_energy), quadrupole_(o.quadrupole), softening_(o.softening),
-     theta_(o.theta), nbodies_(std::uint32_t(o.size)), nsteps_(std::uint32_t(o.steps)) {
+     neighbours_(o.save_neighbours), theta_(o.theta), nbodies_(std::uint32_t(o.size)), nsteps_(std::uint32_t(o.steps)) {
     std::uint32_t const tsz = sizeof(T), dim = D;
     if (pos_) {
       pos_file_.open("positions.bin", std::ios::out | std::ios::binary);
@@ -31,9 +34,16 @@ class Saver {
       put(energy_file_, nsteps_);
       put(energy_file_, tsz);
     }
+    if (neighbours_) {
+      neighbours_file_.open("neighbours.bin", std::ios::out | std::ios::binary);
+      put(neighbours_file_, nbodies_);
+      put(neighbours_file_, nsteps_);
+      put(neighbours_file_, tsz);
+      put(neighbours_file_, dim);
+    }
   }
 
-  bool active() const { return pos_ || energy_; }
+  bool active() const { return pos_ || energy_ || neighbours_; }
 
   // one frame; the device copy is authoritative, so positions are pulled first
   void save_all(System<T, D>& sys, Device<T, D>& dev) {
@@ -46,6 +56,12 @@ class Saver {
       put(energy_file_, kinetic);
       put(energy_file_, potential);
     }
+    if (neighbours_) {
+      dev.neighbours(softening_, phi_, nn_, nnd2_);
+      neighbours_file_.write(reinterpret_cast<char const*>(phi_.data()), std::streamsize(phi_.size() * sizeof(T)));
+      neighbours_file_.write(reinterpret_cast<char const*>(nn_.data()), std::streamsize(nn_.size() * sizeof(std::uint32_t)));
+      neighbours_file_.write(reinterpret_cast<char const*>(nnd2_.data()), std::streamsize(nnd2_.size() * sizeof(T)));
+    }
   }
 
  private:
@@ -56,9 +72,12 @@ class Saver {
   bool pos_, energy_;
   bool tree_energy_, quadrupole_;  // --tree-energy: the octree's energies at theta_, with the --quadrupole term if the run has it
   double softening_;               // --softening: the energies of the softened dynamics
+  bool neighbours_;                // --save-neighbours: phi, nn, nnd2 of every recorded frame, softening_ the potential's length
   double theta_;
   std::uint32_t nbodies_, nsteps_;
-  std::ofstream pos_file_, energy_file_;
+  std::ofstream pos_file_, energy_file_, neighbours_file_;
+  std::vector<T> phi_, nnd2_;
+  std::vector<std::uint32_t> nn_;
 };
 
 }  // namespace nb
