@@ -13,9 +13,10 @@
 // The rounding order of a body's sums (slices of a tile by wave, tiles in order, waves in order, chunks in order) follows from sz
 // alone: hermite_plan_for reads nothing else — not the device, not the CU count — so two runs, an eager step and a replayed one, and
 // a handle destroyed and made again give the same bits.  No atomics on a or the jerk, no waiting between blocks.
-// Block (individual) time steps on the same handle: hermite_block.inc, included below.  The plan, the record, the pair kernel's body
-// (hermite_tile_sum with G = 2) and the host-side checks are hermite_tile.hpp's, shared with the sixth-order integrator.
-#include "hermite_tile.hpp"
+// Block (individual) time steps on the same handle: hermite_block.inc, included below (the schedule: block_schedule.hpp).  The plan,
+// the record, the pair kernel's body (hermite_tile_sum with G = 2) and the host-side checks are hermite_tile.hpp's, shared with the
+// sixth-order integrator, as is hermite_block_common.hpp, through which both come in.
+#include "hermite_block_common.hpp"
 
 namespace nbody {
 
@@ -94,20 +95,7 @@ using namespace nbody;
 
 struct nbody_hermite : hermite_handle {  // started: nbody_hermite_force_jerk has run
   void* jerk = nullptr;  // T[n][D]
-  // block time steps (hermite_block.inc): allocated by the first nbody_hermite_block_start
-  int32_t* blev    = nullptr;  // level l_i, [n]
-  uint32_t* btau   = nullptr;  // last update time tau_i in ticks, [n]
-  uint32_t* bact   = nullptr;  // active list of the block step in flight, ascending, [n]
-  uint32_t* bcount = nullptr;  // active bodies per schedule strip, then its exclusive scan, [bstrips]
-  uint32_t* bsched = nullptr;  // {running minimum, n_act, tau_next, -}
-  uint32_t* bpin   = nullptr;  // pinned, mapped host memory: {n_act, tau_next}, written by the schedule
-  uint32_t* bpin_dev = nullptr;  // its device address
-  void* bpart      = nullptr;  // T[bslots][2 D]: partial sums of the active set, sized for the worst n_act
-  uint32_t bstrips = 0, blast = 0;  // blast: n_act of the last block step
-  uint64_t bslots  = 0;
-  int blevels      = 0;      // max_level of the last block_start
-  double bdt       = 0.0;    // its s->dt
-  bool block_on    = false;  // nbody_hermite_block_start has run and no nbody_hermite_force_jerk since
+  hermite_block blk;  // block time steps (hermite_block.inc): allocated by the first nbody_hermite_block_start
 };
 
 namespace nbody {
@@ -146,7 +134,7 @@ static int hermite_call(nbody_hermite* h, const nbody_state* s, double eps, void
     const int r = h->plan.R == 2 ? hermite_launch<T, D, 2, START>(h, s, e2, as_stream(stream))
                                  : hermite_launch<T, D, 1, START>(h, s, e2, as_stream(stream));
     if (START && r == NBODY_OK) h->started = true;
-    if (START) h->block_on = false;  // levels and tau belong to the state nbody_hermite_block_start saw
+    if (START) h->blk.block_on = false;  // levels and tau belong to the state nbody_hermite_block_start saw
     return r;
   });
 }
@@ -181,7 +169,7 @@ extern "C" void nbody_hermite_destroy(nbody_hermite* h) {
   (void)hipFree(h->recs);
   (void)hipFree(h->part);
   (void)hipFree(h->jerk);
-  hermite_block_free(h);
+  hermite_block_free(&h->blk);
   delete h;
 }
 

@@ -16,7 +16,7 @@
 // a handle destroyed and made again give the same bits.  No atomics on a, the jerk or the snap, no waiting between blocks.
 // The plan (hermite_plan_for with at least two chunks), the record, the pair kernel's body (hermite_tile_sum with G = 3) and the
 // host-side checks are hermite_tile.hpp's, shared with the fourth-order integrator.
-#include "hermite_tile.hpp"
+#include "hermite_block_common.hpp"
 
 namespace nbody {
 
@@ -121,20 +121,7 @@ struct nbody_hermite6 : hermite_handle {  // started: nbody_hermite6_start has r
   void* jerk    = nullptr;  // T[n][D]
   void* snap    = nullptr;  // T[n][D]
   void* crackle = nullptr;  // T[n][D]
-  // block time steps (hermite6_block.inc): allocated by the first nbody_hermite6_block_start
-  int32_t* blev    = nullptr;  // level l_i, [n]
-  uint32_t* btau   = nullptr;  // last update time tau_i in ticks, [n]
-  uint32_t* bact   = nullptr;  // active list of the block step in flight, ascending, [n]
-  uint32_t* bcount = nullptr;  // active bodies per schedule strip, then its exclusive scan, [bstrips]
-  uint32_t* bsched = nullptr;  // {running minimum, n_act, tau_next, -}
-  uint32_t* bpin   = nullptr;  // pinned, mapped host memory: {n_act, tau_next}, written by the schedule
-  uint32_t* bpin_dev = nullptr;  // its device address
-  void* bpart      = nullptr;  // T[bslots][3 D]: partial sums of the active set, sized for the worst n_act
-  uint32_t bstrips = 0, blast = 0;  // blast: n_act of the last block step
-  uint64_t bslots  = 0;
-  int blevels      = 0;      // max_level of the last block_start
-  double bdt       = 0.0;    // its s->dt
-  bool block_on    = false;  // nbody_hermite6_block_start has run and no nbody_hermite6_start since
+  hermite_block blk;  // block time steps (hermite6_block.inc): allocated by the first nbody_hermite6_block_start
 };
 
 namespace nbody {
@@ -178,7 +165,7 @@ static int hermite6_call(nbody_hermite6* h, const nbody_state* s, double eps, vo
       if (r == NBODY_OK)
         r = h->plan.R == 2 ? hermite6_launch<T, D, 2, kH6Start>(h, s, e2, st) : hermite6_launch<T, D, 1, kH6Start>(h, s, e2, st);
       if (r == NBODY_OK) h->started = true;
-      h->block_on = false;  // levels and tau belong to the state nbody_hermite6_block_start saw
+      h->blk.block_on = false;  // levels and tau belong to the state nbody_hermite6_block_start saw
     } else {
       r = h->plan.R == 2 ? hermite6_launch<T, D, 2, kH6Step>(h, s, e2, st) : hermite6_launch<T, D, 1, kH6Step>(h, s, e2, st);
     }
@@ -222,7 +209,7 @@ extern "C" void nbody_hermite6_destroy(nbody_hermite6* h) {
   (void)hipFree(h->jerk);
   (void)hipFree(h->snap);
   (void)hipFree(h->crackle);
-  hermite6_block_free(h);
+  hermite_block_free(&h->blk);
   delete h;
 }
 

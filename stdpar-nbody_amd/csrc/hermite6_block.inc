@@ -4,180 +4,16 @@
 // force, which lies below float's rounding of the sums (DESIGN.md §7), so no float kernel is instantiated here.
 //
 // One block step is seven or eight launches on the caller's stream and one 8-byte read-back, as in hermite_block.inc:
-//   schedule   min, count, scan, compact: hermite_block.inc's four kernels, copied under the names hermite6_sched_* (the originals are
-//              non-template __global__ functions of another translation unit);
+//   schedule   min, count, scan, compact: block_schedule.hpp's four kernels over the body order;
 //   predict    ALL bodies to tau_next, h_i = T(tau_next - tau_i) * tick, the 12-value record of hermite6_predict_kernel;
 //   force+jerk+snap  the active targets, gathered through the list, against all N records: hermite_tile_sum<T, D, R, 3, true>, launched
-//              in the shape of hermite6_block_plan_for(sz, n_act);
-//   reduce     only where the active set is cut into more than kH6SerialChunks chunks: one wave per (slot, row) adds the chunks' sums,
-//              each lane a run of consecutive chunks in chunk order, the runs in lane order;
+//              in the shape of hermite_block_plan_for(sz, n_act, 2);
+//   reduce     only where the active set is cut into more than kSerialChunks chunks: hermite_block_reduce_kernel
+//              (hermite_block_common.hpp);
 //   correct    one lane per active body: chunk sums in chunk order, the corrector and the crackle with h = step_i * tick, the new level.
 // `scan` writes (n_act, tau_next) into pinned host memory; the host synchronises after `predict` and sizes the last launches from it.
-#include "hermite6_block_plan.hpp"
 
 namespace nbody {
-
-constexpr int kS6Items      = 16;                   // rows of kHBlock bodies per schedule strip
-constexpr uint32_t kS6Strip = kHBlock * kS6Items;   // 4096 bodies per schedule block
-constexpr uint32_t kS6NoTime = 0xffffffffu;
-
-// sched[0]: the running minimum (kS6NoTime between steps), sched[1]: n_act, sched[2]: tau_next of the step in flight
-enum { kS6Min = 0, kS6Count = 1, kS6Next = 2, kS6Words = 4 };
-
-__device__ __forceinline__ uint32_t h6_step_of(int32_t lev, int32_t L) { return 1u << (L - lev); }
-
-// ---- schedule ------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kHBlock) void hermite6_sched_min_kernel(const int32_t* __restrict__ lev, const uint32_t* __restrict__ tau,
-                                                                     uint32_t* __restrict__ sched, uint32_t n, int32_t L) {
-  __shared__ uint32_t wmin[kHWaves];
-  uint32_t mn = kS6NoTime;
-#pragma unroll
-  for (int k = 0; k < kS6Items; ++k) {
-    const uint32_t i = blockIdx.x * kS6Strip + k * kHBlock + threadIdx.x;
-    if (i < n) {
-      const uint32_t due = tau[i] + h6_step_of(lev[i], L);
-      mn                 = due < mn ? due : mn;
-    }
-  }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const uint32_t o = __shfl_xor(mn, off);
-    mn               = o < mn ? o : mn;
-  }
-  if ((threadIdx.x & 63) == 0) wmin[threadIdx.x >> 6] = mn;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int w = 1; w < kHWaves; ++w) mn = wmin[w] < mn ? wmin[w] : mn;
-    atomicMin(&sched[kS6Min], mn);
-  }
-}
-
-// the strip's rows one after the other, a ballot per wave: cnt[row * kHWaves + wave]
-__device__ __forceinline__ bool h6_sched_active(const int32_t* lev, const uint32_t* tau, uint32_t i, uint32_t n, int32_t L, uint32_t next) {
-  return i < n && tau[i] + h6_step_of(lev[i], L) == next;
-}
-
-__global__ __launch_bounds__(kHBlock) void hermite6_sched_count_kernel(const int32_t* __restrict__ lev, const uint32_t* __restrict__ tau,
-                                                                       const uint32_t* __restrict__ sched, uint32_t* __restrict__ bcount,
-                                                                       uint32_t n, int32_t L) {
-  __shared__ uint32_t wcnt[kHWaves];
-  const uint32_t next = sched[kS6Min];
-  uint32_t c          = 0;
-#pragma unroll
-  for (int k = 0; k < kS6Items; ++k) {
-    const uint32_t i = blockIdx.x * kS6Strip + k * kHBlock + threadIdx.x;
-    c += uint32_t(__popcll(__ballot(h6_sched_active(lev, tau, i, n, L, next))));
-  }
-  if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int w = 1; w < kHWaves; ++w) c += wcnt[w];
-    bcount[blockIdx.x] = c;
-  }
-}
-
-// inclusive scan over the 64 lanes of a wave
-__device__ __forceinline__ uint32_t h6_wave_inclusive_scan(uint32_t v, int lane) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t o = __shfl_up(v, off);
-    if (lane >= off) v += o;
-  }
-  return v;
-}
-
-// one block: bcount[0 .. nb) -> its exclusive scan in place, the total to sched[kS6Count] (and the host); tau_next moves to sched[kS6Next]
-// and the running minimum is re-armed for the next step (every reader of sched[kS6Min] of this step has finished: stream order)
-__global__ __launch_bounds__(kHBlock) void hermite6_sched_scan_kernel(uint32_t* __restrict__ bcount, uint32_t* __restrict__ sched,
-                                                                      uint32_t* __restrict__ host_pair, uint32_t nb) {
-  __shared__ uint32_t wsum[kHWaves];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t running = 0;
-  for (uint32_t base = 0; base < nb; base += kHBlock) {
-    const uint32_t j   = base + threadIdx.x;
-    const uint32_t v   = j < nb ? bcount[j] : 0u;
-    const uint32_t inc = h6_wave_inclusive_scan(v, lane);
-    __syncthreads();  // the previous round's wsum has been read
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    uint32_t before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kHWaves; ++w) {
-      if (w < wave) before += wsum[w];
-      total += wsum[w];
-    }
-    if (j < nb) bcount[j] = running + before + inc - v;
-    running += total;
-  }
-  if (threadIdx.x == 0) {
-    const uint32_t next = sched[kS6Min];
-    sched[kS6Count]     = running;
-    sched[kS6Next]      = next;
-    sched[kS6Min]       = kS6NoTime;
-    host_pair[0]        = running;  // pinned host memory: read by the host after it has synchronised with the stream
-    host_pair[1]        = next;
-  }
-}
-
-__global__ __launch_bounds__(kHBlock) void hermite6_sched_compact_kernel(const int32_t* __restrict__ lev, const uint32_t* __restrict__ tau,
-                                                                         const uint32_t* __restrict__ sched, const uint32_t* __restrict__ boff,
-                                                                         uint32_t* __restrict__ act, uint32_t n, int32_t L) {
-  __shared__ uint32_t cnt[kS6Items * kHWaves];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint32_t next = sched[kS6Next];
-  uint64_t ballot[kS6Items];
-#pragma unroll
-  for (int k = 0; k < kS6Items; ++k) {
-    const uint32_t i = blockIdx.x * kS6Strip + k * kHBlock + threadIdx.x;
-    ballot[k]        = __ballot(h6_sched_active(lev, tau, i, n, L, next));
-    if (lane == 0) cnt[k * kHWaves + wave] = uint32_t(__popcll(ballot[k]));
-  }
-  __syncthreads();
-  if (wave == 0) {  // exclusive scan of the 64 (row, wave) counts, in body order
-    const uint32_t v = cnt[lane];
-    cnt[lane]        = h6_wave_inclusive_scan(v, lane) - v;
-  }
-  __syncthreads();
-  const uint32_t base = boff[blockIdx.x];
-  const uint64_t below = (1ull << lane) - 1ull;
-#pragma unroll
-  for (int k = 0; k < kS6Items; ++k) {
-    if ((ballot[k] >> lane) & 1ull) {
-      const uint32_t slot = base + cnt[k * kHWaves + wave] + uint32_t(__popcll(ballot[k] & below));
-      if (slot < n) act[slot] = blockIdx.x * kS6Strip + k * kHBlock + threadIdx.x;  // slot < n always: n_act <= n
-    }
-  }
-}
-
-// ---- start: the first levels -----------------------------------------------------------------------------------------------------
-// want = eta_start |a| / |j| (|j| = 0: level 0); the smallest level whose step dtmax 2^-l is <= want, at most L.  tau = 0.
-template <typename T, int D>
-__global__ __launch_bounds__(kHBlock) void hermite6_block_init_kernel(const T* __restrict__ a, const T* __restrict__ jerk,
-                                                                      int32_t* __restrict__ lev, uint32_t* __restrict__ tau, T eta_start,
-                                                                      T dtmax, uint32_t n, int32_t L) {
-  const uint32_t i = blockIdx.x * kHBlock + threadIdx.x;
-  if (i >= n) return;
-  T a2 = T(0), j2 = T(0);
-#pragma unroll
-  for (int k = 0; k < D; ++k) {
-    const T ak = a[uint64_t(i) * D + k], jk = jerk[uint64_t(i) * D + k];
-    a2 = __builtin_elementwise_fma(ak, ak, a2);
-    j2 = __builtin_elementwise_fma(jk, jk, j2);
-  }
-  int32_t l = 0;
-  if (j2 > T(0)) {
-    const T want = eta_start * __builtin_elementwise_sqrt(a2) / __builtin_elementwise_sqrt(j2);
-    T hs         = dtmax;
-    while (l < L && hs > want) {
-      hs *= T(0.5);
-      ++l;
-    }
-  }
-  lev[i] = l;
-  tau[i] = 0u;
-}
 
 // ---- predict with per-body h -------------------------------------------------------------------------------------------------------
 // hermite6_predict_kernel's three Horner chains with h_i = T(tau_next - tau_i) * tick in place of h; the same record, the same padding.
@@ -193,7 +29,7 @@ __global__ __launch_bounds__(kHBlock) void hermite6_block_predict_kernel(const T
 #pragma unroll
   for (int k = 0; k < kH6Rec; ++k) r[k] = T(0);
   if (i < n) {
-    const T h = T(sched[kS6Next] - tau[i]) * tick;
+    const T h = T(sched[kSchedNext] - tau[i]) * tick;
     r[3]      = m[i];
 #pragma unroll
     for (int k = 0; k < D; ++k) {
@@ -218,36 +54,15 @@ __global__ __launch_bounds__(kHBlock) void hermite6_block_active_kernel(const T*
   hermite_tile_sum<T, D, R, 3, true>(flat, part, e2, n_act, ntiles, tiles_per_chunk, act);
 }
 
-// ---- chunk sums of a small active set ----------------------------------------------------------------------------------------------
-// part [chunk][rows][n_act] -> out [rows][n_act], rows = 3 D.  One wave per (row, slot): lane l adds the chunks [l per_lane, (l + 1)
-// per_lane) in chunk order, then the lanes' sums are added in lane order.  The order follows from `chunks` alone.
-template <typename T>
-__global__ __launch_bounds__(kHBlock) void hermite6_block_reduce_kernel(const T* __restrict__ part, T* __restrict__ out, uint32_t n_act,
-                                                                        uint32_t rows, uint32_t chunks, uint32_t per_lane) {
-  const uint32_t w = blockIdx.x * kHWaves + (threadIdx.x >> 6);  // wave-uniform
-  if (w >= rows * n_act) return;
-  const uint32_t lane = threadIdx.x & 63, row = w / n_act, s = w - row * n_act;
-  const uint32_t c0 = lane * per_lane, c1 = c0 + per_lane < chunks ? c0 + per_lane : chunks;
-  T sum = T(0);
-  if (c0 < chunks) {
-    sum = part[(uint64_t(c0) * rows + row) * n_act + s];
-    for (uint32_t ch = c0 + 1; ch < c1; ++ch) sum += part[(uint64_t(ch) * rows + row) * n_act + s];
-  }
-  const uint32_t runs = (chunks + per_lane - 1u) / per_lane;  // <= 64
-  T total             = __shfl(sum, 0);
-  for (uint32_t l = 1; l < runs; ++l) total += __shfl(sum, int(l));
-  if (lane == 0) out[uint64_t(row) * n_act + s] = total;
-}
-
 // ---- correct + crackle + new level ---------------------------------------------------------------------------------------------------
 // hermite6_correct_kernel's corrector and crackle with h = step_i * tick, then the derivatives at the new time of the quintic through
 // (a0, j0, s0) at 0 and (a1, j1, s1) at h:
 //   a3 = k1,   a4 = (360 (a1 - a0) - h (168 j0 + 192 j1) + h^2 (36 s1 - 24 s0)) / h^4,
 //   a5 = (720 (a1 - a0) - 360 h (j0 + j1) + 60 h^2 (s1 - s0)) / h^5
 //   want = eta ((|a1| |s1| + |j1|^2) / (|a3| |a5| + |a4|^2))^(1/6)                                         (denominator 0: no limit)
-// 1 / h = idt 2^l and 1 / h^3 = ih3_0 2^(3 l) are exact scalings of the host's idt = 1 / T(dtmax) and ih3_0 = 1 / (dtmax dtmax dtmax)
-// (the latter as hermite6_launch makes its ih3); the candidate steps h / 2, h / 4, ... are exact too.  One lane per active body, a
-// few hundred at most of them per pair sum over N sources: the division and the cube root cost nothing that shows.
+// and block_next_level.  1 / h = idt 2^l and 1 / h^3 = ih3_0 2^(3 l) are exact scalings of the host's idt = 1 / T(dtmax) and
+// ih3_0 = 1 / (dtmax dtmax dtmax) (the latter as hermite6_launch makes its ih3).  One lane per active body, a few hundred at most of
+// them per pair sum over N sources: the division and the cube root cost nothing that shows.
 template <typename T, int D>
 __global__ __launch_bounds__(kHBlock) void hermite6_block_correct_kernel(const T* __restrict__ part, const uint32_t* __restrict__ act,
                                                                          const uint32_t* __restrict__ sched, T* __restrict__ x, T* __restrict__ v,
@@ -258,9 +73,9 @@ __global__ __launch_bounds__(kHBlock) void hermite6_block_correct_kernel(const T
   const uint32_t s = blockIdx.x * kHBlock + threadIdx.x;
   if (s >= n_act) return;
   const uint32_t i     = act[s];
-  const uint32_t next  = sched[kS6Next];
+  const uint32_t next  = sched[kSchedNext];
   const int32_t l      = lev[i];
-  const uint32_t step  = h6_step_of(l, L);
+  const uint32_t step  = step_of(l, L);
   const T h = T(step) * tick, ih = idt * T(1u << l), ih3 = ih3_0 * T(1ull << (3 * l)), ih4 = ih3 * ih, ih5 = ih4 * ih;
   const T hh = T(0.5) * h, h2 = h * h, h10 = h2 * T(0.1), h120 = (h2 * h) * T(1.0 / 120.0);
   T n_a1 = T(0), n_j1 = T(0), n_s1 = T(0), n_a3 = T(0), n_a4 = T(0), n_a5 = T(0);
@@ -294,61 +109,12 @@ __global__ __launch_bounds__(kHBlock) void hermite6_block_correct_kernel(const T
   // |j1|^2 and |a4|^2 are the sums themselves
   const T num = __builtin_elementwise_fma(__builtin_elementwise_sqrt(n_a1), __builtin_elementwise_sqrt(n_s1), n_j1);
   const T den = __builtin_elementwise_fma(__builtin_elementwise_sqrt(n_a3), __builtin_elementwise_sqrt(n_a5), n_a4);
-  int32_t nl  = l;
-  if (den > T(0)) {
-    const T want = eta * cbrt(__builtin_elementwise_sqrt(num / den));
-    if (want < h) {  // the smallest level deeper than l whose step is <= want, at most L
-      T hs = hh;
-      nl   = l + 1;
-      while (nl < L && hs > want) {
-        hs *= T(0.5);
-        ++nl;
-      }
-      if (nl > L) nl = L;
-    } else if (want >= T(2) * h && l > 0 && (next & (2u * step - 1u)) == 0u) {
-      nl = l - 1;  // one doubling at most, and only onto the coarser level's grid
-    }
-  } else if (l > 0 && (next & (2u * step - 1u)) == 0u) {
-    nl = l - 1;  // no limit
-  }
-  lev[i] = nl;
+  lev[i] = den > T(0) ? block_next_level(eta * cbrt(__builtin_elementwise_sqrt(num / den)), true, h, l, L, step, next)
+                      : block_next_level(T(0), false, h, l, L, step, next);
   tau[i] = next == (1u << L) ? 0u : next;
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------
-inline void hermite6_block_free(nbody_hermite6* h) {
-  (void)hipFree(h->blev);
-  (void)hipFree(h->btau);
-  (void)hipFree(h->bact);
-  (void)hipFree(h->bcount);
-  (void)hipFree(h->bsched);
-  (void)hipFree(h->bpart);
-  if (h->bpin) (void)hipHostFree(h->bpin);
-  h->blev = nullptr;
-  h->btau = h->bact = h->bcount = h->bsched = h->bpin = h->bpin_dev = nullptr;
-  h->bpart = nullptr;
-}
-
-static int hermite6_block_alloc(nbody_hermite6* h) {
-  if (h->bpin) return NBODY_OK;
-  const size_t n  = h->n;
-  h->bstrips      = uint32_t((n + kS6Strip - 1) / kS6Strip);
-  h->bslots       = hermite6_block_part_slots(h->n);
-  hipError_t e    = hipMalloc(reinterpret_cast<void**>(&h->blev), sizeof(int32_t) * n);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->btau), sizeof(uint32_t) * n);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->bact), sizeof(uint32_t) * n);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->bcount), sizeof(uint32_t) * h->bstrips);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->bsched), sizeof(uint32_t) * kS6Words);
-  if (e == hipSuccess) e = hipMalloc(&h->bpart, h->tsz * 3 * size_t(h->dim) * size_t(h->bslots));
-  if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&h->bpin), sizeof(uint32_t) * 2, hipHostMallocMapped);
-  if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&h->bpin_dev), h->bpin, 0);
-  if (e != hipSuccess) {
-    hermite6_block_free(h);
-    return hip_fail(e, "nbody_hermite6_block_start allocation", __FILE__, __LINE__);
-  }
-  return NBODY_OK;
-}
-
 struct h6_block_consts {  // double: the only type the block steps are provided in
   double e2, eta, tick, dtmax, idt, ih3_0;
 };
@@ -366,7 +132,7 @@ static int hermite6_block_check(nbody_hermite6* h, const nbody_state* s, double 
   NB_ARG(h->dtype == s->dtype && h->dim == s->dim && h->n == s->sz,
          "nbody_hermite6 was created for (dtype %d, dim %d, n %u), the state is (dtype %d, dim %d, sz %u)", h->dtype, h->dim, h->n,
          s->dtype, s->dim, s->sz);
-  const int L = is_start ? max_level : h->blevels;
+  const int L = is_start ? max_level : h->blk.sched.levels;
   out->eta    = eta;
   out->dtmax  = s->dt;
   out->tick   = out->dtmax;
@@ -384,11 +150,12 @@ static int hermite6_block_check(nbody_hermite6* h, const nbody_state* s, double 
     return NBODY_ERR_STATE;
   }
   if (!is_start) {
-    if (!h->block_on) {
+    if (!h->blk.block_on) {
       set_error("%s before nbody_hermite6_block_start on this handle (or after a later nbody_hermite6_start)", who);
       return NBODY_ERR_STATE;
     }
-    NB_ARG(s->dt == h->bdt, "%s: the state's dt = %g is not the dt = %g nbody_hermite6_block_start was called with", who, s->dt, h->bdt);
+    NB_ARG(s->dt == h->blk.sched.dt, "%s: the state's dt = %g is not the dt = %g nbody_hermite6_block_start was called with", who, s->dt,
+           h->blk.sched.dt);
   }
   return NBODY_OK;
 }
@@ -396,22 +163,21 @@ static int hermite6_block_check(nbody_hermite6* h, const nbody_state* s, double 
 template <int D>
 static int hermite6_block_start_launch(nbody_hermite6* h, const nbody_state* s, const h6_block_consts& bc, double eta_start, int L,
                                        hipStream_t st) {
-  using T = double;
-  if (int r = hermite6_block_alloc(h)) return r;
-  h->block_on = false;
+  using T          = double;
+  hermite_block& b = h->blk;
+  if (int r = hermite_block_alloc(&b, h, 3, 2, "nbody_hermite6_block_start allocation")) return r;
+  b.block_on = false;
   int r = h->plan.R == 2 ? hermite6_launch<T, D, 2, kH6StartA>(h, s, bc.e2, st) : hermite6_launch<T, D, 1, kH6StartA>(h, s, bc.e2, st);
   if (r == NBODY_OK)
     r = h->plan.R == 2 ? hermite6_launch<T, D, 2, kH6Start>(h, s, bc.e2, st) : hermite6_launch<T, D, 1, kH6Start>(h, s, bc.e2, st);
   if (r != NBODY_OK) return r;
   h->started = true;
-  hipLaunchKernelGGL((hermite6_block_init_kernel<T, D>), dim3((h->n + kHBlock - 1) / kHBlock), dim3(kHBlock), 0, st,
-                     static_cast<const T*>(s->a), static_cast<const T*>(h->jerk), h->blev, h->btau, eta_start, bc.dtmax, h->n, int32_t(L));
+  hipLaunchKernelGGL((hermite_block_init_kernel<T, D>), dim3((h->n + kHBlock - 1) / kHBlock), dim3(kHBlock), 0, st,
+                     static_cast<const T*>(s->a), static_cast<const T*>(h->jerk), b.sched.lev, b.sched.tau, eta_start, bc.dtmax, h->n,
+                     int32_t(L));
   NB_HIP(hipGetLastError());
-  NB_HIP(hipMemsetAsync(h->bsched, 0xff, sizeof(uint32_t) * kS6Words, st));
-  h->blevels  = L;
-  h->bdt      = s->dt;
-  h->blast    = 0;
-  h->block_on = true;
+  if (int r2 = block_schedule_start(&b.sched, L, s->dt, st)) return r2;
+  b.block_on = true;
   return NBODY_OK;
 }
 
@@ -419,55 +185,45 @@ static int hermite6_block_start_launch(nbody_hermite6* h, const nbody_state* s, 
 template <int D>
 static int hermite6_block_step_launch(nbody_hermite6* h, const nbody_state* s, const h6_block_consts& bc, hipStream_t st, uint32_t* n_active,
                                       uint32_t* tau_next) {
-  using T = double;
-  const int32_t L  = h->blevels;
-  const uint32_t n = h->n;
+  using T            = double;
+  hermite_block& b   = h->blk;
+  block_schedule& sc = b.sched;
+  const int32_t L    = sc.levels;
+  const uint32_t n   = h->n;
   T *jerk = static_cast<T*>(h->jerk), *snap = static_cast<T*>(h->snap), *crackle = static_cast<T*>(h->crackle);
   T* recs = static_cast<T*>(h->recs);
-  T* part = static_cast<T*>(h->bpart);
-  hipLaunchKernelGGL(hermite6_sched_min_kernel, dim3(h->bstrips), dim3(kHBlock), 0, st, h->blev, h->btau, h->bsched, n, L);
-  NB_HIP(hipGetLastError());
-  hipLaunchKernelGGL(hermite6_sched_count_kernel, dim3(h->bstrips), dim3(kHBlock), 0, st, h->blev, h->btau, h->bsched, h->bcount, n, L);
-  NB_HIP(hipGetLastError());
-  hipLaunchKernelGGL(hermite6_sched_scan_kernel, dim3(1), dim3(kHBlock), 0, st, h->bcount, h->bsched, h->bpin_dev, h->bstrips);
-  NB_HIP(hipGetLastError());
-  hipLaunchKernelGGL(hermite6_sched_compact_kernel, dim3(h->bstrips), dim3(kHBlock), 0, st, h->blev, h->btau, h->bsched, h->bcount, h->bact, n, L);
-  NB_HIP(hipGetLastError());
+  T* part = static_cast<T*>(b.bpart);
+  if (int r = block_schedule_active(&sc, st)) return r;
   hipLaunchKernelGGL((hermite6_block_predict_kernel<T, D>), dim3(h->padded / kHBlock), dim3(kHBlock), 0, st, static_cast<const T*>(s->m),
-                     static_cast<const T*>(s->x), static_cast<const T*>(s->v), static_cast<const T*>(s->a), jerk, snap, crackle, h->btau,
-                     h->bsched, recs, bc.tick, n, h->padded);
+                     static_cast<const T*>(s->x), static_cast<const T*>(s->v), static_cast<const T*>(s->a), jerk, snap, crackle, sc.tau,
+                     sc.sched, recs, bc.tick, n, h->padded);
   NB_HIP(hipGetLastError());
   NB_HIP(hipStreamSynchronize(st));
-  const uint32_t n_act = h->bpin[0], next = h->bpin[1];
-  const hermite_plan p = hermite6_block_plan_for(n, n_act ? n_act : 1u);
-  const bool reduce    = p.chunks > kH6SerialChunks;
-  if (n_act < 1u || n_act > n || next < 1u || next > (1u << L) || uint64_t(p.chunks) * n_act + (reduce ? n_act : 0u) > h->bslots) {
-    h->block_on = false;
-    set_error("nbody_hermite6_block_step: the schedule on the device is not one of this handle (n_act = %u of %u, tau_next = %u of %u): "
-              "were x, v, a rewritten without nbody_hermite6_block_start?", n_act, n, next, 1u << L);
-    return NBODY_ERR_STATE;
-  }
+  uint32_t n_act, next;
+  hermite_plan p;
+  bool reduce;
+  if (int r = hermite_block_shape(&b, "nbody_hermite6", 2, &n_act, &next, &p, &reduce)) return r;
   if (p.R == 2)
     hipLaunchKernelGGL((hermite6_block_active_kernel<T, D, 2>), dim3(p.blocks, p.chunks), dim3(kHBlock), 0, st, recs, part, bc.e2, n_act,
-                       p.ntiles, p.tiles_per_chunk, h->bact);
+                       p.ntiles, p.tiles_per_chunk, sc.act);
   else
     hipLaunchKernelGGL((hermite6_block_active_kernel<T, D, 1>), dim3(p.blocks, p.chunks), dim3(kHBlock), 0, st, recs, part, bc.e2, n_act,
-                       p.ntiles, p.tiles_per_chunk, h->bact);
+                       p.ntiles, p.tiles_per_chunk, sc.act);
   NB_HIP(hipGetLastError());
   uint32_t chunks = p.chunks;
   if (reduce) {
     T* out = part + uint64_t(p.chunks) * (3 * D) * n_act;
-    hipLaunchKernelGGL((hermite6_block_reduce_kernel<T>), dim3((3 * D * n_act + kHWaves - 1) / kHWaves), dim3(kHBlock), 0, st, part, out, n_act,
+    hipLaunchKernelGGL((hermite_block_reduce_kernel<T>), dim3((3 * D * n_act + kHWaves - 1) / kHWaves), dim3(kHBlock), 0, st, part, out, n_act,
                        uint32_t(3 * D), p.chunks, (p.chunks + 63u) / 64u);
     NB_HIP(hipGetLastError());
     part   = out;
     chunks = 1;
   }
-  hipLaunchKernelGGL((hermite6_block_correct_kernel<T, D>), dim3((n_act + kHBlock - 1) / kHBlock), dim3(kHBlock), 0, st, part, h->bact,
-                     h->bsched, static_cast<T*>(s->x), static_cast<T*>(s->v), static_cast<T*>(s->a), jerk, snap, crackle, h->blev, h->btau,
+  hipLaunchKernelGGL((hermite6_block_correct_kernel<T, D>), dim3((n_act + kHBlock - 1) / kHBlock), dim3(kHBlock), 0, st, part, sc.act,
+                     sc.sched, static_cast<T*>(s->x), static_cast<T*>(s->v), static_cast<T*>(s->a), jerk, snap, crackle, sc.lev, sc.tau,
                      static_cast<T>(s->c), bc.tick, bc.idt, bc.ih3_0, bc.eta, n_act, chunks, L);
   NB_HIP(hipGetLastError());
-  h->blast  = n_act;
+  sc.last   = n_act;
   *n_active = n_act;
   *tau_next = next;
   return NBODY_OK;
@@ -487,20 +243,8 @@ static int hermite6_block_call(nbody_hermite6* h, const nbody_state* s, double e
   auto run = [&](auto dim_tag) -> int {
     constexpr int D = decltype(dim_tag)::value;
     if (is_start) return hermite6_block_start_launch<D>(h, s, bc, eta, max_level, st);
-    uint32_t na = 0, tn = 0;
-    uint64_t nsteps = 0, nbody = 0;
-    do {
-      if (int r = hermite6_block_step_launch<D>(h, s, bc, st, &na, &tn)) return r;
-      ++nsteps;
-      nbody += na;
-    } while (steps && tn != (1u << h->blevels));
-    if (n_active) *n_active = na;
-    if (tau) *tau = tn;
-    if (steps) {
-      steps[0] = nsteps;
-      steps[1] = nbody;
-    }
-    return int(NBODY_OK);
+    return block_schedule_run(
+        &h->blk.sched, [&](uint32_t* na, uint32_t* tn) { return hermite6_block_step_launch<D>(h, s, bc, st, na, tn); }, n_active, tau, steps);
   };
   return s->dim == 2 ? run(std::integral_constant<int, 2>{}) : run(std::integral_constant<int, 3>{});
 }
@@ -528,24 +272,5 @@ extern "C" int nbody_hermite6_block_advance(nbody_hermite6* h, const nbody_state
 }
 
 extern "C" int nbody_hermite6_block_read(nbody_hermite6* h, int what, void* host_out, size_t bytes, void* stream) {
-  NB_ARG(h != nullptr, "nbody_hermite6 is NULL");
-  NB_ARG(host_out != nullptr, "host_out is NULL");
-  NB_ARG(what >= 0 && what <= 2, "what must be 0 (levels), 1 (tau) or 2 (the active list of the last block step), got %d", what);
-  if (int r = check_same_device(h->device, as_stream(stream), "nbody_hermite6")) return r;
-  device_guard guard(h->device);
-  hipStream_t st = as_stream(stream);
-  if (capture_id(st) != 0) {
-    set_error("nbody_hermite6_block_read is blocking: it cannot be recorded (call it outside nbody_graph_begin/end)");
-    return NBODY_ERR_STATE;
-  }
-  if (!h->block_on) {
-    set_error("nbody_hermite6_block_read before nbody_hermite6_block_start on this handle");
-    return NBODY_ERR_STATE;
-  }
-  const size_t need = 4 * size_t(what == 2 ? h->blast : h->n);
-  NB_ARG(bytes == need, "nbody_hermite6_block_read(what = %d) needs %zu bytes, got %zu", what, need, bytes);
-  const void* src = what == 0 ? static_cast<const void*>(h->blev) : what == 1 ? static_cast<const void*>(h->btau) : h->bact;
-  if (need) NB_HIP(hipMemcpyAsync(host_out, src, need, hipMemcpyDeviceToHost, st));
-  NB_HIP(hipStreamSynchronize(st));
-  return NBODY_OK;
+  return nbody::hermite_block_read(h, h ? &h->blk : nullptr, "nbody_hermite6", what, host_out, bytes, stream);
 }

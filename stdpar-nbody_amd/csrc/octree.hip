@@ -26,6 +26,7 @@
 // Key depth: MAXL = 21 (3D) / 32 (2D) levels; cells that still hold >= 2 bodies there are finished level by level by one
 // thread each (ot_build_deep_kernel), so the tree has the reference's shape at any depth.
 #include "common.hpp"
+#include "block_schedule.hpp"
 #include "radix_sort.hpp"
 #include "to_sgpr.hpp"
 

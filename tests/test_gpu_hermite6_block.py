@@ -2,7 +2,7 @@
 restatement of the scheme in tests/hermite6_block_model.py: np.longdouble for single block steps and single evaluations, float64 for
 runs.  The shapes are those of tests/test_gpu_hermite_block.py.
 
-Launch-shape boundaries of hermite6_block_plan_for(sz, n_act) (csrc/hermite6_block_plan.hpp) crossed below.  Over n_act: the block of 64
+Launch-shape boundaries of hermite_block_plan_for(sz, n_act, 2) (csrc/hermite_block_plan.hpp) crossed below.  Over n_act: the block of 64
 targets (63 / 64 / 65), two targets per lane from 65536 active bodies on (max_level = 0 at 65 537 bodies), and the cut of the source
 tiles over grid.y: ceil(2048 / blocks) chunks, at least two, at most one per tile of 256 sources — at N = 20 000 (79 tiles) 1 .. 365
 active bodies take 79 chunks of one tile (more than 64: the reduce kernel), all 20 000 take 7 chunks of 12 tiles, the fixed step's

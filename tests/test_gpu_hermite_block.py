@@ -2,7 +2,7 @@
 include/nbody_hip.h written here (the reference has no Hermite, so there are no fixtures): np.longdouble for single block steps and
 single evaluations, float64 / float32 for runs.
 
-Launch-shape boundaries of hermite_block_plan_for(sz, n_act) (csrc/hermite_block.inc) crossed below.  Over n_act: the block of 64
+Launch-shape boundaries of hermite_block_plan_for(sz, n_act, 1) (csrc/hermite_block_plan.hpp) crossed below.  Over n_act: the block of 64
 targets (63 / 64 / 65: one block, then two), two targets per lane from 65536 active bodies on (max_level = 0 at 65 536 and 70 001
 bodies, all active), and the cut of the
 source tiles over grid.y, which is ceil(2048 / blocks) chunks capped at one chunk per tile of 256 sources: at N = 20 000 (79 tiles)

@@ -162,13 +162,14 @@ def test_model_with_max_level_0_is_the_fixed_step(dim, n):
 
 
 def test_launch_shape_with_every_body_active_is_the_fixed_steps(tmp_path):
-    """tools/hermite6_block_plan_check.cpp, compiled for the host alone: hermite6_block_plan_for(sz, sz) == hermite_plan_for(sz, 2) for
-    sz in 1 .. 200 000, and the partial sums of any active set fit hermite6_block_part_slots."""
+    """tools/hermite_block_plan_check.cpp, compiled for the host alone: hermite_block_plan_for(sz, sz, 2) == hermite_plan_for(sz, 2) for
+    sz in 1 .. 200 000, and the partial sums of any active set fit hermite_block_part_slots(sz, 2) (and the same for the fourth order,
+    with 1 in place of 2)."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     assert os.path.exists(hipcc), "no hipcc"
-    exe = tmp_path / "hermite6_block_plan_check"
+    exe = tmp_path / "hermite_block_plan_check"
     subprocess.check_call([hipcc, "-std=c++17", "-O1", "--offload-host-only", "-I", os.path.join(ROOT, "stdpar-nbody_amd", "csrc"), "-I",
-                           os.path.join(ROOT, "include"), os.path.join(ROOT, "tools", "hermite6_block_plan_check.cpp"), "-o", str(exe)])
+                           os.path.join(ROOT, "include"), os.path.join(ROOT, "tools", "hermite_block_plan_check.cpp"), "-o", str(exe)])
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and r.stdout.rstrip().endswith("ok"), (r.stdout, r.stderr)
 
@@ -212,18 +213,19 @@ def test_active_set_kernels_neither_spill_nor_divide(nb):
 
 
 def test_schedule_kernels_take_no_order_dependent_atomic(nb):
-    """The only atomic of hermite6_sched_* / hermite6_block_* is the unsigned minimum of tau_next."""
+    """The only atomic of block_sched_* / hermite6_block_* / hermite_block_{init,reduce}_kernel is the unsigned minimum of tau_next
+    (every code object's copy of the shared ones: tests/test_block_schedule.py)."""
     if not os.path.exists(OBJDUMP):
         pytest.skip("llvm-objdump not available")
     sp = _tool("check_smem_pipeline")
-    funcs = {n: c for n, c in sp.functions(sp.disassemble(nb.LIB_PATH)).items() if re.search(r"hermite6_(sched|block)_", n) and c}
-    for kernel in ("hermite6_sched_min_kernel", "hermite6_sched_count_kernel", "hermite6_sched_scan_kernel", "hermite6_sched_compact_kernel",
-                   "hermite6_block_init_kernel", "hermite6_block_predict_kernel", "hermite6_block_reduce_kernel",
+    funcs = {n: c for n, c in sp.functions(sp.disassemble(nb.LIB_PATH)).items() if re.search(r"block_sched_|hermite6_block_|hermite_block_(init|reduce)_", n) and c}
+    for kernel in ("block_sched_min_kernel", "block_sched_count_kernel", "block_sched_scan_kernel", "block_sched_compact_kernel",
+                   "hermite_block_init_kernel", "hermite6_block_predict_kernel", "hermite_block_reduce_kernel",
                    "hermite6_block_correct_kernel"):
         assert any(kernel in n for n in funcs), (kernel, sorted(funcs))
     for name, code in funcs.items():
         atomics = [ins for _, ins, _ in code if "atomic" in ins]
-        if "hermite6_sched_min_kernel" in name:
+        if "block_sched_min_kernel" in name:
             assert atomics and all("atomic_umin" in a for a in atomics), (name, atomics)
         else:
             assert not atomics, (name, atomics)

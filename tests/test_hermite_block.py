@@ -175,11 +175,11 @@ def test_schedule_kernels_take_no_order_dependent_atomic(nb):
     if not os.path.exists(OBJDUMP):
         pytest.skip("llvm-objdump not available")
     sp = _tool("check_smem_pipeline")
-    funcs = {n: c for n, c in sp.functions(sp.disassemble(nb.LIB_PATH)).items() if re.search(r"hermite_(sched|block)_", n) and c}
-    assert any("hermite_sched_compact_kernel" in n for n in funcs) and any("hermite_block_correct_kernel" in n for n in funcs), sorted(funcs)
+    funcs = {n: c for n, c in sp.functions(sp.disassemble(nb.LIB_PATH)).items() if re.search(r"block_sched_|hermite_block_", n) and c}
+    assert any("block_sched_compact_kernel" in n for n in funcs) and any("hermite_block_correct_kernel" in n for n in funcs), sorted(funcs)
     for name, code in funcs.items():
         atomics = [ins for _, ins, _ in code if "atomic" in ins]
-        if "hermite_sched_min_kernel" in name:
+        if "block_sched_min_kernel" in name:
             assert atomics and all("atomic_umin" in a for a in atomics), (name, atomics)
         else:
             assert not atomics, (name, atomics)

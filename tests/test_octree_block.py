@@ -221,23 +221,23 @@ def test_new_kernels_are_built_and_do_not_spill(nb):
     names = kr.demangle([k["symbol"].replace(".kd", "") for k in ks])
     seen = {}
     for k, n in zip(ks, names):
-        m = re.search(r"nbody::(otb_\w+_kernel)(?:<(float|double), (\d)>)?", n)
+        m = re.search(r"nbody::((?:otb|block_sched)_\w+_kernel)(?:<(float|double), (\d)>)?", n)
         if m:
             seen.setdefault(m.group(1), set()).add((m.group(2), m.group(3)))
             assert int(k.get("private_segment_fixed_size", 0)) == 0, (n, k)
     td = {(t, d) for t in ("float", "double") for d in ("2", "3")}
     assert {k: v for k, v in seen.items() if k in ("otb_predict_kernel", "otb_kick_kernel", "otb_init_kernel")} == {
         "otb_predict_kernel": td, "otb_kick_kernel": td, "otb_init_kernel": td}, seen
-    for name in ("otb_sched_min_kernel", "otb_list_count_kernel", "otb_list_scan_kernel", "otb_list_compact_kernel"):
+    for name in ("block_sched_min_kernel", "block_sched_count_kernel", "block_sched_scan_kernel", "block_sched_compact_kernel"):
         assert name in seen, sorted(seen)
     sp = _tool("check_smem_pipeline")
-    funcs = {n: c for n, c in sp.functions(sp.disassemble(nb.LIB_PATH)).items() if "otb_" in n and c}
+    funcs = {n: c for n, c in sp.functions(sp.disassemble(nb.LIB_PATH)).items() if ("otb_" in n or "block_sched_" in n) and c}
     assert len(funcs) >= 16, sorted(funcs)
     for name, code in funcs.items():
         text = "\n".join(ins for _, ins, _ in code)
         assert "scratch_" not in text, name
         atomics = [ins for _, ins, _ in code if "atomic" in ins]
-        if "otb_sched_min_kernel" in name:
+        if "block_sched_min_kernel" in name:
             assert atomics and all("atomic_umin" in a for a in atomics), (name, atomics)
         else:
             assert not atomics, (name, atomics)

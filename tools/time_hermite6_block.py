@@ -144,20 +144,20 @@ def summarize(d):
     f = sorted(glob.glob(d + "/**/*kernel_trace.csv", recursive=True))[0]
     rows = sorted(csv.DictReader(open(f)), key=lambda r: int(r["Start_Timestamp"]))
     name = lambda r: r["Kernel_Name"].split("(")[0].replace("void ", "").replace("nbody::", "").split("<")[0]
-    rows = [r for r in rows if name(r).startswith(("hermite6_sched_", "hermite6_block_"))]
+    rows = [r for r in rows if name(r).startswith(("block_sched_", "hermite6_block_", "hermite_block_"))]
     steps, cur = [], []
     for r in rows:
-        if name(r) == "hermite6_block_init_kernel":
+        if name(r) == "hermite_block_init_kernel":
             cur = []
             continue
         cur.append(r)
         if name(r) == "hermite6_block_correct_kernel":
             steps.append(cur)
             cur = []
-    head = ("hermite6_sched_min_kernel", "hermite6_sched_count_kernel", "hermite6_sched_scan_kernel", "hermite6_sched_compact_kernel",
+    head = ("block_sched_min_kernel", "block_sched_count_kernel", "block_sched_scan_kernel", "block_sched_compact_kernel",
             "hermite6_block_predict_kernel", "hermite6_block_active_kernel")
     classes = collections.defaultdict(list)
-    for s in steps:  # with or without hermite6_block_reduce_kernel in front of the corrector
+    for s in steps:  # with or without hermite_block_reduce_kernel in front of the corrector
         if tuple(name(r) for r in s[:6]) == head and len(s) in (7, 8):
             a = s[5]
             wg = int(a.get("Workgroup_Size_X", 256) or 256)

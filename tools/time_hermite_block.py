@@ -159,7 +159,7 @@ def summarize(d):
     f = sorted(glob.glob(d + "/**/*kernel_trace.csv", recursive=True))[0]
     rows = sorted(csv.DictReader(open(f)), key=lambda r: int(r["Start_Timestamp"]))
     name = lambda r: r["Kernel_Name"].split("(")[0].replace("void ", "").replace("nbody::", "").split("<")[0]
-    rows = [r for r in rows if name(r).startswith(("hermite_sched_", "hermite_block_"))]
+    rows = [r for r in rows if name(r).startswith(("block_sched_", "hermite_block_"))]
     steps, cur = [], []
     for r in rows:
         if name(r) == "hermite_block_init_kernel":
@@ -169,7 +169,7 @@ def summarize(d):
         if name(r) == "hermite_block_correct_kernel":
             steps.append(cur)
             cur = []
-    head = ("hermite_sched_min_kernel", "hermite_sched_count_kernel", "hermite_sched_scan_kernel", "hermite_sched_compact_kernel",
+    head = ("block_sched_min_kernel", "block_sched_count_kernel", "block_sched_scan_kernel", "block_sched_compact_kernel",
             "hermite_block_predict_kernel", "hermite_block_active_kernel")
     classes = collections.defaultdict(list)
     for s in steps:  # with or without hermite_block_reduce_kernel in front of the corrector

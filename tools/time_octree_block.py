@@ -167,8 +167,9 @@ def table_b(nb, quick, trace_n=None):
                   f"{statistics.median(q[1] for q in all_active) * 1e3:10.1f} us", flush=True)
 
 
-PHASES = (("schedule", ("otb_sched_min_kernel",)), ("predict", ("otb_predict_kernel",)), ("walk", ("ot_force_softened_kernel",)),
-          ("kick", ("otb_kick_kernel",)), ("lists", ("otb_list_",)))
+PHASES = (("schedule", ("block_sched_min_kernel",)), ("predict", ("otb_predict_kernel",)), ("walk", ("ot_force_softened_kernel",)),
+          ("kick", ("otb_kick_kernel",)),
+          ("lists", ("block_sched_count_kernel", "block_sched_scan_kernel", "block_sched_compact_kernel")))
 
 
 def summarize(d):
@@ -181,7 +182,7 @@ def summarize(d):
     steps, cur = [], None
     for r in rows:
         nm = name(r)
-        if nm == "otb_sched_min_kernel":
+        if nm == "block_sched_min_kernel":
             cur = []
         if cur is not None:
             cur.append(r)
