@@ -92,7 +92,9 @@ typedef struct nbody_state {
  *      for it, nbody_hermite6_block_start, nbody_hermite6_block_step, nbody_hermite6_block_advance, nbody_hermite6_block_read.
  *      Additive, same version: all-pairs per-body potentials, nearest neighbours and the closest pair, nbody_neighbours_create,
  *      nbody_neighbours_create_on, nbody_neighbours_destroy, nbody_neighbours_compute, nbody_neighbours_read,
- *      nbody_neighbours_closest_pair. */
+ *      nbody_neighbours_closest_pair.  Additive, same version: all-pairs k nearest neighbours, local densities and the density
+ *      centre, nbody_knn_create, nbody_knn_create_on, nbody_knn_destroy, nbody_knn_compute, nbody_knn_read,
+ *      nbody_knn_density_centre. */
 #define NBODY_HIP_ABI_VERSION 2004
 int nbody_abi_version(void);
 
@@ -604,6 +606,55 @@ int  nbody_neighbours_compute(nbody_neighbours* h, const nbody_state* s, double 
 int  nbody_neighbours_read(nbody_neighbours* h, int what, void* host_out, size_t bytes, void* stream);
 /* Blocking.  The closest pair of the last compute: *i < *j and its d2 as one T; any of the three may be NULL. */
 int  nbody_neighbours_closest_pair(nbody_neighbours* h, uint32_t* i, uint32_t* j, void* d2_out, void* stream);
+
+/* ---- all-pairs k nearest neighbours, local densities, the density centre (no reference counterpart) ------------------------------
+ * The Casertano & Hut (1985) diagnostics of a star cluster: each body's local density from its k-th neighbour (conventionally k = 6),
+ * the density centre, the core radius and the core density.  Reads a state's (m, x) and changes nothing in it.  Selection is on the
+ * UNSOFTENED squared distance, so there is no eps: it works after any algorithm or integrator, also unsoftened.  With T the state's
+ * type, D its dimension and d = x_j - x_i:
+ *   d2_ij      exactly the d2 of the neighbours section above (one FMA chain in component order, bitwise symmetric in (i, j)).
+ *   order      the k neighbours of i are the k smallest (d2_ij, j), j != i, in lexicographic order — equal computed d2 resolve to the
+ *              LOWEST index — listed ascending in that order.  The self pair is excluded by index.  A body has min(k, n - 1)
+ *              neighbours; unused slots hold index 0xffffffff and d2 +inf.  Column 0 is nn / nnd2 of nbody_neighbours_compute, bit
+ *              for bit.
+ *   k          fixed at create, 1 <= k <= NBODY_KNN_MAX.  The sweep carries a list of capacity 4, 8 or 16 (the smallest >= k); the
+ *              tie rule is exact, so the first k entries do not depend on the capacity: the k neighbours of a handle made for k are
+ *              the first k of a handle made for any larger k.
+ *   density    rho_i = M_i / V, M_i the masses of neighbours 0 .. k - 2 added in list order (the k-th itself excluded: Casertano &
+ *              Hut's unbiased form), d2_k the k-th squared distance: 3D rho_i = M_i / (T(4 pi / 3) * (d2_k * sqrt(d2_k))), 2D rho_i =
+ *              M_i / (T(pi) * d2_k); correctly rounded sqrt, true divide.  k = 1, or fewer than k neighbours (n <= k): rho_i = 0.
+ *              d2_k = 0 (coincident bodies): what IEEE gives (+inf).
+ *   summary    x_dc = sum rho x / sum rho (the density centre); r_c = sqrt(sum rho^2 |x - x_dc|^2 / sum rho^2) (the core radius, the
+ *              rho^2-weighted NBODY form); rho_c = sum rho^2 / sum rho (the core density).  Summed in double for both types in a
+ *              fixed order, rounded to T.  sum rho = 0 (k = 1, n <= k) or a non-finite rho (coincident bodies) gives NaN by IEEE
+ *              rules: that is not an error.
+ * No atomics, no waiting between blocks, nothing read from the device or the CU count: the cut of the work follows from sz alone.
+ * Two runs give the same bits for every output, and so do an eager call and a replayed recorded one, and a handle destroyed and made
+ * again.
+ *  - create allocates everything (packed records, the chunks' partial lists uint32/T[chunk][n][capacity], the three result arrays,
+ *    the summary record) and frees everything again if one allocation fails; the handle owns the results.  Argument errors in this
+ *    order: out NULL, dtype, dim, n = 0 or n > 2^28, k outside 1 .. NBODY_KNN_MAX (all NBODY_ERR_ARG).  create(_on) between
+ *    nbody_graph_begin and nbody_graph_end: NBODY_ERR_STATE.
+ *  - compute reads s->m and s->x only: s->v, s->a and s->ao may be NULL or garbage.  Asynchronous, allocates nothing, may be recorded
+ *    into a step graph; four launches.  Whole system only (first = 0, count = sz).
+ *  - Argument errors of compute are found before the device is touched, in this order: s NULL; the state's dtype, dim, window,
+ *    tuning; the whole-system rule; h NULL; h made for another dtype, dim or n (all NBODY_ERR_ARG).  Then a stream of another device
+ *    (NBODY_ERR_ARG).
+ *  - read and density_centre are blocking; NBODY_ERR_STATE before the first compute on that handle and between nbody_graph_begin and
+ *    nbody_graph_end (the capture stays usable).  Every entry switches to the handle's device and restores the caller's. */
+#define NBODY_KNN_MAX 16
+typedef struct nbody_knn nbody_knn;
+int  nbody_knn_create(nbody_knn** out, int dtype, int dim, uint32_t n, int k);                /* on the current device */
+int  nbody_knn_create_on(nbody_knn** out, int dtype, int dim, uint32_t n, int k, int device); /* device < 0: the current one */
+void nbody_knn_destroy(nbody_knn* h);                                                         /* NULL: no-op */
+/* The k neighbours, rho of all bodies and the summary at (s->m, s->x), into the handle.  Asynchronous, recordable. */
+int  nbody_knn_compute(nbody_knn* h, const nbody_state* s, void* stream);
+/* Blocking.  what: 0 idx uint32[n][k] | 1 d2 T[n][k] | 2 rho T[n] of the last compute, row-major.  bytes must match (NBODY_ERR_ARG;
+ * what and bytes = 0 are refused before the handle is looked at). */
+int  nbody_knn_read(nbody_knn* h, int what, void* host_out, size_t bytes, void* stream);
+/* Blocking.  The summary of the last compute: centre_out T[dim], the core radius and the core density one T each; any of the three
+ * may be NULL. */
+int  nbody_knn_density_centre(nbody_knn* h, void* centre_out, void* core_radius_out, void* core_density_out, void* stream);
 
 /* ---- owning context (device mirrors of a host System), used by the C++ CLI host ------------------ */
 

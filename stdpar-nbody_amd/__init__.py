@@ -70,6 +70,7 @@ ABI_SYMBOLS = [
     "nbody_hermite6_block_start", "nbody_hermite6_block_step", "nbody_hermite6_block_advance", "nbody_hermite6_block_read",
     "nbody_neighbours_create", "nbody_neighbours_create_on", "nbody_neighbours_destroy", "nbody_neighbours_compute",
     "nbody_neighbours_read", "nbody_neighbours_closest_pair",
+    "nbody_knn_create", "nbody_knn_create_on", "nbody_knn_destroy", "nbody_knn_compute", "nbody_knn_read", "nbody_knn_density_centre",
 ]
 ABI_MAJOR = 2
 COMM_ID_BYTES = 128
@@ -133,6 +134,13 @@ def lib():
         L.nbody_neighbours_compute.argtypes = [vp, vp, d, vp]
         L.nbody_neighbours_read.argtypes = [vp, C.c_int, vp, C.c_size_t, vp]
         L.nbody_neighbours_closest_pair.argtypes = [vp, vp, vp, vp, vp]
+        L.nbody_knn_create.argtypes = [vp, C.c_int, C.c_int, C.c_uint32, C.c_int]
+        L.nbody_knn_create_on.argtypes = [vp, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_int]
+        L.nbody_knn_destroy.restype = None
+        L.nbody_knn_destroy.argtypes = [vp]
+        L.nbody_knn_compute.argtypes = [vp, vp, vp]
+        L.nbody_knn_read.argtypes = [vp, C.c_int, vp, C.c_size_t, vp]
+        L.nbody_knn_density_centre.argtypes = [vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -616,6 +624,46 @@ class Neighbours:
         return i.value, j.value, d2[0]
 
 
+class Knn:
+    """All-pairs k nearest neighbours, local densities and the density centre (nbody_knn_*): owns the packed records, the chunks'
+    partial lists and the results.  k is fixed here, 1 <= k <= 16."""
+
+    def __init__(self, dtype, dim, n, k, device=-1):
+        """device: where the handle's buffers live (-1: the calling thread's current device)."""
+        self.h = C.c_void_p()
+        self.dtype, self.dim, self.n, self.k = dtype, dim, n, k
+        _check(lib().nbody_knn_create_on(C.byref(self.h), dtype, dim, C.c_uint32(n), k, device))
+
+    def close(self):
+        if self.h:
+            lib().nbody_knn_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def compute(self, st, stream=None):
+        """idx, d2, rho and the summary at (st.m, st.x), into the handle.  Asynchronous, recordable."""
+        _check(lib().nbody_knn_compute(self.h, C.byref(st), stream))
+
+    def read(self, what, stream=None):
+        """0 idx (n, k) uint32, 1 d2 (n, k) of T, 2 rho (n,) of T of the last compute (blocking)."""
+        t = np_dtype(self.dtype)
+        out = np.zeros(self.n, t) if what == 2 else np.zeros((self.n, self.k), np.uint32 if what == 0 else t)
+        _check(lib().nbody_knn_read(self.h, what, _p(out), out.nbytes, stream))
+        return out
+
+    def density_centre(self, stream=None):
+        """(x_dc (dim,), r_c, rho_c) of the last compute, of T (blocking).  NaN where sum rho is 0 or a rho is not finite."""
+        t = np_dtype(self.dtype)
+        x, rc, rhoc = np.zeros(self.dim, t), np.zeros(1, t), np.zeros(1, t)
+        _check(lib().nbody_knn_density_centre(self.h, _p(x), _p(rc), _p(rhoc), stream))
+        return x, rc[0], rhoc[0]
+
+
 class OctreeBlock:
     """Block (individual) time steps for the octree leapfrog (nbody_octree_block_*): owns the levels, tau, the active lists, the
     predicted positions and the scratch of the active set's forces; the tree is the caller's Octree."""
@@ -678,6 +726,7 @@ class DeviceSystem:
         self._octree_block = None
         self._hermite6 = None
         self._neighbours = None
+        self._knn = {}
 
     @classmethod
     def from_host(cls, hs, device=0):
@@ -704,6 +753,9 @@ class DeviceSystem:
         if self._neighbours is not None:
             self._neighbours.close()
             self._neighbours = None
+        for h in self._knn.values():
+            h.close()
+        self._knn = {}
         if self.h:
             lib().nbody_destroy(self.h)
             self.h = C.c_void_p()
@@ -903,6 +955,36 @@ class DeviceSystem:
         h = self.neighbours_handle
         h.compute(self.state(), eps, self.stream)
         return h.closest_pair(self.stream)
+
+    # k nearest neighbours, local densities, density centre (no reference counterpart)
+    def knn_handle(self, k):
+        """The Knn handle of this system for k, made at the first use and closed with the system."""
+        if k not in self._knn:
+            self._knn[k] = Knn(self.dtype, self.dim, self.n, k, self.device)
+        return self._knn[k]
+
+    def knn_compute(self, k):
+        """nbody_knn_compute on the state as it is; a StepGraph may record it (the handle for k is made before the recording)."""
+        self.knn_handle(k).compute(self.state(), self.stream)
+
+    def knn(self, k):
+        """(idx (n, k) uint32, d2 (n, k) of T): the k nearest neighbours of every body, ascending in (d2, index), and their unsoftened
+        squared distances; unused slots (n <= k) hold (0xffffffff, +inf) (blocking)."""
+        h = self.knn_handle(k)
+        h.compute(self.state(), self.stream)
+        return h.read(0, self.stream), h.read(1, self.stream)
+
+    def local_density(self, k=6):
+        """rho (n,) of T: Casertano & Hut's local density from the k-th neighbour (blocking)."""
+        h = self.knn_handle(k)
+        h.compute(self.state(), self.stream)
+        return h.read(2, self.stream)
+
+    def density_centre(self, k=6):
+        """(x_dc (dim,), r_c, rho_c): the density centre, core radius and core density from the k-th-neighbour densities (blocking)."""
+        h = self.knn_handle(k)
+        h.compute(self.state(), self.stream)
+        return h.density_centre(self.stream)
 
     def calc_energies(self, softening=0.0):
         """(kinetic, potential) as in System::calc_energies (src/system.h:62-79); blocking.  softening > 0: the potential of the

@@ -1,0 +1,535 @@
+// All-pairs k nearest neighbours, Casertano & Hut (1985) local densities, the density centre, core radius and core density:
+// nbody_knn_* of include/nbody_hip.h.  No reference counterpart.  Reads a state's (m, x), changes nothing in it; selection is on the
+// UNSOFTENED squared distance, so no softening is involved and the call works after any algorithm, also with eps = 0.
+//
+// Definitions (T the state's type, D its dimension, d = x_j - x_i):
+//   d2_ij   exactly the d2 of neighbours.hip: one FMA chain in component order, t = d_0 d_0, then t = fma(d_k, d_k, t).  Bitwise
+//           symmetric in (i, j).
+//   order   the k neighbours of i are the k smallest (d2_ij, j), j != i, in lexicographic order (equal computed d2: the lowest index),
+//           listed ascending in that order.  A body has min(k, n - 1) of them; unused slots hold (0xffffffff, +inf).
+//   K       the capacity of the list a lane carries, the smallest of {4, 8, 16} that is >= k.  The tie rule is exact, so the first k
+//           entries of a list do not depend on K.
+//   rho_i   M_i / (V d_k^D): M_i the masses of neighbours 0 .. k - 2 added in list order (the k-th itself excluded: Casertano & Hut's
+//           unbiased form), 3D: rho = M / (T(4 pi / 3) (d2_k sqrt(d2_k))), 2D: rho = M / (T(pi) d2_k).  Correctly rounded sqrt, true
+//           divide.  k = 1 or fewer than k neighbours (n <= k): rho = 0.  d2_k = 0 (coincident bodies): what IEEE gives (+inf).
+//   summary x_dc = sum rho x / sum rho; r_c = sqrt(sum rho^2 |x - x_dc|^2 / sum rho^2) (the rho^2-weighted NBODY form);
+//           rho_c = sum rho^2 / sum rho.  Accumulated in double for both types, rounded to T at the end.  sum rho = 0 (k = 1, n <= k)
+//           or a non-finite rho (coincident bodies) gives NaN by IEEE rules: not an error.
+//
+// Four launches per compute, all on the caller's stream, nothing allocated after nbody_knn_create:
+//   pack     one lane per record: {x[3], m} (4 T; 2D zero-fills component 2), padded with records at the origin to whole tiles.  A
+//            padding record never becomes a neighbour because of an INDEX BOUND: every slice of 64 records that reaches past n runs
+//            the checked batch body, which replaces the d2 of a record j >= n by +inf.
+//   sweep    the hot path, the shape of neighbours.hip's sweep (hermite_tile.hpp): ONE target per lane (the list alone is 48 VGPRs at
+//            K = 16 in double), records staged through LDS tiles of kHTile and read as wave-uniform broadcasts, every tile cut over
+//            the four waves of the block, the tiles cut over grid.y chunks by knn_plan_for(sz): a function of sz alone.  A lane
+//            carries its target's sorted list (d2[K], idx[K]) in registers; every access is statically indexed in unrolled code.
+//            No transcendental at all.  A batch of U records takes U - 1 v_min and ONE compare of the batch's minimum against the
+//            list's last entry; only if some lane of the wave has a candidate (one ballot, one scalar branch) do the lanes walk the
+//            batch in index order (one more ballot per record skips a record no lane can take) and insert each record with d2
+//            strictly below the last entry by an unrolled compare-and-shift.
+//            Strict `<` keeps the earlier (lower) index among equal values, because a lane meets its sources in ascending index
+//            order.  The result is the same whichever way the branch goes.
+//            Two batch bodies, chosen per slice (wave-uniform): the CHECKED one masks the self pair and the padding (d2 +inf) by
+//            index; every other slice runs the plain body, which has no index test at all.
+//            The block's waves merge through LDS, one wave's lists at a time (12 K bytes per lane), LEXICOGRAPHICALLY on (d2, idx):
+//            a wave's slice of a later tile holds higher indices than another wave's slice of an earlier tile.  The chunk's lists
+//            go to the partial arrays T[chunk][n][K], uint32[chunk][n][K].
+//   finish   one lane per body: the chunks' lists merged by the same rule; writes idx[n][k], d2[n][k] row-major and rho[n].
+//   summary  one block: the sums above, strided per lane, then across the wave and the block in a fixed order — a function of sz
+//            alone, no atomics — into the handle's record.
+// Nothing is read from the device or the CU count, no atomics, no waiting between blocks, and the order has an exact tie rule: two
+// runs, an eager call and a replayed recorded one, and a handle destroyed and made again give the same bits.
+// Bound: FP64 / FP32 VALU issue; per pair D subtractions, D chain operations, (U - 1) / U min + 1 / U compare, and for a batch that
+// takes the branch U insertions of K compares and 2 K selects (3 K v_cndmask in double).
+#include "hermite_tile.hpp"
+
+#pragma clang fp contract(off)
+
+namespace nbody {
+
+constexpr uint32_t kKnnNone  = 0xffffffffu;
+constexpr int kKnnMax        = 16;  // NBODY_KNN_MAX
+constexpr int kKnnSumBlock   = 1024;
+constexpr int kKnnSummaryLen = 8;  // the handle's record: x_dc[3], r_c, rho_c, 3 unused — T each
+
+// Source record of the sweep: {x[3], m}, D components used.  The mass is not read by the sweep; finish takes it from here.
+template <typename T>
+struct alignas(sizeof(T) * 4) knn_rec {
+  T p[3];
+  T m;
+};
+
+template <typename T>
+__device__ __forceinline__ T knn_inf() {
+  return __builtin_huge_val();
+}
+
+// Launch shape, from sz alone: one target per lane for every size; as many chunks as bring the grid to about 2048 blocks, at most
+// 64, at least two once there are two tiles, at most one per tile.  Boundaries: 256 | 257 bodies (one tile, one chunk | two tiles,
+// two chunks) and 5888 | 5889 (one tile per chunk | several).
+inline hermite_plan knn_plan_for(uint32_t sz) {
+  hermite_plan p;
+  p.R      = 1u;
+  p.blocks = (sz + 63u) / 64u;
+  p.ntiles = (sz + kHTile - 1u) / kHTile;
+  uint32_t want = (2048u + p.blocks - 1u) / p.blocks;
+  if (want > 64u) want = 64u;
+  if (want < 2u) want = 2u;
+  if (want > p.ntiles) want = p.ntiles;
+  p.tiles_per_chunk = (p.ntiles + want - 1u) / want;
+  p.chunks          = (p.ntiles + p.tiles_per_chunk - 1u) / p.tiles_per_chunk;
+  return p;
+}
+
+// (d, j) into the ascending list by an unrolled compare-and-shift; every index is static.  LEX: lexicographic on (d2, idx) — the
+// merges; otherwise strict `<` on d2 alone — the sweep, where a later record has the higher index.  A record that is not below the
+// last entry changes nothing.
+template <typename T, int K, bool LEX>
+__device__ __forceinline__ void knn_insert(T (&ld)[K], uint32_t (&lj)[K], T d, uint32_t j) {
+  bool below[K];
+#pragma unroll
+  for (int s = 0; s < K; ++s) below[s] = LEX ? (d < ld[s] || (d == ld[s] && j < lj[s])) : (d < ld[s]);
+#pragma unroll
+  for (int s = K - 1; s > 0; --s) {
+    ld[s] = below[s - 1] ? ld[s - 1] : (below[s] ? d : ld[s]);
+    lj[s] = below[s - 1] ? lj[s - 1] : (below[s] ? j : lj[s]);
+  }
+  ld[0] = below[0] ? d : ld[0];
+  lj[0] = below[0] ? j : lj[0];
+}
+
+// ---- pack ----------------------------------------------------------------------------------------------------------------------
+template <typename T, int D>
+__global__ __launch_bounds__(kHBlock) void knn_pack_kernel(const T* __restrict__ m, const T* __restrict__ x, knn_rec<T>* __restrict__ recs,
+                                                           uint32_t n, uint32_t padded) {
+  const uint32_t i = blockIdx.x * kHBlock + threadIdx.x;
+  if (i >= padded) return;
+  knn_rec<T> r;
+  r.p[0] = r.p[1] = r.p[2] = r.m = T(0);  // padding: kept out of the lists by the index bound of the checked slices
+  if (i < n) {
+    r.m = m[i];
+#pragma unroll
+    for (int k = 0; k < D; ++k) r.p[k] = x[uint64_t(i) * D + k];
+  }
+  recs[i] = r;
+}
+
+// ---- the pair batch ------------------------------------------------------------------------------------------------------------
+// U records (global indices j0 ...) against the target of a lane (global index ti).  CHECK: the self pair and the records j >= n are
+// masked by index; without it the slice holds neither.
+template <typename T, int D, int K, int U, bool CHECK>
+__device__ __forceinline__ void knn_pair_batch(T (&ld)[K], uint32_t (&lj)[K], const T (&xi)[D], uint32_t ti, const T (&s)[U][D], uint32_t j0,
+                                               uint32_t n) {
+  T d2[U];
+#pragma unroll
+  for (int b = 0; b < U; ++b) {
+    T d[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) d[k] = s[b][k] - xi[k];
+    T t = d[0] * d[0];
+#pragma unroll
+    for (int k = 1; k < D; ++k) t = __builtin_elementwise_fma(d[k], d[k], t);
+    d2[b] = t;
+  }
+  if constexpr (CHECK) {
+#pragma unroll
+    for (int b = 0; b < U; ++b) {
+      const uint32_t j = j0 + uint32_t(b);
+      d2[b]            = (j < n && j != ti) ? d2[b] : knn_inf<T>();
+    }
+  }
+  T mn = d2[0];
+#pragma unroll
+  for (int b = 1; b < U; ++b) mn = __builtin_elementwise_min(mn, d2[b]);
+  if (__builtin_expect(__builtin_amdgcn_ballot_w64(mn < ld[K - 1]) != 0ull, 0)) {
+#pragma unroll
+    for (int b = 0; b < U; ++b)  // index order; a record no lane can take is skipped (its insertion would change nothing)
+      if (__builtin_amdgcn_ballot_w64(d2[b] < ld[K - 1]) != 0ull) knn_insert<T, K, false>(ld, lj, d2[b], j0 + uint32_t(b));
+  }
+}
+
+// One wave's slice of a tile: SUB records from src (LDS, wave-uniform addresses), global indices j0 ...
+template <typename T, int D, int K, int U, bool CHECK>
+__device__ __forceinline__ void knn_slice(T (&ld)[K], uint32_t (&lj)[K], const T (&xi)[D], uint32_t ti, const knn_rec<T>* src, uint32_t j0,
+                                          uint32_t n) {
+  constexpr int SUB = kHTile / kHWaves;
+#pragma unroll 1
+  for (int jj = 0; jj < SUB; jj += U) {
+    T s[U][D];
+#pragma unroll
+    for (int b = 0; b < U; ++b)
+#pragma unroll
+      for (int k = 0; k < D; ++k) s[b][k] = src[jj + b].p[k];
+    knn_pair_batch<T, D, K, U, CHECK>(ld, lj, xi, ti, s, j0 + uint32_t(jj), n);
+  }
+}
+
+// ---- sweep ---------------------------------------------------------------------------------------------------------------------
+// grid (blocks of 64 targets, chunks).  part_d: T[chunk][n][K], part_j: uint32[chunk][n][K] — a chunk's lists.
+template <typename T, int D, int K>
+__global__ __launch_bounds__(kHBlock) void knn_sweep_kernel(const knn_rec<T>* __restrict__ recs, T* __restrict__ part_d,
+                                                            uint32_t* __restrict__ part_j, uint32_t n, uint32_t ntiles,
+                                                            uint32_t tiles_per_chunk) {
+  constexpr int SUB = kHTile / kHWaves;        // records of a tile one wave takes
+  constexpr int U   = sizeof(T) == 8 ? 2 : 4;  // records a batch
+  constexpr size_t kTileBytes = sizeof(knn_rec<T>) * kHTile, kHandBytes = (sizeof(T) + sizeof(uint32_t)) * K * 64;
+  __shared__ __attribute__((aligned(64))) unsigned char smem[kTileBytes > kHandBytes ? kTileBytes : kHandBytes];
+  const knn_rec<T>* tile = reinterpret_cast<const knn_rec<T>*>(smem);
+  T* tflat               = reinterpret_cast<T*>(smem);
+  T* hand_d              = reinterpret_cast<T*>(smem);  // after the last tile has been consumed: one wave's lists, [K][64]
+  uint32_t* hand_j       = reinterpret_cast<uint32_t*>(hand_d + K * 64);
+
+  const int lane      = threadIdx.x & 63;
+  const uint32_t wave = uint32_t(__builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)));  // in an SGPR: source indices stay scalar
+
+  const uint32_t ti = blockIdx.x * 64u + uint32_t(lane);
+  T xi[D], ld[K];
+  uint32_t lj[K];
+  {
+    const uint32_t i = ti < n ? ti : 0u;  // clamp: out-of-range lanes compute, never store
+#pragma unroll
+    for (int k = 0; k < D; ++k) xi[k] = recs[i].p[k];
+  }
+#pragma unroll
+  for (int s = 0; s < K; ++s) {
+    ld[s] = knn_inf<T>();
+    lj[s] = kKnnNone;
+  }
+  const uint32_t own0 = blockIdx.x * 64u, own1 = own0 + 64u;  // the block's own targets
+
+  const uint32_t t0 = blockIdx.y * tiles_per_chunk;
+  const uint32_t t1 = t0 + tiles_per_chunk < ntiles ? t0 + tiles_per_chunk : ntiles;
+
+  const T* flat = reinterpret_cast<const T*>(recs);
+  T stage[4];  // one record per lane, value by value
+  auto stage_load = [&](uint32_t t) {  // the record array is padded to whole tiles
+#pragma unroll
+    for (int k = 0; k < 4; ++k) stage[k] = flat[(uint64_t(t) * kHTile + threadIdx.x) * 4 + k];
+  };
+  stage_load(t0);
+  for (uint32_t t = t0; t < t1; ++t) {
+    __syncthreads();  // every wave is done reading the previous tile
+#pragma unroll
+    for (int k = 0; k < 4; ++k) tflat[threadIdx.x * 4 + k] = stage[k];
+    __syncthreads();
+    if (t + 1 < t1) stage_load(t + 1);  // in flight while this tile is consumed
+
+    const knn_rec<T>* src = &tile[wave * SUB];
+    const uint32_t j0     = t * kHTile + wave * SUB;
+    // wave-uniform: does the slice hold a target of this block (the self pair) or a record past n (padding)?
+    const bool checked = (j0 + SUB > n) | ((j0 < own1) & (j0 + SUB > own0));
+    if (checked) knn_slice<T, D, K, U, true>(ld, lj, xi, ti, src, j0, n);
+    else knn_slice<T, D, K, U, false>(ld, lj, xi, ti, src, j0, n);
+  }
+
+  // the four waves' lists, one wave at a time, lexicographically
+#pragma unroll 1
+  for (uint32_t p = 1; p < uint32_t(kHWaves); ++p) {
+    __syncthreads();  // the last tile, or the previous wave's lists, have been read
+    if (wave == p) {
+#pragma unroll
+      for (int s = 0; s < K; ++s) {
+        hand_d[s * 64 + lane] = ld[s];
+        hand_j[s * 64 + lane] = lj[s];
+      }
+    }
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+      for (int s = 0; s < K; ++s) knn_insert<T, K, true>(ld, lj, hand_d[s * 64 + lane], hand_j[s * 64 + lane]);
+    }
+  }
+  if (wave == 0 && ti < n) {
+    const uint64_t row = (uint64_t(blockIdx.y) * n + ti) * K;
+#pragma unroll
+    for (int s = 0; s < K; ++s) {
+      part_d[row + s] = ld[s];
+      part_j[row + s] = lj[s];
+    }
+  }
+}
+
+// ---- finish --------------------------------------------------------------------------------------------------------------------
+template <typename T, int D, int K>
+__global__ __launch_bounds__(kHBlock) void knn_finish_kernel(const T* __restrict__ part_d, const uint32_t* __restrict__ part_j,
+                                                             const knn_rec<T>* __restrict__ recs, uint32_t* __restrict__ idx,
+                                                             T* __restrict__ d2, T* __restrict__ rho, uint32_t n, uint32_t chunks, int k) {
+  const uint32_t i = blockIdx.x * kHBlock + threadIdx.x;
+  if (i >= n) return;
+  T ld[K];
+  uint32_t lj[K];
+#pragma unroll
+  for (int s = 0; s < K; ++s) {
+    ld[s] = part_d[uint64_t(i) * K + s];
+    lj[s] = part_j[uint64_t(i) * K + s];
+  }
+  for (uint32_t ch = 1; ch < chunks; ++ch) {
+    const uint64_t row = (uint64_t(ch) * n + i) * K;
+#pragma unroll
+    for (int s = 0; s < K; ++s) knn_insert<T, K, true>(ld, lj, part_d[row + s], part_j[row + s]);
+  }
+  T M = T(0), dk = knn_inf<T>();
+  uint32_t jk = kKnnNone;
+#pragma unroll
+  for (int s = 0; s < K; ++s) {
+    if (s < k) {
+      idx[uint64_t(i) * k + s] = lj[s];
+      d2[uint64_t(i) * k + s]  = ld[s];
+    }
+    if (s < k - 1 && lj[s] < n) M += recs[lj[s]].m;  // neighbours 0 .. k - 2 in list order
+    if (s == k - 1) {
+      dk = ld[s];
+      jk = lj[s];
+    }
+  }
+  T r = T(0);
+  if (k >= 2 && jk != kKnnNone) {
+    if constexpr (D == 3) r = M / (T(4.18879020478639098461685784437267051) * (dk * __builtin_elementwise_sqrt(dk)));
+    else r = M / (T(3.14159265358979323846264338327950288) * dk);
+  }
+  rho[i] = r;
+}
+
+// ---- summary -------------------------------------------------------------------------------------------------------------------
+// One block.  In double for both types; every sum strided per lane, then over the wave by xor shuffles, then the waves in wave order.
+template <int NV>
+__device__ __forceinline__ void knn_block_sum(double (&v)[NV], double (*red)[kKnnSumBlock / 64]) {
+#pragma unroll
+  for (int q = 0; q < NV; ++q)
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v[q] += __shfl_xor(v[q], off, 64);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();  // red is free again
+  if (lane == 0) {
+#pragma unroll
+    for (int q = 0; q < NV; ++q) red[q][wave] = v[q];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < NV; ++q) {
+    double t = red[q][0];
+    for (int w = 1; w < kKnnSumBlock / 64; ++w) t += red[q][w];
+    v[q] = t;  // every lane holds the same total
+  }
+}
+
+template <typename T, int D>
+__global__ __launch_bounds__(kKnnSumBlock) void knn_summary_kernel(const T* __restrict__ rho, const knn_rec<T>* __restrict__ recs,
+                                                                   T* __restrict__ out, uint32_t n) {
+  __shared__ double red[D + 2][kKnnSumBlock / 64];
+  double a[D + 2];  // sum rho, sum rho^2, sum rho x
+#pragma unroll
+  for (int q = 0; q < D + 2; ++q) a[q] = 0.0;
+  for (uint32_t i = threadIdx.x; i < n; i += kKnnSumBlock) {
+    const double r = double(rho[i]);
+    a[0] += r;
+    a[1] += r * r;
+#pragma unroll
+    for (int k = 0; k < D; ++k) a[2 + k] += r * double(recs[i].p[k]);
+  }
+  knn_block_sum<D + 2>(a, red);
+  double xc[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) xc[k] = a[2 + k] / a[0];
+  double b[1] = {0.0};  // sum rho^2 |x - x_dc|^2
+  for (uint32_t i = threadIdx.x; i < n; i += kKnnSumBlock) {
+    const double r = double(rho[i]);
+    double q       = 0.0;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      const double d = double(recs[i].p[k]) - xc[k];
+      q += d * d;
+    }
+    b[0] += (r * r) * q;
+  }
+  knn_block_sum<1>(b, red);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out[k] = k < D ? T(xc[k < D ? k : 0]) : T(0);
+    out[3] = T(__builtin_elementwise_sqrt(b[0] / a[1]));
+    out[4] = T(a[1] / a[0]);
+    out[5] = out[6] = out[7] = T(0);
+  }
+}
+
+}  // namespace nbody
+
+using namespace nbody;
+
+// started: nbody_knn_compute has run (host call order, which a recorded step replays).  recs: knn_rec<T>[padded]; part: the chunks'
+// d2 lists, T[chunks][n][K].
+struct nbody_knn : hermite_handle {
+  int k = 0, K = 0;
+  uint32_t* part_j = nullptr;  // [chunks][n][K]: the lists' indices
+  uint32_t* idx    = nullptr;  // [n][k]
+  void* d2         = nullptr;  // T[n][k]
+  void* rho        = nullptr;  // T[n]
+  void* summary    = nullptr;  // T[kKnnSummaryLen]
+};
+
+namespace nbody {
+
+// check_state without the arrays this call never reads: v, a and ao may be NULL
+static int knn_check_state(const nbody_state* s, const char* who) {
+  NB_ARG(s != nullptr, "nbody_state is NULL");
+  NB_ARG(s->dtype == NBODY_F32 || s->dtype == NBODY_F64, "bad dtype %d", s->dtype);
+  NB_ARG(s->dim == 2 || s->dim == 3, "bad dim %d (must be 2 or 3)", s->dim);
+  NB_ARG(s->m && s->x, "nbody_state has a NULL array pointer (m, x)");
+  NB_ARG(uint64_t(s->first) + uint64_t(s->count) <= uint64_t(s->sz), "shard [%u, %u+%u) exceeds sz=%u", s->first, s->first, s->count,
+         s->sz);
+  if (s->tuning != 0) {
+    NB_ARG((s->tuning & ~0x1ffu) == 0 && (s->tuning & 0x100u) != 0, "nbody_state.tuning = 0x%x is not 0 or an NBODY_TUNING(...) value",
+           s->tuning);
+    if (int r = check_tuning(int(s->tuning & 15u), int((s->tuning >> 4) & 3u), int((s->tuning >> 6) & 3u))) return r;
+  }
+  NB_ARG(s->first == 0 && s->count == s->sz, "%s needs the whole system (first = 0, count = sz), got [%u, %u+%u) of %u", who, s->first,
+         s->first, s->count, s->sz);
+  return NBODY_OK;
+}
+
+template <typename T, int D, int K>
+static int knn_launch(nbody_knn* h, const nbody_state* s, hipStream_t st) {
+  const hermite_plan& p = h->plan;
+  auto* recs            = static_cast<knn_rec<T>*>(h->recs);
+  T* part_d             = static_cast<T*>(h->part);
+  T* rho                = static_cast<T*>(h->rho);
+  hipLaunchKernelGGL((knn_pack_kernel<T, D>), dim3(h->padded / kHBlock), dim3(kHBlock), 0, st, static_cast<const T*>(s->m),
+                     static_cast<const T*>(s->x), recs, h->n, h->padded);
+  NB_HIP(hipGetLastError());
+  hipLaunchKernelGGL((knn_sweep_kernel<T, D, K>), dim3(p.blocks, p.chunks), dim3(kHBlock), 0, st, recs, part_d, h->part_j, h->n, p.ntiles,
+                     p.tiles_per_chunk);
+  NB_HIP(hipGetLastError());
+  hipLaunchKernelGGL((knn_finish_kernel<T, D, K>), dim3((h->n + kHBlock - 1) / kHBlock), dim3(kHBlock), 0, st, part_d, h->part_j, recs,
+                     h->idx, static_cast<T*>(h->d2), rho, h->n, p.chunks, h->k);
+  NB_HIP(hipGetLastError());
+  hipLaunchKernelGGL((knn_summary_kernel<T, D>), dim3(1), dim3(kKnnSumBlock), 0, st, rho, recs, static_cast<T*>(h->summary), h->n);
+  NB_HIP(hipGetLastError());
+  return NBODY_OK;
+}
+
+// the tail of the two blocking reads, after their argument checks: the device, then the state rules
+static int knn_read_ready(const nbody_knn* h, const char* who, hipStream_t st) {
+  if (int r = check_same_device(h->device, st, "nbody_knn")) return r;
+  if (capture_id(st) != 0) {
+    set_error("%s is blocking: it cannot be recorded (call it outside nbody_graph_begin/end)", who);
+    return NBODY_ERR_STATE;
+  }
+  if (!h->started) {
+    set_error("%s before nbody_knn_compute on this handle", who);
+    return NBODY_ERR_STATE;
+  }
+  return NBODY_OK;
+}
+
+}  // namespace nbody
+
+extern "C" int nbody_knn_create(nbody_knn** out, int dtype, int dim, uint32_t n, int k) {
+  return nbody_knn_create_on(out, dtype, dim, n, k, -1);
+}
+
+extern "C" int nbody_knn_create_on(nbody_knn** out, int dtype, int dim, uint32_t n, int k, int device) {
+  NB_ARG(out != nullptr, "out is NULL");
+  *out = nullptr;
+  NB_ARG(dtype == NBODY_F32 || dtype == NBODY_F64, "bad dtype %d", dtype);
+  NB_ARG(dim == 2 || dim == 3, "bad dim %d", dim);
+  NB_ARG(n >= 1 && n <= (1u << 28), "knn needs 1 <= n <= 2^28 (got %u)", n);
+  NB_ARG(k >= 1 && k <= kKnnMax, "knn needs 1 <= k <= %d (got %d)", kKnnMax, k);
+  if (captures_on_this_thread() != 0) {
+    set_error("nbody_knn_create allocates: it cannot be called between nbody_graph_begin and nbody_graph_end");
+    return NBODY_ERR_STATE;
+  }
+  int ndev = 0;
+  NB_HIP(hipGetDeviceCount(&ndev));
+  if (device < 0) device = current_device();
+  NB_ARG(device >= 0 && device < ndev, "device %d out of range (%d HIP devices visible)", device, ndev);
+  device_guard guard(device);
+  auto* h   = new nbody_knn;
+  h->device = device;
+  h->dtype  = dtype;
+  h->dim    = dim;
+  h->n      = n;
+  h->k      = k;
+  h->K      = k <= 4 ? 4 : k <= 8 ? 8 : 16;
+  h->tsz    = dtype == NBODY_F32 ? 4 : 8;
+  h->plan   = knn_plan_for(n);
+  h->padded = h->plan.ntiles * uint32_t(kHTile);
+  const size_t rows = size_t(h->plan.chunks) * size_t(n) * size_t(h->K);
+  // nothing is cleared: every compute writes all of it before it reads it
+  hipError_t e = hipMalloc(&h->recs, h->tsz * 4 * size_t(h->padded));
+  if (e == hipSuccess) e = hipMalloc(&h->part, h->tsz * rows);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->part_j), sizeof(uint32_t) * rows);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->idx), sizeof(uint32_t) * size_t(n) * size_t(k));
+  if (e == hipSuccess) e = hipMalloc(&h->d2, h->tsz * size_t(n) * size_t(k));
+  if (e == hipSuccess) e = hipMalloc(&h->rho, h->tsz * size_t(n));
+  if (e == hipSuccess) e = hipMalloc(&h->summary, h->tsz * kKnnSummaryLen);
+  if (e != hipSuccess) {
+    int r = hip_fail(e, "nbody_knn_create allocation", __FILE__, __LINE__);
+    nbody_knn_destroy(h);
+    return r;
+  }
+  *out = h;
+  return NBODY_OK;
+}
+
+extern "C" void nbody_knn_destroy(nbody_knn* h) {
+  if (!h) return;
+  device_guard guard(h->device);
+  (void)hipFree(h->recs);
+  (void)hipFree(h->part);
+  (void)hipFree(h->part_j);
+  (void)hipFree(h->idx);
+  (void)hipFree(h->d2);
+  (void)hipFree(h->rho);
+  (void)hipFree(h->summary);
+  delete h;
+}
+
+extern "C" int nbody_knn_compute(nbody_knn* h, const nbody_state* s, void* stream) {
+  if (int r = knn_check_state(s, "nbody_knn_compute")) return r;
+  NB_ARG(h != nullptr, "nbody_knn is NULL");
+  NB_ARG(h->dtype == s->dtype && h->dim == s->dim && h->n == s->sz,
+         "nbody_knn was created for (dtype %d, dim %d, n %u), the state is (dtype %d, dim %d, sz %u)", h->dtype, h->dim, h->n, s->dtype,
+         s->dim, s->sz);
+  const hipStream_t st = as_stream(stream);
+  if (int r = check_same_device(h->device, st, "nbody_knn")) return r;
+  return dispatch(s->dtype, s->dim, [&](auto tg) {
+    using T         = typename decltype(tg)::type;
+    constexpr int D = decltype(tg)::dim;
+    device_guard guard(h->device);
+    const int r = h->K == 4 ? knn_launch<T, D, 4>(h, s, st) : h->K == 8 ? knn_launch<T, D, 8>(h, s, st) : knn_launch<T, D, 16>(h, s, st);
+    if (r == NBODY_OK) h->started = true;
+    return r;
+  });
+}
+
+extern "C" int nbody_knn_read(nbody_knn* h, int what, void* host_out, size_t bytes, void* stream) {
+  NB_ARG(what >= 0 && what <= 2, "what must be 0 (idx), 1 (d2) or 2 (rho), got %d", what);
+  NB_ARG(bytes != 0, "nbody_knn_read(what = %d): bytes is 0, it must be n k (idx, d2) or n (rho) elements", what);
+  NB_ARG(h != nullptr, "nbody_knn is NULL");
+  NB_ARG(host_out != nullptr, "host_out is NULL");
+  const size_t need = what == 0 ? sizeof(uint32_t) * size_t(h->n) * size_t(h->k) : what == 1 ? h->tsz * size_t(h->n) * size_t(h->k) : h->tsz * size_t(h->n);
+  NB_ARG(bytes == need, "nbody_knn_read(what = %d) needs %zu bytes, got %zu", what, need, bytes);
+  const hipStream_t st = as_stream(stream);
+  if (int r = knn_read_ready(h, "nbody_knn_read", st)) return r;
+  device_guard guard(h->device);
+  const void* src = what == 0 ? static_cast<const void*>(h->idx) : what == 1 ? h->d2 : h->rho;
+  NB_HIP(hipMemcpyAsync(host_out, src, bytes, hipMemcpyDeviceToHost, st));
+  NB_HIP(hipStreamSynchronize(st));
+  return NBODY_OK;
+}
+
+extern "C" int nbody_knn_density_centre(nbody_knn* h, void* centre_out, void* core_radius_out, void* core_density_out, void* stream) {
+  NB_ARG(h != nullptr, "nbody_knn is NULL");
+  const hipStream_t st = as_stream(stream);
+  if (int r = knn_read_ready(h, "nbody_knn_density_centre", st)) return r;
+  device_guard guard(h->device);
+  unsigned char raw[8 * kKnnSummaryLen];
+  const size_t t = h->tsz;
+  NB_HIP(hipMemcpyAsync(raw, h->summary, t * kKnnSummaryLen, hipMemcpyDeviceToHost, st));
+  NB_HIP(hipStreamSynchronize(st));
+  if (centre_out) memcpy(centre_out, raw, t * size_t(h->dim));
+  if (core_radius_out) memcpy(core_radius_out, raw + 3 * t, t);
+  if (core_density_out) memcpy(core_density_out, raw + 4 * t, t);
+  return NBODY_OK;
+}

@@ -46,6 +46,7 @@ class Device {
   }
   ~Device() {
     if (neighbours_) nbody_neighbours_destroy(neighbours_);
+    if (knn_) nbody_knn_destroy(knn_);
     if (hermite_) nbody_hermite_destroy(hermite_);
     if (hermite6_) nbody_hermite6_destroy(hermite6_);
     if (octree_block_) nbody_octree_block_destroy(octree_block_);
@@ -154,6 +155,17 @@ class Device {
     backend_check(nbody_neighbours_read(neighbours_, 2, nnd2.data(), nnd2.size() * sizeof(T), stream()), "nbody_neighbours_read");
   }
 
+  // --save-density K: the local densities from the K-th neighbour of the current (m, x) into rho, and {x_dc[D], r_c, rho_c} into
+  // summary (nbody_knn_*; the reads are blocking)
+  void density(int k, std::vector<T>& rho, T (&summary)[D + 2]) {
+    single("--save-density");
+    if (!knn_) backend_check(nbody_knn_create_on(&knn_, dtype, D, host_.n, k, 0), "nbody_knn_create_on");
+    backend_check(nbody_knn_compute(knn_, &view_[0], stream()), "nbody_knn_compute");
+    rho.resize(host_.n);
+    backend_check(nbody_knn_read(knn_, 2, rho.data(), rho.size() * sizeof(T), stream()), "nbody_knn_read");
+    backend_check(nbody_knn_density_centre(knn_, &summary[0], &summary[D], &summary[D + 1], stream()), "nbody_knn_density_centre");
+  }
+
   // Record the phase calls issued by `step` once and return a replayable graph of them (one submission per step).
   template <typename F>
   nbody_graph* record(F&& step) {
@@ -255,6 +267,7 @@ class Device {
   nbody_hermite6* hermite6_ = nullptr;
   nbody_octree_block* octree_block_ = nullptr;
   nbody_neighbours* neighbours_ = nullptr;
+  nbody_knn* knn_               = nullptr;
 };
 
 }  // namespace nb

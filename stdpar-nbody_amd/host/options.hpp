@@ -65,6 +65,10 @@ struct Options {
   // nearest neighbours and their squared distances (nbody_neighbours_*) are appended to neighbours.bin; independent of --save; one
   // GPU, with --softening EPS > 0 (the potential's softening length)
   bool save_neighbours = false;
+  // not in the reference either (nor in --help): --save-density K (2 .. 16), at every frame the run's Saver records, the local
+  // densities from the K-th neighbour, the density centre, the core radius and the core density (nbody_knn_*) are appended to
+  // density.bin; independent of --save and of the algorithm, needs no --softening; one GPU
+  int save_density = 0;  // 0: off
 };
 
 namespace detail {
@@ -197,6 +201,15 @@ inline Options parse_options(std::vector<std::string> const& argv) {
       o.tree_energy = true;
     } else if (f == "--save-neighbours") {
       o.save_neighbours = true;
+    } else if (f == "--save-density") {
+      std::string const l = k + 1 < argv.size() ? argv[++k] : std::string();
+      char* end           = nullptr;
+      long const v        = std::strtol(l.c_str(), &end, 10);
+      if (l.empty() || end != l.c_str() + l.size() || v < 2 || v > 16) {
+        std::cerr << "--save-density needs a neighbour count K in 2 .. 16." << std::endl;
+        std::exit(EXIT_FAILURE);
+      }
+      o.save_density = int(v);
     } else if (f == "--print-state") {
       o.print_state = true;
     } else if (f == "--print-info") {
@@ -229,6 +242,10 @@ inline Options parse_options(std::vector<std::string> const& argv) {
       std::cerr << "--save-neighbours runs on one GPU: it cannot be combined with --gpus." << std::endl;
       std::exit(EXIT_FAILURE);
     }
+  }
+  if (o.save_density != 0 && o.gpus_given) {
+    std::cerr << "--save-density runs on one GPU: it cannot be combined with --gpus." << std::endl;
+    std::exit(EXIT_FAILURE);
   }
   if (o.block_levels_given && !(o.block_eta > 0.0)) {
     std::cerr << "--block-levels needs --block-eta ETA." << std::endl;

@@ -3,6 +3,8 @@
 //   energy.bin:    u32 steps, u32 sizeof(T), then (kinetic, potential) per save_all
 // and, with --save-neighbours (no reference counterpart), in the same style
 //   neighbours.bin: u32 nbodies, u32 steps, u32 sizeof(T), u32 dim, then per save_all phi T[n], nn u32[n], nnd2 T[n]
+// and, with --save-density K,
+//   density.bin:    u32 nbodies, u32 steps, u32 sizeof(T), u32 dim, u32 k, then per save_all rho T[n], x_dc T[dim], r_c T, rho_c T
 #pragma once
 #include <cstdint>
 #include <cstdlib>
@@ -20,7 +22,7 @@ class Saver {
  public:
   explicit Saver(Options const& o)
    : pos_(o.save_pos), energy_(o.save_energy), tree_energy_(o.tree_energy), quadrupole_(o.quadrupole), softening_(o.softening),
-     neighbours_(o.save_neighbours), theta_(o.theta), nbodies_(std::uint32_t(o.size)), nsteps_(std::uint32_t(o.steps)) {
+     neighbours_(o.save_neighbours), density_k_(o.save_density), theta_(o.theta), nbodies_(std::uint32_t(o.size)), nsteps_(std::uint32_t(o.steps)) {
     std::uint32_t const tsz = sizeof(T), dim = D;
     if (pos_) {
       pos_file_.open("positions.bin", std::ios::out | std::ios::binary);
@@ -41,9 +43,18 @@ class Saver {
       put(neighbours_file_, tsz);
       put(neighbours_file_, dim);
     }
+    if (density_k_ != 0) {
+      std::uint32_t const k = std::uint32_t(density_k_);
+      density_file_.open("density.bin", std::ios::out | std::ios::binary);
+      put(density_file_, nbodies_);
+      put(density_file_, nsteps_);
+      put(density_file_, tsz);
+      put(density_file_, dim);
+      put(density_file_, k);
+    }
   }
 
-  bool active() const { return pos_ || energy_ || neighbours_; }
+  bool active() const { return pos_ || energy_ || neighbours_ || density_k_ != 0; }
 
   // one frame; the device copy is authoritative, so positions are pulled first
   void save_all(System<T, D>& sys, Device<T, D>& dev) {
@@ -62,6 +73,12 @@ class Saver {
       neighbours_file_.write(reinterpret_cast<char const*>(nn_.data()), std::streamsize(nn_.size() * sizeof(std::uint32_t)));
       neighbours_file_.write(reinterpret_cast<char const*>(nnd2_.data()), std::streamsize(nnd2_.size() * sizeof(T)));
     }
+    if (density_k_ != 0) {
+      T summary[D + 2];  // x_dc, r_c, rho_c
+      dev.density(density_k_, rho_, summary);
+      density_file_.write(reinterpret_cast<char const*>(rho_.data()), std::streamsize(rho_.size() * sizeof(T)));
+      density_file_.write(reinterpret_cast<char const*>(summary), std::streamsize(sizeof summary));
+    }
   }
 
  private:
@@ -73,10 +90,11 @@ class Saver {
   bool tree_energy_, quadrupole_;  // --tree-energy: the octree's energies at theta_, with the --quadrupole term if the run has it
   double softening_;               // --softening: the energies of the softened dynamics
   bool neighbours_;                // --save-neighbours: phi, nn, nnd2 of every recorded frame, softening_ the potential's length
+  int density_k_;                  // --save-density K: rho and the density-centre summary of every recorded frame; 0: off
   double theta_;
   std::uint32_t nbodies_, nsteps_;
-  std::ofstream pos_file_, energy_file_, neighbours_file_;
-  std::vector<T> phi_, nnd2_;
+  std::ofstream pos_file_, energy_file_, neighbours_file_, density_file_;
+  std::vector<T> phi_, nnd2_, rho_;
   std::vector<std::uint32_t> nn_;
 };
 
