@@ -76,6 +76,15 @@ __device__ __forceinline__ void hermite_pair_head(T (&d)[D], T (&u)[D], T& q, T&
 // and what each order builds its 1 / q from.  Double: A = fl(y y), e = fl(1 - q A) (one FMA: the exact residual of the ROUNDED A up to
 // 2^-76), so 1 / q = A / (1 - e) = A (1 + e + e^2 + O(e^3)), e <= 2^-23.  Float: A = y y from the 1-ulp v_rsq_f32 is 1 / q within
 // 2.5 ulp — the size of m y^3's own ~3 ulp — and takes no correction (e is not set).
+//
+// Rounding error of one pair term, P_g, in units of eps_T (2^-52, 2^-23; one rounding = 0.5) times the term's magnitude scale (every
+// product taken as the product of norms, every sum as the sum of absolute values), counted from d, u, b, q, d.u and |u|^2 + d.b as the
+// pair's head made them.  tests/hermite_wide_model.py carries the table, tests/test_gpu_hermite_wide.py holds the kernels to it:
+//                         a       jerk    snap
+//   double                2.5     5       7
+//   float                 4.5     8.5     12
+// a is w's figure.  Double: 2.5, the series above.  Float: y within 1 ulp makes y^3 within 3, and A = y y, A y and m (A y) round once
+// each: 4.5.  The jerk's and the snap's figures are derived beside hermite_pair_batch of each order; the jerk's is the same in both.
 template <typename T>
 __device__ __forceinline__ T hermite_pair_weight(T q, T m, const pair_consts<T>& pc, T& A, T& e) {
   if constexpr (sizeof(T) == 8) {
@@ -100,6 +109,8 @@ __device__ __forceinline__ T hermite_pair_weight(T q, T m, const pair_consts<T>&
 // Double: B = -3 A (<= 1/2 ulp beyond A's), alpha' = fma(B, fma(e, e, e), B) (truncation 2^-69, one rounding), alpha = du alpha' (one
 // rounding): alpha is within 2 ulp of -3 fl(d.u) / q, against w's <= 2.5 ulp of m q^(-3/2); t = fma(alpha, d, u) rounds once.  The
 // jerk's pair term fl-error is therefore <= 2.5 ulp on its w u part and <= 5 ulp on its w alpha d part.
+// Float: A within 2.5 ulp of 1 / q, -3 A and du (-3 A) round once each: alpha within 3.5 ulp; t rounds once (0.5, on |u| + |alpha d|);
+// with w's 4.5 the term is within 5 ulp on its w u part and 4.5 + 3.5 + 0.5 = 8.5 ulp on its w alpha d part.
 // Self pair, coincident bodies at equal velocity, zero-mass padding: d = 0 (and u = 0) or w = 0 add exactly 0; q >= e2 keeps all finite.
 template <typename T, int D, int R, int U>
 __device__ __forceinline__ void hermite_pair_batch(T (&acc)[2][R][D], const T (&tg)[2][R][D], const hermite_rec<T, 2> (&s)[U],
@@ -142,6 +153,14 @@ __device__ __forceinline__ void hermite_pair_batch(T (&acc)[2][R][D], const T (&
 // Double: 1 / q as fma(A, fma(e, e, e), A): truncation 2^-69, two roundings.  alpha, gamma: one more rounding each on top of their dot
 // products'; c3 = fma(15 alpha, alpha, -3 gamma).  (Order 4's alpha folds the -3 into B first and differs from c1 in the last bit:
 // each order keeps its own.)
+// The pair term's fl-error, I the error of iq = 1 / q (double 1 ulp: two roundings; float 2.5 ulp: A) and W that of w (2.5, 4.5):
+//   alpha, gamma   I + 0.5 (the product with du, with g2)                                           1.5 ulp    float 3
+//   c1 = c2 / 2    + 0.5 (the product with -3; c2 = c1 + c1 is exact)                               2          3.5
+//   c3             15 alpha: I + 1, times alpha: 2 I + 1.5, the FMA's rounding 0.5 (the -3 gamma
+//                  part, I + 1.5, is smaller)                                                       4          7
+//   jerk  w tj     tj = fma(c1, d, u) rounds once: W + 0.5 on w u, W + c1's + 0.5 on w c1 d         5          8.5
+//   snap  w ts     ts = fma(c3, d, fma(c2, u, b)), two roundings: W + 1 on w b, W + c2's + 1 on
+//                  w c2 u, W + c3's + 0.5 on w c3 d                                                 7          12
 // Self pair, coincident bodies at equal velocity and acceleration, zero-mass padding: d = u = b = 0 or w = 0 add exactly 0 (alpha =
 // gamma = 0 there, no 0 x inf: q >= e2 keeps everything finite).  All velocities zero: du = 0, c1 = c2 = -0, the jerk's term is 0.
 template <typename T, int D, int R, int U>

@@ -8,7 +8,9 @@ tiles and two chunks), two targets per lane from 65536 bodies on (65535 / 65536 
 Measured on an MI355X (max|got - ref| / max|ref|, worst over the sizes): a 8.2e-15 and jerk 6.1e-15 in double, a 4.0e-6 and jerk 4.5e-6 in
 float (all at N = 262 017); against the softened K1 1.0e-6 in float; one step within 7.4e-15; two-body errors 1.613e-5 / 9.798e-7 /
 6.04e-8 / 3.749e-9, equal to NumPy's to the printed digits; |dE / E| 5.6e-6 and 1.77e-7 (NumPy the same) against the leapfrog's 1.36e-2
-and 6.87e-3; the float trajectory at 0.72 x its yardstick (7.1e-7)."""
+and 6.87e-3; the float trajectory at 0.72 x its yardstick (7.1e-7).
+
+Per-body bounds in ulps against a wide reference, c != 1 and the ends of the softening range are in tests/test_gpu_hermite_wide.py."""
 import ctypes
 import os
 import re

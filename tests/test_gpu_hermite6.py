@@ -13,7 +13,9 @@ subset of 256 (first body, the whole last block of 64, random others) up to 20 0
 Measured on an MI355X (max|got - ref| / max|ref|, worst over the sizes): a 1.8e-15, jerk 3.7e-15, snap 5.2e-15 in double; a 9.8e-7,
 jerk 2.6e-6, snap 4.3e-6 in float; two steps within 5e-15 except the crackle, 6.9e-14 at dt = 0.05; two-body errors 6.71e-5 / 1.033e-6 /
 1.572e-8 / 2.417e-10 (ratios 65.0, 65.7, 65.1), equal to NumPy's to the printed digits; |dE / E| 1.29e-8 and 4.83e-9 (NumPy the same)
-against the fourth order's 5.6e-6 and 1.77e-7; the float trajectory at 0.72 x its yardstick (7.07e-7, GPU 5.08e-7)."""
+against the fourth order's 5.6e-6 and 1.77e-7; the float trajectory at 0.72 x its yardstick (7.07e-7, GPU 5.08e-7).
+
+Per-body bounds in ulps against a wide reference, c != 1 and the ends of the softening range are in tests/test_gpu_hermite_wide.py."""
 import ctypes
 import os
 import re

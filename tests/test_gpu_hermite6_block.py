@@ -15,7 +15,9 @@ float64 model):
   crackle   largest distance (maxrel) 2.38e-10 (N = 65 537, 3D; 1.14e-10 at N = 2 in 2D, 1.3e-12 .. 7.3e-11 elsewhere): the crackle
             is 60 (a1 - a0) / h^3 - ..., a third difference.  CRACKLE_TOL = 8 x that.
   want      largest relative difference 5.54e-9 (N = 2, 2D, want / h = 4.7; <= 1.7e-9 elsewhere, 1.6e-9 and 1.2e-9 at N = 65 537), no
-            level different in any of the ten cases, want / h between 0.15 and 4.7.  LEVEL_EXCUSE = 10 x that."""
+            level different in any of the ten cases, want / h between 0.15 and 4.7.  LEVEL_EXCUSE = 10 x that.
+
+Per-body bounds in ulps against a wide reference, c != 1 and the ends of the softening range are in tests/test_gpu_hermite_wide.py."""
 import ctypes
 
 import numpy as np

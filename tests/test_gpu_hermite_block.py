@@ -15,7 +15,9 @@ Measured on an MI355X (max|got - ref| / max|ref|, worst over the cases): one blo
 3.4e-16, jerk 4.1e-16; max_level = 0 bitwise equal to nbody_hermite_step in all four cases; the binary in a cluster 1115 block steps,
 16 755 body steps, |dE / E| 8.34e-8 — NumPy's to the printed digits — against the fixed step's 2.15e-2 (2.6e5 x), final x within 3.0e-14 of NumPy's; in float 339 block steps / 14 499
 body steps against float64's 334 / 14 496, |dE / E| 3.4e-8 under a bound of 4 x 6.75e-8, the trajectory at 0.86 x its yardstick
-(9.7e-7); CLI max |dE / E| over 8 steps 1.2e-6 with --hermite-eta 0.02 against 0.49 without."""
+(9.7e-7); CLI max |dE / E| over 8 steps 1.2e-6 with --hermite-eta 0.02 against 0.49 without.
+
+Per-body bounds in ulps against a wide reference, c != 1 and the ends of the softening range are in tests/test_gpu_hermite_wide.py."""
 import ctypes
 import os
 import struct
