@@ -91,11 +91,13 @@ constexpr const char* experiment_env(const char*) { return nullptr; }
 
 inline int check_tuning(int split, int tpt, int path);
 
-inline int check_state(const nbody_state* s) {
+// all_arrays = false: a call that reads only (m, x) — v, a and ao may be NULL
+inline int check_state(const nbody_state* s, bool all_arrays = true) {
   NB_ARG(s != nullptr, "nbody_state is NULL");
   NB_ARG(s->dtype == NBODY_F32 || s->dtype == NBODY_F64, "bad dtype %d", s->dtype);
   NB_ARG(s->dim == 2 || s->dim == 3, "bad dim %d (must be 2 or 3)", s->dim);
-  NB_ARG(s->m && s->x && s->v && s->a && s->ao, "nbody_state has a NULL array pointer");
+  if (all_arrays) NB_ARG(s->m && s->x && s->v && s->a && s->ao, "nbody_state has a NULL array pointer");
+  NB_ARG(s->m && s->x, "nbody_state has a NULL array pointer (m, x)");
   NB_ARG(uint64_t(s->first) + uint64_t(s->count) <= uint64_t(s->sz), "shard [%u, %u+%u) exceeds sz=%u", s->first, s->first,
          s->count, s->sz);
   // tuning is 0 or a value NBODY_TUNING() made: a hand-built state that was not zero-initialised is refused, not obeyed

@@ -3,8 +3,8 @@
 // UNSOFTENED squared distance, so no softening is involved and the call works after any algorithm, also with eps = 0.
 //
 // Definitions (T the state's type, D its dimension, d = x_j - x_i):
-//   d2_ij   exactly the d2 of neighbours.hip: one FMA chain in component order, t = d_0 d_0, then t = fma(d_k, d_k, t).  Bitwise
-//           symmetric in (i, j).
+//   d2_ij   the UNSOFTENED squared distance, pair_d2 of pair_sweep.hpp (exactly the d2 of neighbours.hip): one FMA chain in component
+//           order, bitwise symmetric in (i, j).
 //   order   the k neighbours of i are the k smallest (d2_ij, j), j != i, in lexicographic order (equal computed d2: the lowest index),
 //           listed ascending in that order.  A body has min(k, n - 1) of them; unused slots hold (0xffffffff, +inf).
 //   K       the capacity of the list a lane carries, the smallest of {4, 8, 16} that is >= k.  The tie rule is exact, so the first k
@@ -17,21 +17,21 @@
 //           or a non-finite rho (coincident bodies) gives NaN by IEEE rules: not an error.
 //
 // Four launches per compute, all on the caller's stream, nothing allocated after nbody_knn_create:
-//   pack     one lane per record: {x[3], m} (4 T; 2D zero-fills component 2), padded with records at the origin to whole tiles.  A
-//            padding record never becomes a neighbour because of an INDEX BOUND: every slice of 64 records that reaches past n runs
-//            the checked batch body, which replaces the d2 of a record j >= n by +inf.
-//   sweep    the hot path, the shape of neighbours.hip's sweep (hermite_tile.hpp): ONE target per lane (the list alone is 48 VGPRs at
-//            K = 16 in double), records staged through LDS tiles of kHTile and read as wave-uniform broadcasts, every tile cut over
-//            the four waves of the block, the tiles cut over grid.y chunks by knn_plan_for(sz): a function of sz alone.  A lane
-//            carries its target's sorted list (d2[K], idx[K]) in registers; every access is statically indexed in unrolled code.
+//   pack     pair_sweep.hpp's: one lane per record {x[3], m}, padded with records at the origin to whole tiles.  A padding record
+//            never becomes a neighbour because of an INDEX BOUND: every slice of 64 records that reaches past n runs the checked
+//            batch body, which replaces the d2 of a record j >= n by +inf.
+//   sweep    the hot path, over pair_sweep_tiles of pair_sweep.hpp: ONE target per lane (the list alone is 48 VGPRs at K = 16 in
+//            double), the tiles cut over grid.y chunks by knn_plan_for(sz): a function of sz alone; what is here is the pair batch,
+//            the slice and the merge of the block's waves.  A lane carries its target's sorted list (d2[K], idx[K]) in registers;
+//            every access is statically indexed in unrolled code.
 //            No transcendental at all.  A batch of U records takes U - 1 v_min and ONE compare of the batch's minimum against the
 //            list's last entry; only if some lane of the wave has a candidate (one ballot, one scalar branch) do the lanes walk the
 //            batch in index order (one more ballot per record skips a record no lane can take) and insert each record with d2
 //            strictly below the last entry by an unrolled compare-and-shift.
 //            Strict `<` keeps the earlier (lower) index among equal values, because a lane meets its sources in ascending index
 //            order.  The result is the same whichever way the branch goes.
-//            Two batch bodies, chosen per slice (wave-uniform): the CHECKED one masks the self pair and the padding (d2 +inf) by
-//            index; every other slice runs the plain body, which has no index test at all.
+//            Two batch bodies, chosen per slice by pair_sweep_tiles: the CHECKED one masks the self pair and the padding (d2 +inf)
+//            by index; every other slice runs the plain body, which has no index test at all.
 //            The block's waves merge through LDS, one wave's lists at a time (12 K bytes per lane), LEXICOGRAPHICALLY on (d2, idx):
 //            a wave's slice of a later tile holds higher indices than another wave's slice of an earlier tile.  The chunk's lists
 //            go to the partial arrays T[chunk][n][K], uint32[chunk][n][K].
@@ -42,28 +42,15 @@
 // runs, an eager call and a replayed recorded one, and a handle destroyed and made again give the same bits.
 // Bound: FP64 / FP32 VALU issue; per pair D subtractions, D chain operations, (U - 1) / U min + 1 / U compare, and for a batch that
 // takes the branch U insertions of K compares and 2 K selects (3 K v_cndmask in double).
-#include "hermite_tile.hpp"
+#include "pair_sweep.hpp"
 
 #pragma clang fp contract(off)
 
 namespace nbody {
 
-constexpr uint32_t kKnnNone  = 0xffffffffu;
 constexpr int kKnnMax        = 16;  // NBODY_KNN_MAX
 constexpr int kKnnSumBlock   = 1024;
 constexpr int kKnnSummaryLen = 8;  // the handle's record: x_dc[3], r_c, rho_c, 3 unused — T each
-
-// Source record of the sweep: {x[3], m}, D components used.  The mass is not read by the sweep; finish takes it from here.
-template <typename T>
-struct alignas(sizeof(T) * 4) knn_rec {
-  T p[3];
-  T m;
-};
-
-template <typename T>
-__device__ __forceinline__ T knn_inf() {
-  return __builtin_huge_val();
-}
 
 // Launch shape, from sz alone: one target per lane for every size; as many chunks as bring the grid to about 2048 blocks, at most
 // 64, at least two once there are two tiles, at most one per tile.  Boundaries: 256 | 257 bodies (one tile, one chunk | two tiles,
@@ -99,22 +86,6 @@ __device__ __forceinline__ void knn_insert(T (&ld)[K], uint32_t (&lj)[K], T d, u
   lj[0] = below[0] ? j : lj[0];
 }
 
-// ---- pack ----------------------------------------------------------------------------------------------------------------------
-template <typename T, int D>
-__global__ __launch_bounds__(kHBlock) void knn_pack_kernel(const T* __restrict__ m, const T* __restrict__ x, knn_rec<T>* __restrict__ recs,
-                                                           uint32_t n, uint32_t padded) {
-  const uint32_t i = blockIdx.x * kHBlock + threadIdx.x;
-  if (i >= padded) return;
-  knn_rec<T> r;
-  r.p[0] = r.p[1] = r.p[2] = r.m = T(0);  // padding: kept out of the lists by the index bound of the checked slices
-  if (i < n) {
-    r.m = m[i];
-#pragma unroll
-    for (int k = 0; k < D; ++k) r.p[k] = x[uint64_t(i) * D + k];
-  }
-  recs[i] = r;
-}
-
 // ---- the pair batch ------------------------------------------------------------------------------------------------------------
 // U records (global indices j0 ...) against the target of a lane (global index ti).  CHECK: the self pair and the records j >= n are
 // masked by index; without it the slice holds neither.
@@ -123,20 +94,12 @@ __device__ __forceinline__ void knn_pair_batch(T (&ld)[K], uint32_t (&lj)[K], co
                                                uint32_t n) {
   T d2[U];
 #pragma unroll
-  for (int b = 0; b < U; ++b) {
-    T d[D];
-#pragma unroll
-    for (int k = 0; k < D; ++k) d[k] = s[b][k] - xi[k];
-    T t = d[0] * d[0];
-#pragma unroll
-    for (int k = 1; k < D; ++k) t = __builtin_elementwise_fma(d[k], d[k], t);
-    d2[b] = t;
-  }
+  for (int b = 0; b < U; ++b) d2[b] = pair_d2<T, D>(s[b], xi);
   if constexpr (CHECK) {
 #pragma unroll
     for (int b = 0; b < U; ++b) {
       const uint32_t j = j0 + uint32_t(b);
-      d2[b]            = (j < n && j != ti) ? d2[b] : knn_inf<T>();
+      d2[b]            = (j < n && j != ti) ? d2[b] : pair_inf<T>();
     }
   }
   T mn = d2[0];
@@ -151,7 +114,7 @@ __device__ __forceinline__ void knn_pair_batch(T (&ld)[K], uint32_t (&lj)[K], co
 
 // One wave's slice of a tile: SUB records from src (LDS, wave-uniform addresses), global indices j0 ...
 template <typename T, int D, int K, int U, bool CHECK>
-__device__ __forceinline__ void knn_slice(T (&ld)[K], uint32_t (&lj)[K], const T (&xi)[D], uint32_t ti, const knn_rec<T>* src, uint32_t j0,
+__device__ __forceinline__ void knn_slice(T (&ld)[K], uint32_t (&lj)[K], const T (&xi)[D], uint32_t ti, const pair_rec<T>* src, uint32_t j0,
                                           uint32_t n) {
   constexpr int SUB = kHTile / kHWaves;
 #pragma unroll 1
@@ -168,17 +131,14 @@ __device__ __forceinline__ void knn_slice(T (&ld)[K], uint32_t (&lj)[K], const T
 // ---- sweep ---------------------------------------------------------------------------------------------------------------------
 // grid (blocks of 64 targets, chunks).  part_d: T[chunk][n][K], part_j: uint32[chunk][n][K] — a chunk's lists.
 template <typename T, int D, int K>
-__global__ __launch_bounds__(kHBlock) void knn_sweep_kernel(const knn_rec<T>* __restrict__ recs, T* __restrict__ part_d,
+__global__ __launch_bounds__(kHBlock) void knn_sweep_kernel(const pair_rec<T>* __restrict__ recs, T* __restrict__ part_d,
                                                             uint32_t* __restrict__ part_j, uint32_t n, uint32_t ntiles,
                                                             uint32_t tiles_per_chunk) {
-  constexpr int SUB = kHTile / kHWaves;        // records of a tile one wave takes
-  constexpr int U   = sizeof(T) == 8 ? 2 : 4;  // records a batch
-  constexpr size_t kTileBytes = sizeof(knn_rec<T>) * kHTile, kHandBytes = (sizeof(T) + sizeof(uint32_t)) * K * 64;
+  constexpr int U = sizeof(T) == 8 ? 2 : 4;  // records a batch
+  constexpr size_t kTileBytes = sizeof(pair_rec<T>) * kHTile, kHandBytes = (sizeof(T) + sizeof(uint32_t)) * K * 64;
   __shared__ __attribute__((aligned(64))) unsigned char smem[kTileBytes > kHandBytes ? kTileBytes : kHandBytes];
-  const knn_rec<T>* tile = reinterpret_cast<const knn_rec<T>*>(smem);
-  T* tflat               = reinterpret_cast<T*>(smem);
-  T* hand_d              = reinterpret_cast<T*>(smem);  // after the last tile has been consumed: one wave's lists, [K][64]
-  uint32_t* hand_j       = reinterpret_cast<uint32_t*>(hand_d + K * 64);
+  T* hand_d        = reinterpret_cast<T*>(smem);  // after the last tile has been consumed: one wave's lists, [K][64]
+  uint32_t* hand_j = reinterpret_cast<uint32_t*>(hand_d + K * 64);
 
   const int lane      = threadIdx.x & 63;
   const uint32_t wave = uint32_t(__builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)));  // in an SGPR: source indices stay scalar
@@ -193,35 +153,14 @@ __global__ __launch_bounds__(kHBlock) void knn_sweep_kernel(const knn_rec<T>* __
   }
 #pragma unroll
   for (int s = 0; s < K; ++s) {
-    ld[s] = knn_inf<T>();
-    lj[s] = kKnnNone;
+    ld[s] = pair_inf<T>();
+    lj[s] = kNoNeighbour;
   }
   const uint32_t own0 = blockIdx.x * 64u, own1 = own0 + 64u;  // the block's own targets
 
-  const uint32_t t0 = blockIdx.y * tiles_per_chunk;
-  const uint32_t t1 = t0 + tiles_per_chunk < ntiles ? t0 + tiles_per_chunk : ntiles;
-
-  const T* flat = reinterpret_cast<const T*>(recs);
-  T stage[4];  // one record per lane, value by value
-  auto stage_load = [&](uint32_t t) {  // the record array is padded to whole tiles
-#pragma unroll
-    for (int k = 0; k < 4; ++k) stage[k] = flat[(uint64_t(t) * kHTile + threadIdx.x) * 4 + k];
-  };
-  stage_load(t0);
-  for (uint32_t t = t0; t < t1; ++t) {
-    __syncthreads();  // every wave is done reading the previous tile
-#pragma unroll
-    for (int k = 0; k < 4; ++k) tflat[threadIdx.x * 4 + k] = stage[k];
-    __syncthreads();
-    if (t + 1 < t1) stage_load(t + 1);  // in flight while this tile is consumed
-
-    const knn_rec<T>* src = &tile[wave * SUB];
-    const uint32_t j0     = t * kHTile + wave * SUB;
-    // wave-uniform: does the slice hold a target of this block (the self pair) or a record past n (padding)?
-    const bool checked = (j0 + SUB > n) | ((j0 < own1) & (j0 + SUB > own0));
-    if (checked) knn_slice<T, D, K, U, true>(ld, lj, xi, ti, src, j0, n);
-    else knn_slice<T, D, K, U, false>(ld, lj, xi, ti, src, j0, n);
-  }
+  pair_sweep_tiles<T>(recs, smem, wave, n, ntiles, tiles_per_chunk, own0, own1, [&](const pair_rec<T>* src, uint32_t j0, auto checked) {
+    knn_slice<T, D, K, U, decltype(checked)::value>(ld, lj, xi, ti, src, j0, n);
+  });
 
   // the four waves' lists, one wave at a time, lexicographically
 #pragma unroll 1
@@ -253,7 +192,7 @@ __global__ __launch_bounds__(kHBlock) void knn_sweep_kernel(const knn_rec<T>* __
 // ---- finish --------------------------------------------------------------------------------------------------------------------
 template <typename T, int D, int K>
 __global__ __launch_bounds__(kHBlock) void knn_finish_kernel(const T* __restrict__ part_d, const uint32_t* __restrict__ part_j,
-                                                             const knn_rec<T>* __restrict__ recs, uint32_t* __restrict__ idx,
+                                                             const pair_rec<T>* __restrict__ recs, uint32_t* __restrict__ idx,
                                                              T* __restrict__ d2, T* __restrict__ rho, uint32_t n, uint32_t chunks, int k) {
   const uint32_t i = blockIdx.x * kHBlock + threadIdx.x;
   if (i >= n) return;
@@ -269,8 +208,8 @@ __global__ __launch_bounds__(kHBlock) void knn_finish_kernel(const T* __restrict
 #pragma unroll
     for (int s = 0; s < K; ++s) knn_insert<T, K, true>(ld, lj, part_d[row + s], part_j[row + s]);
   }
-  T M = T(0), dk = knn_inf<T>();
-  uint32_t jk = kKnnNone;
+  T M = T(0), dk = pair_inf<T>();
+  uint32_t jk = kNoNeighbour;
 #pragma unroll
   for (int s = 0; s < K; ++s) {
     if (s < k) {
@@ -284,7 +223,7 @@ __global__ __launch_bounds__(kHBlock) void knn_finish_kernel(const T* __restrict
     }
   }
   T r = T(0);
-  if (k >= 2 && jk != kKnnNone) {
+  if (k >= 2 && jk != kNoNeighbour) {
     if constexpr (D == 3) r = M / (T(4.18879020478639098461685784437267051) * (dk * __builtin_elementwise_sqrt(dk)));
     else r = M / (T(3.14159265358979323846264338327950288) * dk);
   }
@@ -315,7 +254,7 @@ __device__ __forceinline__ void knn_block_sum(double (&v)[NV], double (*red)[kKn
 }
 
 template <typename T, int D>
-__global__ __launch_bounds__(kKnnSumBlock) void knn_summary_kernel(const T* __restrict__ rho, const knn_rec<T>* __restrict__ recs,
+__global__ __launch_bounds__(kKnnSumBlock) void knn_summary_kernel(const T* __restrict__ rho, const pair_rec<T>* __restrict__ recs,
                                                                    T* __restrict__ out, uint32_t n) {
   __shared__ double red[D + 2][kKnnSumBlock / 64];
   double a[D + 2];  // sum rho, sum rho^2, sum rho x
@@ -357,7 +296,7 @@ __global__ __launch_bounds__(kKnnSumBlock) void knn_summary_kernel(const T* __re
 
 using namespace nbody;
 
-// started: nbody_knn_compute has run (host call order, which a recorded step replays).  recs: knn_rec<T>[padded]; part: the chunks'
+// started: nbody_knn_compute has run (host call order, which a recorded step replays).  recs: pair_rec<T>[padded]; part: the chunks'
 // d2 lists, T[chunks][n][K].
 struct nbody_knn : hermite_handle {
   int k = 0, K = 0;
@@ -370,31 +309,13 @@ struct nbody_knn : hermite_handle {
 
 namespace nbody {
 
-// check_state without the arrays this call never reads: v, a and ao may be NULL
-static int knn_check_state(const nbody_state* s, const char* who) {
-  NB_ARG(s != nullptr, "nbody_state is NULL");
-  NB_ARG(s->dtype == NBODY_F32 || s->dtype == NBODY_F64, "bad dtype %d", s->dtype);
-  NB_ARG(s->dim == 2 || s->dim == 3, "bad dim %d (must be 2 or 3)", s->dim);
-  NB_ARG(s->m && s->x, "nbody_state has a NULL array pointer (m, x)");
-  NB_ARG(uint64_t(s->first) + uint64_t(s->count) <= uint64_t(s->sz), "shard [%u, %u+%u) exceeds sz=%u", s->first, s->first, s->count,
-         s->sz);
-  if (s->tuning != 0) {
-    NB_ARG((s->tuning & ~0x1ffu) == 0 && (s->tuning & 0x100u) != 0, "nbody_state.tuning = 0x%x is not 0 or an NBODY_TUNING(...) value",
-           s->tuning);
-    if (int r = check_tuning(int(s->tuning & 15u), int((s->tuning >> 4) & 3u), int((s->tuning >> 6) & 3u))) return r;
-  }
-  NB_ARG(s->first == 0 && s->count == s->sz, "%s needs the whole system (first = 0, count = sz), got [%u, %u+%u) of %u", who, s->first,
-         s->first, s->count, s->sz);
-  return NBODY_OK;
-}
-
 template <typename T, int D, int K>
 static int knn_launch(nbody_knn* h, const nbody_state* s, hipStream_t st) {
   const hermite_plan& p = h->plan;
-  auto* recs            = static_cast<knn_rec<T>*>(h->recs);
+  auto* recs            = static_cast<pair_rec<T>*>(h->recs);
   T* part_d             = static_cast<T*>(h->part);
   T* rho                = static_cast<T*>(h->rho);
-  hipLaunchKernelGGL((knn_pack_kernel<T, D>), dim3(h->padded / kHBlock), dim3(kHBlock), 0, st, static_cast<const T*>(s->m),
+  hipLaunchKernelGGL((pair_pack_kernel<T, D>), dim3(h->padded / kHBlock), dim3(kHBlock), 0, st, static_cast<const T*>(s->m),
                      static_cast<const T*>(s->x), recs, h->n, h->padded);
   NB_HIP(hipGetLastError());
   hipLaunchKernelGGL((knn_sweep_kernel<T, D, K>), dim3(p.blocks, p.chunks), dim3(kHBlock), 0, st, recs, part_d, h->part_j, h->n, p.ntiles,
@@ -408,20 +329,6 @@ static int knn_launch(nbody_knn* h, const nbody_state* s, hipStream_t st) {
   return NBODY_OK;
 }
 
-// the tail of the two blocking reads, after their argument checks: the device, then the state rules
-static int knn_read_ready(const nbody_knn* h, const char* who, hipStream_t st) {
-  if (int r = check_same_device(h->device, st, "nbody_knn")) return r;
-  if (capture_id(st) != 0) {
-    set_error("%s is blocking: it cannot be recorded (call it outside nbody_graph_begin/end)", who);
-    return NBODY_ERR_STATE;
-  }
-  if (!h->started) {
-    set_error("%s before nbody_knn_compute on this handle", who);
-    return NBODY_ERR_STATE;
-  }
-  return NBODY_OK;
-}
-
 }  // namespace nbody
 
 extern "C" int nbody_knn_create(nbody_knn** out, int dtype, int dim, uint32_t n, int k) {
@@ -429,34 +336,16 @@ extern "C" int nbody_knn_create(nbody_knn** out, int dtype, int dim, uint32_t n,
 }
 
 extern "C" int nbody_knn_create_on(nbody_knn** out, int dtype, int dim, uint32_t n, int k, int device) {
-  NB_ARG(out != nullptr, "out is NULL");
-  *out = nullptr;
-  NB_ARG(dtype == NBODY_F32 || dtype == NBODY_F64, "bad dtype %d", dtype);
-  NB_ARG(dim == 2 || dim == 3, "bad dim %d", dim);
-  NB_ARG(n >= 1 && n <= (1u << 28), "knn needs 1 <= n <= 2^28 (got %u)", n);
+  if (int r = hermite_create_check_args(out, dtype, dim, n, "knn")) return r;
   NB_ARG(k >= 1 && k <= kKnnMax, "knn needs 1 <= k <= %d (got %d)", kKnnMax, k);
-  if (captures_on_this_thread() != 0) {
-    set_error("nbody_knn_create allocates: it cannot be called between nbody_graph_begin and nbody_graph_end");
-    return NBODY_ERR_STATE;
-  }
-  int ndev = 0;
-  NB_HIP(hipGetDeviceCount(&ndev));
-  if (device < 0) device = current_device();
-  NB_ARG(device >= 0 && device < ndev, "device %d out of range (%d HIP devices visible)", device, ndev);
+  if (int r = hermite_create_check_device(&device, "knn")) return r;
   device_guard guard(device);
-  auto* h   = new nbody_knn;
-  h->device = device;
-  h->dtype  = dtype;
-  h->dim    = dim;
-  h->n      = n;
-  h->k      = k;
-  h->K      = k <= 4 ? 4 : k <= 8 ? 8 : 16;
-  h->tsz    = dtype == NBODY_F32 ? 4 : 8;
-  h->plan   = knn_plan_for(n);
-  h->padded = h->plan.ntiles * uint32_t(kHTile);
-  const size_t rows = size_t(h->plan.chunks) * size_t(n) * size_t(h->K);
+  auto* h = new nbody_knn;
+  h->k    = k;
+  h->K    = k <= 4 ? 4 : k <= 8 ? 8 : 16;
   // nothing is cleared: every compute writes all of it before it reads it
-  hipError_t e = hipMalloc(&h->recs, h->tsz * 4 * size_t(h->padded));
+  hipError_t e      = pair_handle_alloc(h, dtype, dim, n, device, knn_plan_for(n));
+  const size_t rows = size_t(h->plan.chunks) * size_t(n) * size_t(h->K);
   if (e == hipSuccess) e = hipMalloc(&h->part, h->tsz * rows);
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->part_j), sizeof(uint32_t) * rows);
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->idx), sizeof(uint32_t) * size_t(n) * size_t(k));
@@ -486,7 +375,7 @@ extern "C" void nbody_knn_destroy(nbody_knn* h) {
 }
 
 extern "C" int nbody_knn_compute(nbody_knn* h, const nbody_state* s, void* stream) {
-  if (int r = knn_check_state(s, "nbody_knn_compute")) return r;
+  if (int r = pair_check_state(s, "nbody_knn_compute")) return r;
   NB_ARG(h != nullptr, "nbody_knn is NULL");
   NB_ARG(h->dtype == s->dtype && h->dim == s->dim && h->n == s->sz,
          "nbody_knn was created for (dtype %d, dim %d, n %u), the state is (dtype %d, dim %d, sz %u)", h->dtype, h->dim, h->n, s->dtype,
@@ -511,7 +400,7 @@ extern "C" int nbody_knn_read(nbody_knn* h, int what, void* host_out, size_t byt
   const size_t need = what == 0 ? sizeof(uint32_t) * size_t(h->n) * size_t(h->k) : what == 1 ? h->tsz * size_t(h->n) * size_t(h->k) : h->tsz * size_t(h->n);
   NB_ARG(bytes == need, "nbody_knn_read(what = %d) needs %zu bytes, got %zu", what, need, bytes);
   const hipStream_t st = as_stream(stream);
-  if (int r = knn_read_ready(h, "nbody_knn_read", st)) return r;
+  if (int r = pair_read_ready(h, "nbody_knn", "nbody_knn_read", "nbody_knn_compute", st)) return r;
   device_guard guard(h->device);
   const void* src = what == 0 ? static_cast<const void*>(h->idx) : what == 1 ? h->d2 : h->rho;
   NB_HIP(hipMemcpyAsync(host_out, src, bytes, hipMemcpyDeviceToHost, st));
@@ -522,7 +411,7 @@ extern "C" int nbody_knn_read(nbody_knn* h, int what, void* host_out, size_t byt
 extern "C" int nbody_knn_density_centre(nbody_knn* h, void* centre_out, void* core_radius_out, void* core_density_out, void* stream) {
   NB_ARG(h != nullptr, "nbody_knn is NULL");
   const hipStream_t st = as_stream(stream);
-  if (int r = knn_read_ready(h, "nbody_knn_density_centre", st)) return r;
+  if (int r = pair_read_ready(h, "nbody_knn", "nbody_knn_density_centre", "nbody_knn_compute", st)) return r;
   device_guard guard(h->device);
   unsigned char raw[8 * kKnnSummaryLen];
   const size_t t = h->tsz;

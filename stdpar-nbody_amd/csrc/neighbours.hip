@@ -3,8 +3,7 @@
 // refused: the unsoftened potential's pair is the reference's m / (|d| + eps(T)), a different form).
 //
 // Definitions (T the state's type, D its dimension, e2 = fl_T(T(eps) * T(eps)), d = x_j - x_i):
-//   d2_ij   the UNSOFTENED squared distance as one FMA chain in component order: t = d_0 d_0, then t = fma(d_k, d_k, t).  Bitwise
-//           symmetric in (i, j): x_i - x_j is the exact negation of x_j - x_i.
+//   d2_ij   the UNSOFTENED squared distance, pair_d2 of pair_sweep.hpp: one FMA chain in component order, bitwise symmetric in (i, j).
 //   q_ij    d2_ij + e2 (one rounding).
 //   phi_i   -c S_i, S_i = sum_{j != i} m_j / sqrt(q_ij).  The self pair is excluded BY INDEX (its term would be m_i / eps, not 0);
 //           coincident distinct bodies contribute m_j / eps.  One reciprocal square root per pair: v_rsq_f64 polished to third order
@@ -16,13 +15,13 @@
 //           of lowest index among those with minimal nnd2, with its nn.  n = 1: (0xffffffff, 0xffffffff, +inf).
 //
 // Four launches per compute, all on the caller's stream, nothing allocated after nbody_neighbours_create:
-//   pack     one lane per record: {x[3], m} (4 T; 2D zero-fills component 2), padded with zero-mass records at the origin to whole
-//            tiles.  A padding record adds m y = 0 to S; it never becomes a neighbour because of an INDEX BOUND: every slice of 64
-//            records that reaches past n runs the checked batch body below, which replaces the d2 of a record j >= n by +inf.
-//   sweep    the hot path, the Hermite sweeps' shape (hermite_tile.hpp): R targets per lane in registers, records staged through LDS
-//            tiles of kHTile and read as wave-uniform broadcasts, every tile cut over the four waves of the block, the tiles cut over
-//            grid.y chunks by hermite_plan_for(sz, 2) — the sixth order's plan: a function of sz alone.  A lane carries S, the
-//            running minimum of d2 and its index.  The terms of a slice (64 records) are summed by themselves, in U interleaved
+//   pack     pair_sweep.hpp's: one lane per record {x[3], m}, padded with zero-mass records at the origin to whole tiles.  A padding
+//            record adds m y = 0 to S; it never becomes a neighbour because of an INDEX BOUND: every slice of 64 records that
+//            reaches past n runs the checked batch body below, which replaces the d2 of a record j >= n by +inf.
+//   sweep    the hot path, over pair_sweep_tiles of pair_sweep.hpp (the Hermite sweeps' shape): R targets per lane in registers,
+//            the tiles cut over grid.y chunks by hermite_plan_for(sz, 2) — the sixth order's plan: a function of sz alone; what
+//            is here is the pair batch, the slice and the merge of the block's waves.  A lane carries S, the running minimum of d2
+//            and its index.  The terms of a slice (64 records) are summed by themselves, in U interleaved
 //            chains joined pairwise, and the slice sums added up: one chain over a chunk lets a large term swallow the later ones
 //            (energy.hip: 8.4e-6 of the potential at N = 65 537 in float).
 //            Selection: a batch of U records takes U - 1 v_min and ONE compare of the batch's minimum against the running one per
@@ -30,9 +29,9 @@
 //            times in all) do the lanes walk the batch in index order, min and 32-bit select under the compare's mask.  The result
 //            is the same whichever way the branch goes.  The source index is wave-uniform (the wave number is read with
 //            v_readfirstlane), so the walk compares against and selects from a scalar.
-//            Two batch bodies, chosen per slice (wave-uniform): the CHECKED one masks the self pair (term 0, d2 +inf) and the padding
-//            (d2 +inf) by index and runs only for slices that overlap the block's own targets or reach past n — at most two of a
-//            wave's slices per chunk; every other slice runs the plain body, which has no index test at all.
+//            Two batch bodies, chosen per slice by pair_sweep_tiles: the CHECKED one masks the self pair (term 0, d2 +inf) and the
+//            padding (d2 +inf) by index and runs only for slices that overlap the block's own targets or reach past n — at most two
+//            of a wave's slices per chunk; every other slice runs the plain body, which has no index test at all.
 //            The block's waves merge through LDS: S added in wave order, (d2, index) lexicographically — a wave's slice of a later
 //            tile holds higher indices than another wave's slice of an earlier tile, so `<` on d2 alone would not keep the lowest
 //            index.  The chunk's raw results go to the partial arrays.
@@ -45,7 +44,7 @@
 // rule: two runs, an eager call and a replayed recorded one, and a handle destroyed and made again give the same bits.
 // Bound: FP64 / FP32 VALU issue, like the Hermite sweeps; per pair D subtractions, D chain operations, one add, the weight (5 + rsq
 // in double, 1 + rsq in float), one add into the slice sum and (U - 1) / U min + 1 / U compare.
-#include "hermite_tile.hpp"
+#include "pair_sweep.hpp"
 
 // every product that is meant to be fused below is written as an fma: m y in float rounds before it is added, whichever batch body
 // (with or without the self pair's select between the two) a slice runs
@@ -53,15 +52,7 @@
 
 namespace nbody {
 
-constexpr uint32_t kNoNeighbour = 0xffffffffu;
-constexpr int kNbClosestBlock   = 1024;
-
-// Source record of the sweep: {x[3], m}, D components used.  32 B in double (two ds_read_b128), 16 B in float (one).
-template <typename T>
-struct alignas(sizeof(T) * 4) nb_rec {
-  T p[3];
-  T m;
-};
+constexpr int kNbClosestBlock = 1024;
 
 template <typename T>
 struct nb_closest_rec {  // the handle's closest-pair record
@@ -75,54 +66,17 @@ struct nb_consts {
   __device__ __forceinline__ nb_consts() : k0375(T(0.375)) { asm volatile("" : "+s"(k0375)); }  // not an inline constant
 };
 
-template <typename T>
-__device__ __forceinline__ T nb_inf() {
-  return __builtin_huge_val();
-}
-
-// (d2, j) < (best, idx) lexicographically
-template <typename T>
-__device__ __forceinline__ void nb_merge(T& best, uint32_t& idx, T d2, uint32_t j) {
-  const bool take = d2 < best || (d2 == best && j < idx);
-  best            = take ? d2 : best;
-  idx             = take ? j : idx;
-}
-
-// ---- pack ----------------------------------------------------------------------------------------------------------------------
-template <typename T, int D>
-__global__ __launch_bounds__(kHBlock) void neighbours_pack_kernel(const T* __restrict__ m, const T* __restrict__ x, nb_rec<T>* __restrict__ recs,
-                                                                  uint32_t n, uint32_t padded) {
-  const uint32_t i = blockIdx.x * kHBlock + threadIdx.x;
-  if (i >= padded) return;
-  nb_rec<T> r;
-  r.p[0] = r.p[1] = r.p[2] = r.m = T(0);  // padding: zero mass at the origin (kept out of nn by the index bound of the checked slices)
-  if (i < n) {
-    r.m = m[i];
-#pragma unroll
-    for (int k = 0; k < D; ++k) r.p[k] = x[uint64_t(i) * D + k];
-  }
-  recs[i] = r;
-}
-
 // ---- the pair batch ------------------------------------------------------------------------------------------------------------
 // U records (global indices j0 ...) against the R targets of a lane (global indices ti[r]).  ls[b][r]: the slice's U sum chains.
 // CHECK: the self pair and the records j >= n are masked by index; without it the slice holds neither.
 template <typename T, int D, int R, int U, bool CHECK>
 __device__ __forceinline__ void nb_pair_batch(T (&ls)[U][R], T (&best)[R], uint32_t (&idx)[R], const T (&xi)[R][D], const uint32_t (&ti)[R],
-                                              const nb_rec<T> (&s)[U], uint32_t j0, uint32_t n, const nb_consts<T>& pc, T e2) {
+                                              const pair_rec<T> (&s)[U], uint32_t j0, uint32_t n, const nb_consts<T>& pc, T e2) {
   T d2[U][R], w[U][R];
 #pragma unroll
   for (int b = 0; b < U; ++b)
 #pragma unroll
-    for (int r = 0; r < R; ++r) {
-      T d[D];
-#pragma unroll
-      for (int k = 0; k < D; ++k) d[k] = s[b].p[k] - xi[r][k];
-      T t = d[0] * d[0];
-#pragma unroll
-      for (int k = 1; k < D; ++k) t = __builtin_elementwise_fma(d[k], d[k], t);
-      d2[b][r] = t;
-    }
+    for (int r = 0; r < R; ++r) d2[b][r] = pair_d2<T, D>(s[b].p, xi[r]);
 #pragma unroll
   for (int b = 0; b < U; ++b)
 #pragma unroll
@@ -147,7 +101,7 @@ __device__ __forceinline__ void nb_pair_batch(T (&ls)[U][R], T (&best)[R], uint3
       for (int r = 0; r < R; ++r) {
         const bool self = j == ti[r];
         w[b][r]         = self ? T(0) : w[b][r];
-        d2[b][r]        = (real && !self) ? d2[b][r] : nb_inf<T>();
+        d2[b][r]        = (real && !self) ? d2[b][r] : pair_inf<T>();
       }
     }
   }
@@ -179,7 +133,7 @@ __device__ __forceinline__ void nb_pair_batch(T (&ls)[U][R], T (&best)[R], uint3
 // One wave's slice of a tile: SUB records from src (LDS, wave-uniform addresses), global indices j0 ...; adds the slice's sum to S.
 template <typename T, int D, int R, int U, bool CHECK>
 __device__ __forceinline__ void nb_slice(T (&S)[R], T (&best)[R], uint32_t (&idx)[R], const T (&xi)[R][D], const uint32_t (&ti)[R],
-                                         const nb_rec<T>* src, uint32_t j0, uint32_t n, const nb_consts<T>& pc, T e2) {
+                                         const pair_rec<T>* src, uint32_t j0, uint32_t n, const nb_consts<T>& pc, T e2) {
   constexpr int SUB = kHTile / kHWaves;
   T ls[U][R];
 #pragma unroll
@@ -188,7 +142,7 @@ __device__ __forceinline__ void nb_slice(T (&S)[R], T (&best)[R], uint32_t (&idx
     for (int r = 0; r < R; ++r) ls[b][r] = T(0);
 #pragma unroll 1
   for (int jj = 0; jj < SUB; jj += U) {
-    nb_rec<T> s[U];  // field by field: a struct copy may be left in private memory by the compiler
+    pair_rec<T> s[U];  // field by field: a struct copy may be left in private memory by the compiler
 #pragma unroll
     for (int b = 0; b < U; ++b) {
 #pragma unroll
@@ -211,19 +165,16 @@ __device__ __forceinline__ void nb_slice(T (&S)[R], T (&best)[R], uint32_t (&idx
 // ---- sweep ---------------------------------------------------------------------------------------------------------------------
 // grid (blocks of 64 R targets, chunks).  part_s, part_d: T[chunk][n], part_j: uint32[chunk][n] — a chunk's raw S, minimum and index.
 template <typename T, int D, int R>
-__global__ __launch_bounds__(kHBlock) void neighbours_sweep_kernel(const nb_rec<T>* __restrict__ recs, T* __restrict__ part_s,
+__global__ __launch_bounds__(kHBlock) void neighbours_sweep_kernel(const pair_rec<T>* __restrict__ recs, T* __restrict__ part_s,
                                                                    T* __restrict__ part_d, uint32_t* __restrict__ part_j, T e2, uint32_t n,
                                                                    uint32_t ntiles, uint32_t tiles_per_chunk) {
-  constexpr int SUB = kHTile / kHWaves;              // records of a tile one wave takes
-  constexpr int U   = (sizeof(T) == 8 ? 2 : 4) / R;  // records a batch: 2 pairs in flight per lane in double, 4 in float
-  constexpr int NH  = (kHWaves - 1) * R * 64;        // the other waves' results, handed over through LDS
-  constexpr size_t kTileBytes = sizeof(nb_rec<T>) * kHTile, kHandBytes = (2 * sizeof(T) + sizeof(uint32_t)) * NH;
+  constexpr int U  = (sizeof(T) == 8 ? 2 : 4) / R;  // records a batch: 2 pairs in flight per lane in double, 4 in float
+  constexpr int NH = (kHWaves - 1) * R * 64;        // the other waves' results, handed over through LDS
+  constexpr size_t kTileBytes = sizeof(pair_rec<T>) * kHTile, kHandBytes = (2 * sizeof(T) + sizeof(uint32_t)) * NH;
   __shared__ __attribute__((aligned(64))) unsigned char smem[kTileBytes > kHandBytes ? kTileBytes : kHandBytes];
-  const nb_rec<T>* tile = reinterpret_cast<const nb_rec<T>*>(smem);
-  T* tflat              = reinterpret_cast<T*>(smem);
-  T* hand_s             = reinterpret_cast<T*>(smem);  // after the last tile has been consumed
-  T* hand_d             = hand_s + NH;
-  uint32_t* hand_j      = reinterpret_cast<uint32_t*>(hand_d + NH);
+  T* hand_s        = reinterpret_cast<T*>(smem);  // after the last tile has been consumed
+  T* hand_d        = hand_s + NH;
+  uint32_t* hand_j = reinterpret_cast<uint32_t*>(hand_d + NH);
 
   const int lane      = threadIdx.x & 63;
   const uint32_t wave = uint32_t(__builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)));  // in an SGPR: source indices stay scalar
@@ -237,36 +188,15 @@ __global__ __launch_bounds__(kHBlock) void neighbours_sweep_kernel(const nb_rec<
 #pragma unroll
     for (int k = 0; k < D; ++k) xi[r][k] = recs[i].p[k];
     S[r]    = T(0);
-    best[r] = nb_inf<T>();
+    best[r] = pair_inf<T>();
     idx[r]  = kNoNeighbour;
   }
   const uint32_t own0 = blockIdx.x * (64 * R), own1 = own0 + 64 * R;  // the block's own targets
 
-  const uint32_t t0 = blockIdx.y * tiles_per_chunk;
-  const uint32_t t1 = t0 + tiles_per_chunk < ntiles ? t0 + tiles_per_chunk : ntiles;
   const nb_consts<T> pc;
-
-  const T* flat = reinterpret_cast<const T*>(recs);
-  T stage[4];  // one record per lane, value by value
-  auto stage_load = [&](uint32_t t) {  // the record array is padded to whole tiles
-#pragma unroll
-    for (int k = 0; k < 4; ++k) stage[k] = flat[(uint64_t(t) * kHTile + threadIdx.x) * 4 + k];
-  };
-  stage_load(t0);
-  for (uint32_t t = t0; t < t1; ++t) {
-    __syncthreads();  // every wave is done reading the previous tile
-#pragma unroll
-    for (int k = 0; k < 4; ++k) tflat[threadIdx.x * 4 + k] = stage[k];
-    __syncthreads();
-    if (t + 1 < t1) stage_load(t + 1);  // in flight while this tile is consumed
-
-    const nb_rec<T>* src = &tile[wave * SUB];
-    const uint32_t j0    = t * kHTile + wave * SUB;
-    // wave-uniform: does the slice hold a target of this block (the self pair) or a record past n (padding)?
-    const bool checked = (j0 + SUB > n) | ((j0 < own1) & (j0 + SUB > own0));
-    if (checked) nb_slice<T, D, R, U, true>(S, best, idx, xi, ti, src, j0, n, pc, e2);
-    else nb_slice<T, D, R, U, false>(S, best, idx, xi, ti, src, j0, n, pc, e2);
-  }
+  pair_sweep_tiles<T>(recs, smem, wave, n, ntiles, tiles_per_chunk, own0, own1, [&](const pair_rec<T>* src, uint32_t j0, auto checked) {
+    nb_slice<T, D, R, U, decltype(checked)::value>(S, best, idx, xi, ti, src, j0, n, pc, e2);
+  });
 
   // the four slices: S in wave order, (d2, index) lexicographically
   __syncthreads();
@@ -287,7 +217,7 @@ __global__ __launch_bounds__(kHBlock) void neighbours_sweep_kernel(const nb_rec<
       for (int r = 0; r < R; ++r) {
         const int slot = ((p - 1) * R + r) * 64 + lane;
         S[r] += hand_s[slot];
-        nb_merge<T>(best[r], idx[r], hand_d[slot], hand_j[slot]);
+        pair_merge<T>(best[r], idx[r], hand_d[slot], hand_j[slot]);
       }
     const uint64_t row = uint64_t(blockIdx.y) * n;
 #pragma unroll
@@ -314,7 +244,7 @@ __global__ __launch_bounds__(kHBlock) void neighbours_finish_kernel(const T* __r
   for (uint32_t ch = 1; ch < chunks; ++ch) {
     const uint64_t e = uint64_t(ch) * n + i;
     S += part_s[e];
-    nb_merge<T>(best, idx, part_d[e], part_j[e]);
+    pair_merge<T>(best, idx, part_d[e], part_j[e]);
   }
   phi[i]  = -c * S;
   nn[i]   = idx;
@@ -329,14 +259,14 @@ __global__ __launch_bounds__(kNbClosestBlock) void neighbours_closest_kernel(con
                                                                              nb_closest_rec<T>* __restrict__ out, uint32_t n) {
   __shared__ T red_d[kNbClosestBlock / 64];
   __shared__ uint32_t red_i[kNbClosestBlock / 64];
-  T best       = nb_inf<T>();
+  T best       = pair_inf<T>();
   uint32_t idx = kNoNeighbour;
-  for (uint32_t i = threadIdx.x; i < n; i += kNbClosestBlock) nb_merge<T>(best, idx, nnd2[i], i);
+  for (uint32_t i = threadIdx.x; i < n; i += kNbClosestBlock) pair_merge<T>(best, idx, nnd2[i], i);
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     const T od        = __shfl_xor(best, off, 64);
     const uint32_t oi = __shfl_xor(idx, off, 64);
-    nb_merge<T>(best, idx, od, oi);
+    pair_merge<T>(best, idx, od, oi);
   }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) {
@@ -345,7 +275,7 @@ __global__ __launch_bounds__(kNbClosestBlock) void neighbours_closest_kernel(con
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    for (int w = 1; w < kNbClosestBlock / 64; ++w) nb_merge<T>(best, idx, red_d[w], red_i[w]);
+    for (int w = 1; w < kNbClosestBlock / 64; ++w) pair_merge<T>(best, idx, red_d[w], red_i[w]);
     nb_closest_rec<T> r;
     const uint32_t j = idx < n ? nn[idx] : kNoNeighbour;
     r.d2             = best;
@@ -359,7 +289,7 @@ __global__ __launch_bounds__(kNbClosestBlock) void neighbours_closest_kernel(con
 
 using namespace nbody;
 
-// started: nbody_neighbours_compute has run (host call order, which a recorded step replays).  recs: nb_rec<T>[padded]; part: the
+// started: nbody_neighbours_compute has run (host call order, which a recorded step replays).  recs: pair_rec<T>[padded]; part: the
 // chunks' S, T[chunks][n].
 struct nbody_neighbours : hermite_handle {
   void* part_d     = nullptr;  // T[chunks][n]: the chunks' minimum d2
@@ -372,32 +302,14 @@ struct nbody_neighbours : hermite_handle {
 
 namespace nbody {
 
-// check_state without the arrays this call never reads: v, a and ao may be NULL
-static int neighbours_check_state(const nbody_state* s, const char* who) {
-  NB_ARG(s != nullptr, "nbody_state is NULL");
-  NB_ARG(s->dtype == NBODY_F32 || s->dtype == NBODY_F64, "bad dtype %d", s->dtype);
-  NB_ARG(s->dim == 2 || s->dim == 3, "bad dim %d (must be 2 or 3)", s->dim);
-  NB_ARG(s->m && s->x, "nbody_state has a NULL array pointer (m, x)");
-  NB_ARG(uint64_t(s->first) + uint64_t(s->count) <= uint64_t(s->sz), "shard [%u, %u+%u) exceeds sz=%u", s->first, s->first, s->count,
-         s->sz);
-  if (s->tuning != 0) {
-    NB_ARG((s->tuning & ~0x1ffu) == 0 && (s->tuning & 0x100u) != 0, "nbody_state.tuning = 0x%x is not 0 or an NBODY_TUNING(...) value",
-           s->tuning);
-    if (int r = check_tuning(int(s->tuning & 15u), int((s->tuning >> 4) & 3u), int((s->tuning >> 6) & 3u))) return r;
-  }
-  NB_ARG(s->first == 0 && s->count == s->sz, "%s needs the whole system (first = 0, count = sz), got [%u, %u+%u) of %u", who, s->first,
-         s->first, s->count, s->sz);
-  return NBODY_OK;
-}
-
 template <typename T, int D, int R>
 static int neighbours_launch(nbody_neighbours* h, const nbody_state* s, T e2, hipStream_t st) {
   const hermite_plan& p = h->plan;
-  auto* recs            = static_cast<nb_rec<T>*>(h->recs);
+  auto* recs            = static_cast<pair_rec<T>*>(h->recs);
   T* part_s             = static_cast<T*>(h->part);
   T* part_d             = static_cast<T*>(h->part_d);
   T* nnd2               = static_cast<T*>(h->nnd2);
-  hipLaunchKernelGGL((neighbours_pack_kernel<T, D>), dim3(h->padded / kHBlock), dim3(kHBlock), 0, st, static_cast<const T*>(s->m),
+  hipLaunchKernelGGL((pair_pack_kernel<T, D>), dim3(h->padded / kHBlock), dim3(kHBlock), 0, st, static_cast<const T*>(s->m),
                      static_cast<const T*>(s->x), recs, h->n, h->padded);
   NB_HIP(hipGetLastError());
   hipLaunchKernelGGL((neighbours_sweep_kernel<T, D, R>), dim3(p.blocks, p.chunks), dim3(kHBlock), 0, st, recs, part_s, part_d, h->part_j,
@@ -412,20 +324,6 @@ static int neighbours_launch(nbody_neighbours* h, const nbody_state* s, T e2, hi
   return NBODY_OK;
 }
 
-// the tail of the two blocking reads, after their argument checks: the device, then the state rules
-static int neighbours_read_ready(const nbody_neighbours* h, const char* who, hipStream_t st) {
-  if (int r = check_same_device(h->device, st, "nbody_neighbours")) return r;
-  if (capture_id(st) != 0) {
-    set_error("%s is blocking: it cannot be recorded (call it outside nbody_graph_begin/end)", who);
-    return NBODY_ERR_STATE;
-  }
-  if (!h->started) {
-    set_error("%s before nbody_neighbours_compute on this handle", who);
-    return NBODY_ERR_STATE;
-  }
-  return NBODY_OK;
-}
-
 }  // namespace nbody
 
 extern "C" int nbody_neighbours_create(nbody_neighbours** out, int dtype, int dim, uint32_t n) {
@@ -435,17 +333,10 @@ extern "C" int nbody_neighbours_create(nbody_neighbours** out, int dtype, int di
 extern "C" int nbody_neighbours_create_on(nbody_neighbours** out, int dtype, int dim, uint32_t n, int device) {
   if (int r = hermite_create_check(out, dtype, dim, n, &device, "neighbours")) return r;
   device_guard guard(device);
-  auto* h   = new nbody_neighbours;
-  h->device = device;
-  h->dtype  = dtype;
-  h->dim    = dim;
-  h->n      = n;
-  h->tsz    = dtype == NBODY_F32 ? 4 : 8;
-  h->plan   = hermite_plan_for(n, 2);
-  h->padded = h->plan.ntiles * uint32_t(kHTile);
-  const size_t rows = size_t(h->plan.chunks) * size_t(n);
+  auto* h = new nbody_neighbours;
   // nothing is cleared: every compute writes all of it before it reads it
-  hipError_t e = hipMalloc(&h->recs, h->tsz * 4 * size_t(h->padded));
+  hipError_t e      = pair_handle_alloc(h, dtype, dim, n, device, hermite_plan_for(n, 2));
+  const size_t rows = size_t(h->plan.chunks) * size_t(n);
   if (e == hipSuccess) e = hipMalloc(&h->part, h->tsz * rows);
   if (e == hipSuccess) e = hipMalloc(&h->part_d, h->tsz * rows);
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->part_j), sizeof(uint32_t) * rows);
@@ -477,7 +368,7 @@ extern "C" void nbody_neighbours_destroy(nbody_neighbours* h) {
 }
 
 extern "C" int nbody_neighbours_compute(nbody_neighbours* h, const nbody_state* s, double eps, void* stream) {
-  if (int r = neighbours_check_state(s, "nbody_neighbours_compute")) return r;
+  if (int r = pair_check_state(s, "nbody_neighbours_compute")) return r;
   return dispatch(s->dtype, s->dim, [&](auto tg) {
     using T         = typename decltype(tg)::type;
     constexpr int D = decltype(tg)::dim;
@@ -498,7 +389,7 @@ extern "C" int nbody_neighbours_read(nbody_neighbours* h, int what, void* host_o
   const size_t need = (what == 1 ? sizeof(uint32_t) : h->tsz) * size_t(h->n);
   NB_ARG(bytes == need, "nbody_neighbours_read(what = %d) needs %zu bytes, got %zu", what, need, bytes);
   const hipStream_t st = as_stream(stream);
-  if (int r = neighbours_read_ready(h, "nbody_neighbours_read", st)) return r;
+  if (int r = pair_read_ready(h, "nbody_neighbours", "nbody_neighbours_read", "nbody_neighbours_compute", st)) return r;
   device_guard guard(h->device);
   const void* src = what == 0 ? h->phi : what == 1 ? static_cast<const void*>(h->nn) : h->nnd2;
   NB_HIP(hipMemcpyAsync(host_out, src, bytes, hipMemcpyDeviceToHost, st));
@@ -509,7 +400,7 @@ extern "C" int nbody_neighbours_read(nbody_neighbours* h, int what, void* host_o
 extern "C" int nbody_neighbours_closest_pair(nbody_neighbours* h, uint32_t* i, uint32_t* j, void* d2_out, void* stream) {
   NB_ARG(h != nullptr, "nbody_neighbours is NULL");
   const hipStream_t st = as_stream(stream);
-  if (int r = neighbours_read_ready(h, "nbody_neighbours_closest_pair", st)) return r;
+  if (int r = pair_read_ready(h, "nbody_neighbours", "nbody_neighbours_closest_pair", "nbody_neighbours_compute", st)) return r;
   device_guard guard(h->device);
   unsigned char raw[16];
   NB_HIP(hipMemcpyAsync(raw, h->closest, sizeof raw, hipMemcpyDeviceToHost, st));

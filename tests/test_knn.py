@@ -152,8 +152,9 @@ def _load_tool(name):
 
 
 def test_knn_kernels_do_not_spill_and_the_sweep_has_no_transcendental(nb):
-    """Every knn_*_kernel: private segment 0 and no scratch_ instruction; the sweep exists per (dtype, dim, list capacity) and has no
-    v_rsq, v_rcp, v_sqrt or v_div_*: only finish and summary may divide or take a root (pack has none either)."""
+    """Every knn_*_kernel and the pack kernel (csrc/pair_sweep.hpp's, shared with neighbours): private segment 0 and no scratch_
+    instruction; the sweep exists per (dtype, dim, list capacity) and has no v_rsq, v_rcp, v_sqrt or v_div_*: only finish and summary
+    may divide or take a root (pack has none either)."""
     if not os.path.exists(OBJDUMP):
         pytest.skip("llvm-objdump not available")
     kr = _load_tool("kernel_resources")
@@ -162,7 +163,7 @@ def test_knn_kernels_do_not_spill_and_the_sweep_has_no_transcendental(nb):
     seen = {"pack": set(), "sweep": set(), "finish": set(), "summary": set()}
     for k, n in zip(ks, names):
         assert not re.search(r"neighbours_\w*knn|knn_\w*neighbours", n)
-        m = re.search(r"nbody::knn_(\w+)_kernel<(float|double)(?:, (\d+))?(?:, (\d+))?>", n)
+        m = re.search(r"nbody::(?:knn|pair)_(\w+)_kernel<(float|double)(?:, (\d+))?(?:, (\d+))?>", n)
         if not m:
             assert "knn_" not in n, f"a knn kernel with an unexpected name: {n}"
             continue
@@ -175,7 +176,7 @@ def test_knn_kernels_do_not_spill_and_the_sweep_has_no_transcendental(nb):
     assert seen["pack"] == {(t, d) for t in types for d in (2, 3)}, sorted(seen["pack"])
     assert seen["summary"] == {(t, d) for t in types for d in (2, 3)}, sorted(seen["summary"])
     sm = _load_tool("check_smem_pipeline")
-    funcs = {n: c for n, c in sm.functions(sm.disassemble(nb.LIB_PATH)).items() if re.search(r"knn_\w+_kernel", n) and c}
+    funcs = {n: c for n, c in sm.functions(sm.disassemble(nb.LIB_PATH)).items() if re.search(r"(knn_\w+|pair_pack)_kernel", n) and c}
     assert len(funcs) == 12 + 12 + 4 + 4, sorted(funcs)
     for name, code in funcs.items():
         text = "\n".join(ins for _, ins, _ in code)

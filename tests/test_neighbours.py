@@ -147,8 +147,9 @@ def _disassembly(nb):
 
 
 def test_neighbours_kernels_neither_spill_nor_divide(nb):
-    """Every new kernel: private segment 0, no scratch_ instruction, no v_div_*; the sweep exists per (dtype, dim, targets per lane)
-    and its only transcendental is the reciprocal square root (no v_rcp, no v_sqrt); the other kernels have none."""
+    """Every kernel of a compute (the pack kernel is csrc/pair_sweep.hpp's, shared with kNN): private segment 0, no scratch_
+    instruction, no v_div_*; the sweep exists per (dtype, dim, targets per lane) and its only transcendental is the reciprocal square
+    root (no v_rcp, no v_sqrt); the other kernels have none."""
     if not os.path.exists(OBJDUMP):
         pytest.skip("llvm-objdump not available")
     import importlib.util
@@ -159,7 +160,7 @@ def test_neighbours_kernels_neither_spill_nor_divide(nb):
     names = kr.demangle([k["symbol"].replace(".kd", "") for k in ks])
     sweeps, others = set(), set()
     for k, n in zip(ks, names):
-        m = re.search(r"nbody::neighbours_(pack|sweep|finish|closest)_kernel<(float|double)(?:, (\d))?(?:, (\d))?>", n)
+        m = re.search(r"nbody::(?:pair|neighbours)_(pack|sweep|finish|closest)_kernel<(float|double)(?:, (\d))?(?:, (\d))?>", n)
         if not m:
             continue
         assert int(k.get("private_segment_fixed_size", 0)) == 0, (n, k)
@@ -169,7 +170,7 @@ def test_neighbours_kernels_neither_spill_nor_divide(nb):
             others.add((m.group(1), m.group(2)))
     assert sweeps == {(t, d, r) for t in ("float", "double") for d in (2, 3) for r in (1, 2)}, sorted(sweeps)
     assert others == {(k, t) for k in ("pack", "finish", "closest") for t in ("float", "double")}, sorted(others)
-    funcs = {n: c for n, c in _disassembly(nb).items() if re.search(r"neighbours_(pack|sweep|finish|closest)_kernel", n) and c}
+    funcs = {n: c for n, c in _disassembly(nb).items() if re.search(r"(pair|neighbours)_(pack|sweep|finish|closest)_kernel", n) and c}
     assert len(funcs) == 8 + 4 + 2 + 2, sorted(funcs)
     for name, code in funcs.items():
         text = "\n".join(ins for _, ins, _ in code)

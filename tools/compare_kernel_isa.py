@@ -6,9 +6,11 @@ offsets, symbol comments and the s_nop padding behind a function's last instruct
 next, not to the function), and for every kernel symbol present in both reports whether its instruction text is identical.  Used to
 show that a change which adds kernels left the existing ones as they were.
 
-    python tools/compare_kernel_isa.py OLD.so NEW.so [-v]
+    python tools/compare_kernel_isa.py OLD.so NEW.so [-v] [--rename OLD_TEXT=NEW_TEXT ...]
 
-Prints one summary line; exit status 1 if any common kernel differs (-v lists them, and the symbols found in one build only)."""
+Prints one summary line; exit status 1 if any common kernel differs (-v lists them, and the symbols found in one build only).
+--rename replaces OLD_TEXT in the old build's symbols first: a type that was renamed changes the mangled name of every kernel that
+takes it (--rename 7knn_rec=8pair_rec), and without this such kernels would be listed as gone and new instead of being compared."""
 import os
 import re
 import subprocess
@@ -53,8 +55,10 @@ def kernels(lib_path):
     return {n: tuple(v) for n, v in out.items() if v}
 
 
-def compare(old_path, new_path):
+def compare(old_path, new_path, renames=()):
     a, b = kernels(old_path), kernels(new_path)
+    for old, new in renames:
+        a = {n.replace(old, new): v for n, v in a.items()}
     common = sorted(set(a) & set(b))
     differ = [n for n in common if a[n] != b[n]]
     return common, differ, sorted(set(a) - set(b)), sorted(set(b) - set(a))
@@ -64,7 +68,8 @@ def main():
     if len(sys.argv) < 3:
         print(__doc__)
         return 2
-    common, differ, gone, added = compare(sys.argv[1], sys.argv[2])
+    renames = [tuple(sys.argv[i + 1].split("=", 1)) for i, arg in enumerate(sys.argv[:-1]) if arg == "--rename"]
+    common, differ, gone, added = compare(sys.argv[1], sys.argv[2], renames)
     print(f"{len(common)} kernels in both builds: {len(common) - len(differ)} identical, {len(differ)} differ; "
           f"{len(gone)} only in the old build, {len(added)} only in the new")
     if "-v" in sys.argv:
