@@ -1816,37 +1816,6 @@ __global__ __launch_bounds__(kOC) void ot_owned_scatter_kernel(const uint32_t* _
   if (own) owned[block_offsets[blockIdx.x] + wfirst[wave] + uint32_t(__builtin_popcountll(b & ((1ull << lane) - 1ull)))] = body;
 }
 
-// One body per 2^D lanes.  When a node is opened its 2^D children are examined side by side, one per lane (their records
-// are contiguous), the ones to open are pushed on the body's stack in LDS in reverse child order and the walk continues
-// with the popped one — the order of the reference's walk.  The dependent chain of a body is the number of nodes it OPENS
-// (~180 at N = 10^6, theta 0.5), not the number it visits (~1430).  Each lane sums the terms of its own child slots and
-// the 2^D partial sums are combined at the end in a fixed order: the summation order differs from the reference's
-// (tolerance parity), the set of tests, accepted terms and therefore the counters do not, and the result of a body
-// depends on nothing but the tree and that body (so it is independent of the shard window).
-// ot_force_softened_kernel: the walk of nbody_octree_compute_softened_force — the same tests in the same order, the accepted term
-// ot_accumulate_soft.
-template <typename T, int D, bool COUNT>
-__global__ __launch_bounds__(64) void ot_force_kernel(const ot_node<T>* __restrict__ rootrec, const ot_group<T, D>* __restrict__ groups,
-                                                      const uint32_t* __restrict__ list,
-                                                      uint32_t nlist, const T* __restrict__ x, T* __restrict__ a, T c,
-                                                      uint32_t first, T theta, uint32_t capacity, const T* __restrict__ root,
-                                                      uint32_t* __restrict__ flags, uint32_t* __restrict__ counters) {
-  [[maybe_unused]] constexpr T e2 = T(0);
-#define OT_SOFT false
-#include "ot_walk_body.inc"
-#undef OT_SOFT
-}
-template <typename T, int D, bool COUNT>
-__global__ __launch_bounds__(64) void ot_force_softened_kernel(const ot_node<T>* __restrict__ rootrec,
-                                                               const ot_group<T, D>* __restrict__ groups, const uint32_t* __restrict__ list,
-                                                               uint32_t nlist, const T* __restrict__ x, T* __restrict__ a, T c,
-                                                               uint32_t first, T theta, uint32_t capacity, const T* __restrict__ root,
-                                                               uint32_t* __restrict__ flags, uint32_t* __restrict__ counters, T e2) {
-#define OT_SOFT true
-#include "ot_walk_body.inc"
-#undef OT_SOFT
-}
-
 // ---- quadrupole moments (nbody_octree_compute_quadrupoles, nbody_octree_compute_quadrupole_force; no reference counterpart) ----
 // Q(cell) = sum over its children c, in child order, empty ones skipped, of Q_c + m_c (3 d d^T - |d|^2 I), d = p_c - p(cell); a body
 // leaf has Q = 0.  2D takes the same formula in the plane (the 3D tensor restricted to z = 0: not traceless, and it need not be).
@@ -2028,23 +1997,6 @@ __device__ __forceinline__ void ot_accumulate_quad(bool on, T (&acc)[D], const T
   for (int k = 0; k < D; ++k) acc[k] += ((s * u[k] - qu[k]) * y2) * y2;
 }
 
-// ot_force_quadrupole_kernel: the walk of nbody_octree_compute_quadrupole_force — ot_force_kernel's tests, order and monopole terms,
-// and the quadrupole term of every accepted cell.
-template <typename T, int D, bool COUNT>
-__global__ __launch_bounds__(64) void ot_force_quadrupole_kernel(const ot_node<T>* __restrict__ rootrec,
-                                                                 const ot_group<T, D>* __restrict__ groups, const uint32_t* __restrict__ list,
-                                                                 uint32_t nlist, const T* __restrict__ x, T* __restrict__ a, T c,
-                                                                 uint32_t first, T theta, uint32_t capacity, const T* __restrict__ root,
-                                                                 uint32_t* __restrict__ flags, uint32_t* __restrict__ counters,
-                                                                 const T* __restrict__ quad) {
-  [[maybe_unused]] constexpr T e2 = T(0);
-#define OT_SOFT false
-#define OT_QUAD
-#include "ot_walk_body.inc"
-#undef OT_QUAD
-#undef OT_SOFT
-}
-
 // ---- per-body potentials (nbody_octree_compute_*potential, nbody_octree_calc_energies; no reference counterpart) ----------------
 // S_i = the sum over body i's walk of the accepted terms, phi_i = -c S_i, and PE = -c/2 sum_i m_i S_i: System::calc_energies
 // (src/system.h:62-79) with the inner sum taken from the tree.  Unlike the force, whose self term is 0 * d, the potential's is
@@ -2154,21 +2106,208 @@ __device__ __forceinline__ void ot_potential_quad(bool on, T& s, const T (&dj)[D
   s += ((T(0.5) * uqu) * (y * y)) * y;
 }
 
-// The potential walks: ot_force_kernel's, ot_force_softened_kernel's and ot_force_quadrupole_kernel's tests in the same order, the
-// same per-slot partial sums combined in the same order; phi[body - first] = scale * S (scale -c for phi, 1 for the energies).
-// With counters on they write the force walk's counters.
+// ---- the compiler-scheduled walk (walk form 1) and its six kernels ---------------------------------------------------------------
+// Which accepted term a walk adds: the monopole, the Plummer-softened monopole (e2), or the monopole and every accepted cell's
+// quadrupole (quad, after nbody_octree_compute_quadrupoles).  Also the host's name for the walk (ot_force_run, ot_potential_run).
+enum ot_kind { kOtMono = 0, kOtSoft = 1, kOtQuad = 2 };
+
+// The accepted terms of a walk as a type, which owns the per-lane sums: zero(); node(), the monopole term of an accepted node for the
+// lanes in `on` (on_mask: their ballot); cell(), the quadrupole of an accepted cell, node number `node` of the quadrupole array (nothing
+// unless KIND is kOtQuad: leaves have none, and a round that accepts no cell loads nothing more); combine(), one __shfl_xor step over
+// the 2^D lanes of a body; store(), row k of the output = the sum scaled.  The force: acc[D], a = c * acc.
+template <typename T, int D, ot_kind KIND>
+struct ot_force_terms {
+  T* __restrict__ a;
+  T c, e2;
+  const T* __restrict__ quad;
+  T acc[D];
+  pair_consts<T> pc;
+  __device__ __forceinline__ void zero() {
+#pragma unroll
+    for (int k = 0; k < D; ++k) acc[k] = T(0);
+  }
+  __device__ __forceinline__ void node(bool on, uint64_t on_mask, const T (&di)[D], T m, T d2f, T y0) {
+    if constexpr (KIND == kOtSoft) ot_accumulate_soft<T, D>(on, acc, di, m, e2, pc);
+    else ot_accumulate<T, D>(on, on_mask, acc, di, m, d2f, y0, pc);
+  }
+  __device__ __forceinline__ void cell(bool on, const T (&di)[D], T d2f, T y0, uint32_t node) {
+    if constexpr (KIND == kOtQuad)
+      if (__builtin_amdgcn_ballot_w64(on) != 0ull)
+        ot_accumulate_quad<T, D>(on, acc, di, d2f, y0, quad + (uint64_t(node) * uint32_t(kOtQS<D>)));
+  }
+  __device__ __forceinline__ void combine(int off) {
+#pragma unroll
+    for (int k = 0; k < D; ++k) acc[k] += __shfl_xor(acc[k], off, 64);
+  }
+  __device__ __forceinline__ void store(uint64_t k) const {
+#pragma unroll
+    for (int j = 0; j < D; ++j) a[k * D + j] = c * acc[j];
+  }
+};
+
+// The potential: one scalar sum S per lane (ot_potential_term, ot_potential_soft, ot_potential_quad), phi = scale * S (scale -c for
+// phi, 1 for the energies).
+template <typename T, int D, ot_kind KIND>
+struct ot_potential_terms {
+  T* __restrict__ phi;
+  T scale, e2;
+  const T* __restrict__ quad;
+  T pot;
+  __device__ __forceinline__ void zero() { pot = T(0); }
+  __device__ __forceinline__ void node(bool on, uint64_t on_mask, const T (&di)[D], T m, T d2f, T y0) {
+    if constexpr (KIND == kOtSoft) ot_potential_soft<T, D>(on, pot, di, m, e2);
+    else ot_potential_term<T, D>(on, on_mask, pot, di, m, d2f, y0);
+  }
+  __device__ __forceinline__ void cell(bool on, const T (&di)[D], T d2f, T y0, uint32_t node) {
+    if constexpr (KIND == kOtQuad)
+      if (__builtin_amdgcn_ballot_w64(on) != 0ull)
+        ot_potential_quad<T, D>(on, pot, di, d2f, y0, quad + (uint64_t(node) * uint32_t(kOtQS<D>)));
+  }
+  __device__ __forceinline__ void combine(int off) { pot += __shfl_xor(pot, off, 64); }
+  __device__ __forceinline__ void store(uint64_t k) const { phi[k] = scale * pot; }
+};
+
+// One body per 2^D lanes.  When a node is opened its 2^D children are examined side by side, one per lane (their records
+// are contiguous), the ones to open are pushed on the body's stack in LDS in reverse child order and the walk continues
+// with the popped one — the order of the reference's walk.  The dependent chain of a body is the number of nodes it OPENS
+// (~180 at N = 10^6, theta 0.5), not the number it visits (~1430).  Each lane sums the terms of its own child slots and
+// the 2^D partial sums are combined at the end in a fixed order: the summation order differs from the reference's
+// (tolerance parity), the set of tests, accepted terms and therefore the counters do not, and the result of a body
+// depends on nothing but the tree and that body (so it is independent of the shard window).
+// The walk knows no kind of term: the tests, their order, the pushes, the exits and the counters are the same for every Terms.
+template <typename T, int D, bool COUNT, typename Terms>
+__device__ __forceinline__ void ot_walk(Terms terms, const ot_node<T>* __restrict__ rootrec, const ot_group<T, D>* __restrict__ groups,
+                                        const uint32_t* __restrict__ list, uint32_t nlist, const T* __restrict__ x, uint32_t first,
+                                        T theta, uint32_t capacity, const T* __restrict__ root, uint32_t* __restrict__ flags,
+                                        uint32_t* __restrict__ counters) {
+  constexpr uint32_t NCH   = 1u << D;
+  constexpr uint32_t GPW   = 64u / NCH;                         // bodies per wave
+  constexpr uint32_t DEPTH = (NCH - 1u) * kMaxLevels<D> + NCH;  // a pop frees one slot, an open adds <= 2^D
+  __shared__ uint32_t stack[GPW][DEPTH];
+  const uint32_t g = threadIdx.x / NCH, cc = threadIdx.x % NCH;
+  // `list`: the owned bodies in key order (neighbours share most of their walk: cache); XCD-contiguous blocks
+  const uint32_t t    = ot_xcd_contiguous_block(blockIdx.x, gridDim.x) * GPW + g;
+  const bool valid    = t < nlist;
+  const uint32_t body = valid ? list[t] : first;
+  const ot_theta<T> th(theta);
+  const T root_side = root[D];
+  T xi[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) xi[k] = valid ? x[uint64_t(body) * D + k] : T(0);
+  terms.zero();
+  uint32_t c_nodes = 0, c_terms = 0;
+  uint32_t cur = 0, sp = 0;
+  bool more = false;
+  if (valid) {  // the root is examined alone (by every lane of the group; lane 0 keeps the result)
+    const ot_node<T> nd = *rootrec;
+    T di[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) di[k] = nd.p[k] - xi[k];
+    const T d2f     = ot_dist2_fused<T, D>(di);
+    const T y0      = ot_rsq(d2f);
+    const bool leaf = nd.fc >= kOtBody;  // kOtBody or kOtEmpty
+    const bool take = leaf || ot_accept<T, D>(!leaf, root_side, di, y0, th);
+    {
+      const bool on0 = take && cc == 0;  // the root is examined by every lane of the group; lane 0 keeps the result
+      const uint64_t m0 = __builtin_amdgcn_ballot_w64(on0);
+      if (m0 != 0ull) terms.node(on0, m0, di, nd.m, d2f, y0);
+      terms.cell(on0 && !leaf, di, d2f, y0, 0u);  // an accepted root cell: its quadrupole is node 0's slot
+    }
+    if (COUNT && cc == 0) {
+      c_nodes = 1;
+      c_terms = take;
+    }
+    more = !take;
+    cur  = nd.fc;  // the root's stored fc is already a sibling-group number, like every fl[][0] below
+  }
+  uint32_t guard = capacity;  // a well-formed tree is left after < capacity steps; never spin on a damaged one
+  while (more && guard-- != 0u) {  // the lanes of a group leave together
+    const ot_node<T> nd = groups[cur].load(cc);  // this lane's child: two or three 16-/8-byte loads
+    T di[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) di[k] = nd.p[k] - xi[k];
+    const T d2f     = ot_dist2_fused<T, D>(di);
+    const T y0      = ot_rsq(d2f);
+    const bool leaf = nd.fc >= kOtBody;
+    const bool take = leaf || ot_accept<T, D>(!leaf, ot_ldexp(root_side, -int(nd.lvl)), di, y0, th);
+    if (COUNT) {
+      ++c_nodes;
+      c_terms += take;
+    }
+    const uint64_t take_mask = __builtin_amdgcn_ballot_w64(take);
+    if (take_mask != 0ull) terms.node(take, take_mask, di, nd.m, d2f, y0);
+    terms.cell(take && !leaf, di, d2f, y0, 1u + cur * NCH + cc);
+    const uint32_t open_mask = uint32_t((__ballot(!take) >> (g * NCH)) & ((1ull << NCH) - 1ull));
+    if (sp + uint32_t(__builtin_popcount(open_mask)) > DEPTH) {  // only below the key depth can a walk hold this many
+      if (cc == 0) atomicOr(flags, kFlagStack);                  // pending nodes; reported by nbody_octree_info
+      break;
+    }
+    if (!take) stack[g][sp + uint32_t(__builtin_popcount(open_mask >> (cc + 1u)))] = nd.fc;  // reverse child order
+    sp += uint32_t(__builtin_popcount(open_mask));
+    if (sp == 0u) break;
+    __builtin_amdgcn_wave_barrier();  // one lane pushed, all lanes of the group pop: keep the LDS write before the read
+    cur = stack[g][--sp];
+    __builtin_amdgcn_wave_barrier();  // ... and this read before the next round's push into the same slot
+  }
+  if (more && guard == 0xffffffffu && cc == 0) atomicOr(flags, kFlagWalk);  // step budget spent: the tree is damaged
+  // combine the 2^D partial sums of a body (fixed order)
+#pragma unroll
+  for (uint32_t off = NCH / 2; off > 0; off >>= 1) {
+    terms.combine(int(off));
+    if (COUNT) {
+      c_nodes += __shfl_xor(c_nodes, int(off), 64);
+      c_terms += __shfl_xor(c_terms, int(off), 64);
+    }
+  }
+  if (valid && cc == 0) {
+    terms.store(uint64_t(body - first));
+    if (COUNT) {
+      counters[uint64_t(body) * 2 + 0] = c_nodes;
+      counters[uint64_t(body) * 2 + 1] = c_terms;
+    }
+  }
+}
+
+// The six kernels: one signature (with e2 or quad behind it), one call each.  ot_force_softened_kernel is the walk of
+// nbody_octree_compute_softened_force and of the octree block steps, ot_force_quadrupole_kernel that of
+// nbody_octree_compute_quadrupole_force.
+template <typename T, int D, bool COUNT>
+__global__ __launch_bounds__(64) void ot_force_kernel(const ot_node<T>* __restrict__ rootrec, const ot_group<T, D>* __restrict__ groups,
+                                                      const uint32_t* __restrict__ list,
+                                                      uint32_t nlist, const T* __restrict__ x, T* __restrict__ a, T c,
+                                                      uint32_t first, T theta, uint32_t capacity, const T* __restrict__ root,
+                                                      uint32_t* __restrict__ flags, uint32_t* __restrict__ counters) {
+  ot_walk<T, D, COUNT>(ot_force_terms<T, D, kOtMono>{a, c}, rootrec, groups, list, nlist, x, first, theta, capacity, root, flags, counters);
+}
+template <typename T, int D, bool COUNT>
+__global__ __launch_bounds__(64) void ot_force_softened_kernel(const ot_node<T>* __restrict__ rootrec,
+                                                               const ot_group<T, D>* __restrict__ groups, const uint32_t* __restrict__ list,
+                                                               uint32_t nlist, const T* __restrict__ x, T* __restrict__ a, T c,
+                                                               uint32_t first, T theta, uint32_t capacity, const T* __restrict__ root,
+                                                               uint32_t* __restrict__ flags, uint32_t* __restrict__ counters, T e2) {
+  ot_walk<T, D, COUNT>(ot_force_terms<T, D, kOtSoft>{a, c, e2}, rootrec, groups, list, nlist, x, first, theta, capacity, root, flags,
+                       counters);
+}
+template <typename T, int D, bool COUNT>
+__global__ __launch_bounds__(64) void ot_force_quadrupole_kernel(const ot_node<T>* __restrict__ rootrec,
+                                                                 const ot_group<T, D>* __restrict__ groups, const uint32_t* __restrict__ list,
+                                                                 uint32_t nlist, const T* __restrict__ x, T* __restrict__ a, T c,
+                                                                 uint32_t first, T theta, uint32_t capacity, const T* __restrict__ root,
+                                                                 uint32_t* __restrict__ flags, uint32_t* __restrict__ counters,
+                                                                 const T* __restrict__ quad) {
+  ot_walk<T, D, COUNT>(ot_force_terms<T, D, kOtQuad>{a, c, T(0), quad}, rootrec, groups, list, nlist, x, first, theta, capacity, root,
+                       flags, counters);
+}
+// The potential walks: the three force walks' tests in the same order, the same per-slot partial sums combined in the same order;
+// phi[body - first] = scale * S.  With counters on they write the force walk's counters.
 template <typename T, int D, bool COUNT>
 __global__ __launch_bounds__(64) void ot_potential_kernel(const ot_node<T>* __restrict__ rootrec, const ot_group<T, D>* __restrict__ groups,
                                                           const uint32_t* __restrict__ list, uint32_t nlist, const T* __restrict__ x,
                                                           T* __restrict__ phi, T scale, uint32_t first, T theta, uint32_t capacity,
                                                           const T* __restrict__ root, uint32_t* __restrict__ flags,
                                                           uint32_t* __restrict__ counters) {
-  [[maybe_unused]] constexpr T e2 = T(0);
-#define OT_SOFT false
-#define OT_POT
-#include "ot_walk_body.inc"
-#undef OT_POT
-#undef OT_SOFT
+  ot_walk<T, D, COUNT>(ot_potential_terms<T, D, kOtMono>{phi, scale}, rootrec, groups, list, nlist, x, first, theta, capacity, root,
+                       flags, counters);
 }
 template <typename T, int D, bool COUNT>
 __global__ __launch_bounds__(64) void ot_potential_softened_kernel(const ot_node<T>* __restrict__ rootrec,
@@ -2177,11 +2316,8 @@ __global__ __launch_bounds__(64) void ot_potential_softened_kernel(const ot_node
                                                                    const T* __restrict__ x, T* __restrict__ phi, T scale, uint32_t first,
                                                                    T theta, uint32_t capacity, const T* __restrict__ root,
                                                                    uint32_t* __restrict__ flags, uint32_t* __restrict__ counters, T e2) {
-#define OT_SOFT true
-#define OT_POT
-#include "ot_walk_body.inc"
-#undef OT_POT
-#undef OT_SOFT
+  ot_walk<T, D, COUNT>(ot_potential_terms<T, D, kOtSoft>{phi, scale, e2}, rootrec, groups, list, nlist, x, first, theta, capacity, root,
+                       flags, counters);
 }
 template <typename T, int D, bool COUNT>
 __global__ __launch_bounds__(64) void ot_potential_quadrupole_kernel(const ot_node<T>* __restrict__ rootrec,
@@ -2191,14 +2327,8 @@ __global__ __launch_bounds__(64) void ot_potential_quadrupole_kernel(const ot_no
                                                                      uint32_t first, T theta, uint32_t capacity,
                                                                      const T* __restrict__ root, uint32_t* __restrict__ flags,
                                                                      uint32_t* __restrict__ counters, const T* __restrict__ quad) {
-  [[maybe_unused]] constexpr T e2 = T(0);
-#define OT_SOFT false
-#define OT_QUAD
-#define OT_POT
-#include "ot_walk_body.inc"
-#undef OT_POT
-#undef OT_QUAD
-#undef OT_SOFT
+  ot_walk<T, D, COUNT>(ot_potential_terms<T, D, kOtQuad>{phi, scale, T(0), quad}, rootrec, groups, list, nlist, x, first, theta,
+                       capacity, root, flags, counters);
 }
 
 // the accepted term's weight for d2 >= 2^-46 (ot_accumulate's far form, same operations in the same order); v[60:61] = mass
@@ -2771,6 +2901,11 @@ using namespace nbody;
 
 namespace nbody {
 
+// the flags word (kFlagDepth ... of the build, kFlagStack and kFlagWalk of the walks): behind the level counts and the deep groups
+static uint32_t* ot_flags(const nbody_octree* t) { return t->lvl_count + ((t->dim == 3 ? kMaxLevels<3> : kMaxLevels<2>) + 2); }
+// the tree is built in one pass over the sorted keys (build form 3, which 0 = auto selects)
+static bool ot_one_pass(const nbody_octree* t) { return t->build == 0 || t->build == 3; }
+
 static int ot_check(const nbody_octree* t, const nbody_state* s, void* stream) {
   NB_ARG(t != nullptr, "nbody_octree is NULL");
   if (int r = check_state(s)) return r;
@@ -2802,8 +2937,8 @@ static int ot_insert_run(nbody_octree* t, const nbody_state* s, hipStream_t st) 
   constexpr uint32_t NCH = 1u << D;
   const uint32_t n       = s->sz;
   const ot_tree<T, D> tree{static_cast<ot_group<T, D>*>(t->groups), static_cast<ot_node<T>*>(t->rootrec)};
-  if (n <= kSmallN && (t->build == 0 || t->build == 3)) {  // one block does everything up to the cells
-    uint32_t* flags = t->lvl_count + (kMaxLevels<D> + 2);
+  if (n <= kSmallN && ot_one_pass(t)) {  // one block does everything up to the cells
+    uint32_t* flags = ot_flags(t);
     const ot_lcp_args<T, D> args{t->keys[0], t->idx[0], n, t->lcp, t->plocal, t->bsum, t->rankpos, static_cast<const T*>(s->m),
                                  static_cast<const T*>(s->x), tree, t->cells, t->tops, t->lvl_count, flags, t->capacity, t->max_cells};
     hipLaunchKernelGGL((ot_insert_small_kernel<T, D>), dim3(1), dim3(kSmallB), 0, st, args, static_cast<const T*>(t->root), t->keys[0],
@@ -2818,8 +2953,8 @@ static int ot_insert_run(nbody_octree* t, const nbody_state* s, hipStream_t st) 
   int fin = 0;
   if (int r = radix_sort_pairs(t->keys, t->idx, n, D == 3 ? 63 : 64, t->hist, st, &fin)) return r;
   t->sorted_buf = fin;
-  uint32_t* flags = t->lvl_count + (kMaxLevels<D> + 2);
-  if (t->build == 0 || t->build == 3) {  // one pass over the sorted keys: 4 launches whatever the depth
+  uint32_t* flags = ot_flags(t);
+  if (ot_one_pass(t)) {  // one pass over the sorted keys: 4 launches whatever the depth
     const uint32_t nblk = n / kLcpB + 1;  // positions 0 ... n
     hipLaunchKernelGGL((ot_lcp_kernel<D>), dim3(nblk), dim3(kLcpB), 0, st, t->keys[fin], n, t->lcp, t->plocal, t->bsum, t->bhist);
     NB_HIP(hipGetLastError());
@@ -2889,7 +3024,7 @@ static int ot_tree_run(nbody_octree* t, hipStream_t st) {
   constexpr uint32_t NCH = 1u << D;
   const ot_tree<T, D> tree{static_cast<ot_group<T, D>*>(t->groups), static_cast<ot_node<T>*>(t->rootrec)};
   const uint32_t max_chunks = (t->max_cells + kMpChunk - 1) / kMpChunk;
-  if ((t->build == 0 || t->build == 3) && max_chunks > kMpMaxBlocks) {  // beyond 4.2 * 10^6 bodies: one launch per level over all ranks
+  if (ot_one_pass(t) && max_chunks > kMpMaxBlocks) {  // beyond 4.2 * 10^6 bodies: one launch per level over all ranks
     for (int l = kMaxLevels<D> - 1; l >= 0; --l) {
       hipLaunchKernelGGL((ot_multipole_ranks_level_kernel<T, D>), dim3((t->max_cells + kOB - 1) / kOB), dim3(kOB), 0, st, l, tree,
                          t->cells, t->lvl_count, t->capacity, t->max_cells);
@@ -2900,13 +3035,13 @@ static int ot_tree_run(nbody_octree* t, hipStream_t st) {
   // one block for the whole tree where that is one chunk's work: a single chunk of kMpChunk ranks, or — in float — of 1024 (more cells
   // than that, rare: chunk after chunk, then the crown).  Double trees of two or three chunks take the two launches below: their
   // chunks side by side on two CUs + the crown are 22 us, one after the other in one block 30 (n = 1000)
-  if ((t->build == 0 || t->build == 3) && (max_chunks == 1 || (sizeof(T) == 4 && max_chunks <= kSmallChunks))) {
+  if (ot_one_pass(t) && (max_chunks == 1 || (sizeof(T) == 4 && max_chunks <= kSmallChunks))) {
     hipLaunchKernelGGL((ot_multipole_small_kernel<T, D>), dim3(1), dim3((kSmallMpThreads<T, D>)), 0, st, tree, t->cells, t->lvl_count, t->later,
                        t->later_mask, t->capacity, t->max_cells, max_chunks);
     NB_HIP(hipGetLastError());
     return NBODY_OK;
   }
-  if (t->build == 0 || t->build == 3) {  // rank chunks, then the cells that span chunk boundaries: in one block, or in two rounds
+  if (ot_one_pass(t)) {  // rank chunks, then the cells that span chunk boundaries: in one block, or in two rounds
     hipLaunchKernelGGL((ot_multipole_chunks_kernel<T, D>), dim3(max_chunks), dim3(kMpChunk), 0, st, tree, t->cells, t->lvl_count,
                        t->later, t->later_mask, t->capacity, t->max_cells);
     NB_HIP(hipGetLastError());
@@ -2964,66 +3099,51 @@ static int ot_walk_list(nbody_octree* t, const nbody_state* s, hipStream_t st, c
   return NBODY_OK;
 }
 
-// the softened walk's refusal after nbody_octree_set_walk(t, 2) (also the block steps', which take that walk: octree_block.inc)
-static int ot_soft_walk_form(const nbody_octree* t) {
+// The refusal of a walk that exists in the compiler-scheduled form only ("softened": also the block steps', which take that walk —
+// octree_block.inc; "quadrupole"; "potential") after nbody_octree_set_walk(t, 2).
+static int ot_form1_only(const nbody_octree* t, const char* walk) {
   if (t->walk == 2) {
-    set_error("octree walk: the softened walk exists in the compiler-scheduled form only (walk form 1 or 0 = auto), not as the ISA "
-              "visit round set by nbody_octree_set_walk(t, 2)");
+    set_error("octree walk: the %s walk exists in the compiler-scheduled form only (walk form 1 or 0 = auto), not as the ISA "
+              "visit round set by nbody_octree_set_walk(t, 2)", walk);
     return NBODY_ERR_ARG;
   }
   return NBODY_OK;
 }
 
-// soft: the softened walk (e2 > 0), which exists in the compiler-scheduled form only
+// One launch for every walk kernel: `plain` and `counting` are its two COUNT instantiations (the tree's counters choose), out / scale
+// are a / c or phi / scale, `extra` is what the kernel takes behind the common arguments (e2, quad or nothing).  One block per wave
+// of 2^(6 - D) bodies; a well-formed tree is left after < capacity rounds.
+template <typename T, int D, typename... Extra>
+using ot_walk_kernel = void (*)(const ot_node<T>*, const ot_group<T, D>*, const uint32_t*, uint32_t, const T*, T*, T, uint32_t, T, uint32_t,
+                                const T*, uint32_t*, uint32_t*, Extra...);
+template <typename T, int D, typename... Extra>
+static int ot_walk_launch(const nbody_octree* t, ot_walk_kernel<T, D, Extra...> plain, ot_walk_kernel<T, D, Extra...> counting,
+                          const uint32_t* list, uint32_t nlist, const T* x, T* out, T scale, uint32_t first, double theta,
+                          hipStream_t st, Extra... extra) {
+  const uint32_t per_wave = 64u >> D;
+  hipLaunchKernelGGL(t->counters_on ? counting : plain, dim3((nlist + per_wave - 1) / per_wave), dim3(64), 0, st,
+                     static_cast<const ot_node<T>*>(t->rootrec), static_cast<const ot_group<T, D>*>(t->groups), list, nlist, x, out,
+                     scale, first, static_cast<T>(theta), t->step_budget ? t->step_budget : t->capacity,
+                     static_cast<const T*>(t->root), ot_flags(t), t->counters, extra...);
+  NB_HIP(hipGetLastError());
+  return NBODY_OK;
+}
+
+// kind: kOtSoft (e2 > 0) and kOtQuad exist in the compiler-scheduled form only
 template <typename T, int D>
-static int ot_force_run(nbody_octree* t, const nbody_state* s, double theta, hipStream_t st, bool soft = false, T e2 = T(0),
-                        bool quadrupole = false) {
-  if (quadrupole && t->walk == 2) {
-    set_error("octree walk: the quadrupole walk exists in the compiler-scheduled form only (walk form 1 or 0 = auto), not as the "
-              "ISA visit round set by nbody_octree_set_walk(t, 2)");
-    return NBODY_ERR_ARG;
-  }
-  if (soft)
-    if (int r = ot_soft_walk_form(t)) return r;
+static int ot_force_run(nbody_octree* t, const nbody_state* s, double theta, hipStream_t st, ot_kind kind = kOtMono, T e2 = T(0)) {
+  if (kind != kOtMono)
+    if (int r = ot_form1_only(t, kind == kOtSoft ? "softened" : "quadrupole")) return r;
   if (s->count == 0) return NBODY_OK;
   const uint32_t* list = nullptr;
   if (int r = ot_walk_list(t, s, st, &list)) return r;
-  const uint32_t per_wave = 64u >> D;
-  const uint32_t blocks   = (s->count + per_wave - 1) / per_wave;
-  const uint32_t budget   = t->step_budget ? t->step_budget : t->capacity;  // a well-formed tree is left after < capacity rounds
-  auto* rootrec           = static_cast<const ot_node<T>*>(t->rootrec);
-#define NB_OT_LAUNCH(CNT)                                                                                                    \
-  hipLaunchKernelGGL((ot_force_kernel<T, D, CNT>), dim3(blocks), dim3(64), 0, st, rootrec,                                   \
-                     static_cast<const ot_group<T, D>*>(t->groups), list, s->count,                                          \
-                     static_cast<const T*>(s->x), static_cast<T*>(s->a), static_cast<T>(s->c), s->first,                     \
-                     static_cast<T>(theta), budget, static_cast<const T*>(t->root),                                        \
-                     t->lvl_count + ((D == 3 ? kMaxLevels<3> : kMaxLevels<2>) + 2), t->counters)
-  if (soft) {
-#define NB_OT_SOFT(CNT)                                                                                                      \
-  hipLaunchKernelGGL((ot_force_softened_kernel<T, D, CNT>), dim3(blocks), dim3(64), 0, st, rootrec,                          \
-                     static_cast<const ot_group<T, D>*>(t->groups), list, s->count,                                          \
-                     static_cast<const T*>(s->x), static_cast<T*>(s->a), static_cast<T>(s->c), s->first,                     \
-                     static_cast<T>(theta), budget, static_cast<const T*>(t->root),                                        \
-                     t->lvl_count + ((D == 3 ? kMaxLevels<3> : kMaxLevels<2>) + 2), t->counters, e2)
-    if (t->counters_on) NB_OT_SOFT(true);
-    else NB_OT_SOFT(false);
-#undef NB_OT_SOFT
-    NB_HIP(hipGetLastError());
-    return NBODY_OK;
-  }
-  if (quadrupole) {
-#define NB_OT_QUAD(CNT)                                                                                                      \
-  hipLaunchKernelGGL((ot_force_quadrupole_kernel<T, D, CNT>), dim3(blocks), dim3(64), 0, st, rootrec,                        \
-                     static_cast<const ot_group<T, D>*>(t->groups), list, s->count,                                          \
-                     static_cast<const T*>(s->x), static_cast<T*>(s->a), static_cast<T>(s->c), s->first,                     \
-                     static_cast<T>(theta), budget, static_cast<const T*>(t->root),                                        \
-                     t->lvl_count + ((D == 3 ? kMaxLevels<3> : kMaxLevels<2>) + 2), t->counters, static_cast<const T*>(t->quad))
-    if (t->counters_on) NB_OT_QUAD(true);
-    else NB_OT_QUAD(false);
-#undef NB_OT_QUAD
-    NB_HIP(hipGetLastError());
-    return NBODY_OK;
-  }
+  auto launch = [&](auto plain, auto counting, auto... extra) {
+    return ot_walk_launch<T, D>(t, plain, counting, list, s->count, static_cast<const T*>(s->x), static_cast<T*>(s->a),
+                                static_cast<T>(s->c), s->first, theta, st, extra...);
+  };
+  if (kind == kOtSoft) return launch(ot_force_softened_kernel<T, D, false>, ot_force_softened_kernel<T, D, true>, e2);
+  if (kind == kOtQuad)
+    return launch(ot_force_quadrupole_kernel<T, D, false>, ot_force_quadrupole_kernel<T, D, true>, static_cast<const T*>(t->quad));
   // the visit round written as ISA (ot_force_isa_kernel, ot_force_isa_f32_kernel; 2D and 3D), while 24-bit group numbers times the group
   // size stay inside 32-bit offsets; nbody_octree_set_walk(t, 1) keeps the compiler-scheduled kernel (tests compare the two bitwise)
   bool isa = false;
@@ -3037,61 +3157,29 @@ static int ot_force_run(nbody_octree* t, const nbody_state* s, double theta, hip
     return NBODY_ERR_ARG;
   }
   if (isa) {
-#define NB_OT_ISA(KERN, CNT)                                                                                                  \
-  hipLaunchKernelGGL((KERN<D, CNT>), dim3(blocks), dim3(64), 0, st, rootrec, static_cast<const ot_group<T, D>*>(t->groups), list, \
-                     s->count, static_cast<const T*>(s->x), static_cast<T*>(s->a), static_cast<T>(s->c), s->first,            \
-                     static_cast<T>(theta), budget, static_cast<const T*>(t->root),                                           \
-                     t->lvl_count + ((D == 3 ? kMaxLevels<3> : kMaxLevels<2>) + 2), t->counters)
-    if constexpr (sizeof(T) == 8) {
-      if (t->counters_on) NB_OT_ISA(ot_force_isa_kernel, true);
-      else NB_OT_ISA(ot_force_isa_kernel, false);
-    } else {
-      if (t->counters_on) NB_OT_ISA(ot_force_isa_f32_kernel, true);
-      else NB_OT_ISA(ot_force_isa_f32_kernel, false);
-    }
-#undef NB_OT_ISA
-  } else if (t->counters_on) NB_OT_LAUNCH(true);
-  else NB_OT_LAUNCH(false);
-#undef NB_OT_LAUNCH
-  NB_HIP(hipGetLastError());
-  return NBODY_OK;
+    if constexpr (sizeof(T) == 8) return launch(ot_force_isa_kernel<D, false>, ot_force_isa_kernel<D, true>);
+    else return launch(ot_force_isa_f32_kernel<D, false>, ot_force_isa_f32_kernel<D, true>);
+  }
+  return launch(ot_force_kernel<T, D, false>, ot_force_kernel<T, D, true>);
 }
 
-// The potential walks: kind 0 monopole, 1 softened (e2), 2 quadrupole (after nbody_octree_compute_quadrupoles); phi[k] = scale * S of
-// body first + k.  Compiler-scheduled form only; shard windows through the force walk's owned list.
-enum { kOtPotMono = 0, kOtPotSoft = 1, kOtPotQuad = 2 };
+// The potential walks, kOtQuad after nbody_octree_compute_quadrupoles; phi[k] = scale * S of body first + k.  Compiler-scheduled form
+// only; shard windows through the force walk's owned list.
 template <typename T, int D>
-static int ot_potential_run(nbody_octree* t, const nbody_state* s, double theta, hipStream_t st, int kind, T e2, T* phi, T scale) {
-  if (t->walk == 2) {
-    set_error("octree walk: the potential walk exists in the compiler-scheduled form only (walk form 1 or 0 = auto), not as the ISA "
-              "visit round set by nbody_octree_set_walk(t, 2)");
-    return NBODY_ERR_ARG;
-  }
+static int ot_potential_run(nbody_octree* t, const nbody_state* s, double theta, hipStream_t st, ot_kind kind, T e2, T* phi, T scale) {
+  if (int r = ot_form1_only(t, "potential")) return r;
   if (s->count == 0) return NBODY_OK;
   const uint32_t* list = nullptr;
   if (int r = ot_walk_list(t, s, st, &list)) return r;
-  const uint32_t per_wave = 64u >> D;
-  const uint32_t blocks   = (s->count + per_wave - 1) / per_wave;
-  const uint32_t budget   = t->step_budget ? t->step_budget : t->capacity;
-  auto* rootrec           = static_cast<const ot_node<T>*>(t->rootrec);
-  uint32_t* flags         = t->lvl_count + ((D == 3 ? kMaxLevels<3> : kMaxLevels<2>) + 2);
-#define NB_OT_POT(KERN, CNT, ...)                                                                                              \
-  hipLaunchKernelGGL((KERN<T, D, CNT>), dim3(blocks), dim3(64), 0, st, rootrec, static_cast<const ot_group<T, D>*>(t->groups), list, \
-                     s->count, static_cast<const T*>(s->x), phi, scale, s->first, static_cast<T>(theta), budget,               \
-                     static_cast<const T*>(t->root), flags, t->counters __VA_OPT__(, ) __VA_ARGS__)
-  if (kind == kOtPotSoft) {
-    if (t->counters_on) NB_OT_POT(ot_potential_softened_kernel, true, e2);
-    else NB_OT_POT(ot_potential_softened_kernel, false, e2);
-  } else if (kind == kOtPotQuad) {
-    if (t->counters_on) NB_OT_POT(ot_potential_quadrupole_kernel, true, static_cast<const T*>(t->quad));
-    else NB_OT_POT(ot_potential_quadrupole_kernel, false, static_cast<const T*>(t->quad));
-  } else {
-    if (t->counters_on) NB_OT_POT(ot_potential_kernel, true);
-    else NB_OT_POT(ot_potential_kernel, false);
-  }
-#undef NB_OT_POT
-  NB_HIP(hipGetLastError());
-  return NBODY_OK;
+  auto launch = [&](auto plain, auto counting, auto... extra) {
+    return ot_walk_launch<T, D>(t, plain, counting, list, s->count, static_cast<const T*>(s->x), phi, scale, s->first, theta, st,
+                                extra...);
+  };
+  if (kind == kOtSoft) return launch(ot_potential_softened_kernel<T, D, false>, ot_potential_softened_kernel<T, D, true>, e2);
+  if (kind == kOtQuad)
+    return launch(ot_potential_quadrupole_kernel<T, D, false>, ot_potential_quadrupole_kernel<T, D, true>,
+                  static_cast<const T*>(t->quad));
+  return launch(ot_potential_kernel<T, D, false>, ot_potential_kernel<T, D, true>);
 }
 
 // Children before parents: the cells below the key depth (one thread per cell of depth kMaxLevels), then the key levels one launch
@@ -3102,7 +3190,7 @@ static int ot_quad_run(nbody_octree* t, hipStream_t st) {
   constexpr uint32_t NCH = 1u << D;
   const ot_tree<T, D> tree{static_cast<ot_group<T, D>*>(t->groups), static_cast<ot_node<T>*>(t->rootrec)};
   T* quad              = static_cast<T*>(t->quad);
-  const bool one_pass  = t->build == 0 || t->build == 3;
+  const bool one_pass  = ot_one_pass(t);
   NB_HIP(hipMemsetAsync(quad, 0, sizeof(T) * kOtQS<D>, st));
   hipLaunchKernelGGL((ot_quadrupole_deep_kernel<T, D>), dim3(64), dim3(64), 0, st, tree, quad, t->cells,
                      one_pass ? t->tops : static_cast<const ot_cell*>(nullptr), t->lvl_count, t->capacity);
@@ -3359,7 +3447,7 @@ extern "C" int nbody_octree_compute_softened_force(nbody_octree* t, const nbody_
     using T  = typename TG::type;
     T e2;
     (void)check_softening<T>(eps, &e2);
-    return ot_force_run<T, TG::dim>(t, s, theta, as_stream(stream), true, e2);
+    return ot_force_run<T, TG::dim>(t, s, theta, as_stream(stream), kOtSoft, e2);
   });
 }
 
@@ -3387,7 +3475,7 @@ extern "C" int nbody_octree_info(nbody_octree* t, uint32_t* tree_size, void* roo
   NB_HIP(hipMemcpyAsync(rec, t->rootrec, t->tsz * 4, hipMemcpyDeviceToHost, st));
   NB_HIP(hipStreamSynchronize(st));
   const uint32_t flags = lv[maxl + 2];  // set by ANY build since the last call
-  if (flags != 0) NB_HIP(hipMemsetAsync(t->lvl_count + (maxl + 2), 0, sizeof(uint32_t), st));
+  if (flags != 0) NB_HIP(hipMemsetAsync(ot_flags(t), 0, sizeof(uint32_t), st));
   if (flags & kFlagDepth) {
     set_error("octree depth limit: bodies not separated after %d levels (coincident positions, or closer than root_side/2^%d)",
               kOtDeepLevels, kOtDeepLevels);
@@ -3477,7 +3565,7 @@ extern "C" int nbody_octree_compute_quadrupole_force(nbody_octree* t, const nbod
   return dispatch(s->dtype, s->dim, [&](auto tg) {
     using TG = decltype(tg);
     using T  = typename TG::type;
-    return ot_force_run<T, TG::dim>(t, s, theta, as_stream(stream), false, T(0), true);
+    return ot_force_run<T, TG::dim>(t, s, theta, as_stream(stream), kOtQuad);
   });
 }
 
@@ -3514,7 +3602,7 @@ extern "C" int nbody_octree_compute_potential(nbody_octree* t, const nbody_state
   return ot_potential_entry(t, s, phi, stream, "nbody_octree_compute_potential", [&](auto tg, auto* p, auto scale) {
     using TG = decltype(tg);
     using T  = typename TG::type;
-    return ot_potential_run<T, TG::dim>(t, s, theta, as_stream(stream), kOtPotMono, T(0), p, scale);
+    return ot_potential_run<T, TG::dim>(t, s, theta, as_stream(stream), kOtMono, T(0), p, scale);
   });
 }
 
@@ -3531,7 +3619,7 @@ extern "C" int nbody_octree_compute_softened_potential(nbody_octree* t, const nb
     using T  = typename TG::type;
     T e2;
     (void)check_softening<T>(eps, &e2);
-    return ot_potential_run<T, TG::dim>(t, s, theta, as_stream(stream), kOtPotSoft, e2, p, scale);
+    return ot_potential_run<T, TG::dim>(t, s, theta, as_stream(stream), kOtSoft, e2, p, scale);
   });
 }
 
@@ -3540,7 +3628,7 @@ extern "C" int nbody_octree_compute_quadrupole_potential(nbody_octree* t, const 
     using TG = decltype(tg);
     using T  = typename TG::type;
     if (int r = ot_quad_ready(t, "nbody_octree_compute_quadrupole_potential")) return r;
-    return ot_potential_run<T, TG::dim>(t, s, theta, as_stream(stream), kOtPotQuad, T(0), p, scale);
+    return ot_potential_run<T, TG::dim>(t, s, theta, as_stream(stream), kOtQuad, T(0), p, scale);
   });
 }
 
@@ -3577,16 +3665,16 @@ extern "C" int nbody_octree_calc_energies(nbody_octree* t, const nbody_state* s,
     nbody_octree* t;
     const nbody_state* s;
     double theta, eps;
-    int kind;
+    ot_kind kind;
     hipStream_t st;
-  } ctx{t, s, theta, eps, quadrupole ? int(kOtPotQuad) : eps > 0.0 ? int(kOtPotSoft) : int(kOtPotMono), st};
+  } ctx{t, s, theta, eps, quadrupole ? kOtQuad : eps > 0.0 ? kOtSoft : kOtMono, st};
   auto fill = [](void* sums, void* p) -> int {
     const fill_ctx& c = *static_cast<const fill_ctx*>(p);
     return dispatch(c.s->dtype, c.s->dim, [&](auto tg) {
       using TG = decltype(tg);
       using T  = typename TG::type;
       T e2     = T(0);
-      if (c.kind == kOtPotSoft) (void)check_softening<T>(c.eps, &e2);
+      if (c.kind == kOtSoft) (void)check_softening<T>(c.eps, &e2);
       return ot_potential_run<T, TG::dim>(c.t, c.s, c.theta, c.st, c.kind, e2, static_cast<T*>(sums), T(1));
     });
   };

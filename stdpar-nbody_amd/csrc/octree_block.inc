@@ -6,8 +6,8 @@
 //   predict    ALL bodies to tau_next into the handle's xp, h_i = T(tau_next - tau_i) * tick;
 //   build      the tree on xp: bounds, keys + sort + cells, multipoles — the launches of a fixed step, on a view whose x is xp;
 //   walk list  count / scan / compact again, over the key order the build has just produced (sidx = the sorted body indices);
-//   walk       ot_force_softened_kernel as it is, list = the walk list, nlist = n_act, x = xp, a = the handle's a1: it writes the
-//              listed rows only;
+//   walk       ot_force_softened_kernel as it is, through the walks' one launch (ot_walk_launch): list = the walk list, nlist = n_act,
+//              x = xp, a = the handle's a1 — it writes the listed rows only;
 //   kick       one lane per active body: v += h/2 (a + a1), x = xp, a = a1, the new level, tau.
 // The host synchronises after the walk list is queued and sizes the last two launches from (n_act, tau_next).
 
@@ -133,7 +133,7 @@ static int otb_check(nbody_octree_block* h, nbody_octree* t, const nbody_state* 
               is_start ? "starts a run of block steps, which are not recordable" : "is blocking (it reads the size of the active set back)");
     return NBODY_ERR_STATE;
   }
-  if (int r = ot_soft_walk_form(t)) return r;  // after nbody_octree_set_walk(t, 2): the softened walk's refusal
+  if (int r = ot_form1_only(t, "softened")) return r;  // after nbody_octree_set_walk(t, 2): the softened walk's refusal
   if (!is_start) {
     if (!h->on) {
       set_error("%s before nbody_octree_block_start on this handle", who);
@@ -163,7 +163,7 @@ static int otb_start_launch(nbody_octree_block* h, nbody_octree* t, const nbody_
                             hipStream_t st) {
   h->on = h->stepped = false;
   if (int r = otb_build<T, D>(t, s, st)) return r;
-  if (int r = ot_force_run<T, D>(t, s, theta, st, true, bc.e2)) return r;
+  if (int r = ot_force_run<T, D>(t, s, theta, st, kOtSoft, bc.e2)) return r;
   hipLaunchKernelGGL((otb_init_kernel<T, D>), dim3((h->n + kOtbBlock - 1) / kOtbBlock), dim3(kOtbBlock), 0, st,
                      static_cast<const T*>(s->a), h->sched.lev, h->sched.tau, bc.k, bc.dtmax, h->n, int32_t(L));
   NB_HIP(hipGetLastError());
@@ -196,20 +196,10 @@ static int otb_step_launch(nbody_octree_block* h, nbody_octree* t, const nbody_s
     h->on = false;
     return r;
   }
-  {  // the softened walk of ot_force_run, over the walk list, from xp into a1
-    const uint32_t per_wave = 64u >> D;
-    const uint32_t blocks   = (n_act + per_wave - 1) / per_wave;
-    const uint32_t budget   = t->step_budget ? t->step_budget : t->capacity;
-#define NB_OTB_WALK(CNT)                                                                                                               \
-  hipLaunchKernelGGL((ot_force_softened_kernel<T, D, CNT>), dim3(blocks), dim3(64), 0, st, static_cast<const ot_node<T>*>(t->rootrec), \
-                     static_cast<const ot_group<T, D>*>(t->groups), h->wlist, n_act, static_cast<const T*>(xp), a1,                    \
-                     static_cast<T>(s->c), 0u, static_cast<T>(theta), budget, static_cast<const T*>(t->root),                          \
-                     t->lvl_count + ((D == 3 ? kMaxLevels<3> : kMaxLevels<2>) + 2), t->counters, bc.e2)
-    if (t->counters_on) NB_OTB_WALK(true);
-    else NB_OTB_WALK(false);
-#undef NB_OTB_WALK
-    NB_HIP(hipGetLastError());
-  }
+  // the softened walk of ot_force_run, over the walk list, from xp into a1
+  if (int r = ot_walk_launch<T, D>(t, ot_force_softened_kernel<T, D, false>, ot_force_softened_kernel<T, D, true>, h->wlist, n_act,
+                                   static_cast<const T*>(xp), a1, static_cast<T>(s->c), 0u, theta, st, bc.e2))
+    return r;
   hipLaunchKernelGGL((otb_kick_kernel<T, D>), dim3((n_act + kOtbBlock - 1) / kOtbBlock), dim3(kOtbBlock), 0, st, sc.act, sc.sched, xp, a1,
                      static_cast<T*>(s->x), static_cast<T*>(s->v), static_cast<T*>(s->a), sc.lev, sc.tau, bc.k, bc.tick, n_act, n, L);
   NB_HIP(hipGetLastError());
