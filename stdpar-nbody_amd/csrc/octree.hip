@@ -2175,7 +2175,12 @@ struct ot_potential_terms {
 // (tolerance parity), the set of tests, accepted terms and therefore the counters do not, and the result of a body
 // depends on nothing but the tree and that body (so it is independent of the shard window).
 // The walk knows no kind of term: the tests, their order, the pushes, the exits and the counters are the same for every Terms.
-template <typename T, int D, bool COUNT, typename Terms>
+// ISA: the visit rounds are ot_isa_rounds' (the same rounds written as ISA, monopole force only) instead of the loop below; lane
+// setup, the root and the end are the same code.
+template <typename T, int D, bool COUNT>
+struct ot_isa_rounds;
+
+template <typename T, int D, bool COUNT, bool ISA = false, typename Terms>
 __device__ __forceinline__ void ot_walk(Terms terms, const ot_node<T>* __restrict__ rootrec, const ot_group<T, D>* __restrict__ groups,
                                         const uint32_t* __restrict__ list, uint32_t nlist, const T* __restrict__ x, uint32_t first,
                                         T theta, uint32_t capacity, const T* __restrict__ root, uint32_t* __restrict__ flags,
@@ -2183,7 +2188,6 @@ __device__ __forceinline__ void ot_walk(Terms terms, const ot_node<T>* __restric
   constexpr uint32_t NCH   = 1u << D;
   constexpr uint32_t GPW   = 64u / NCH;                         // bodies per wave
   constexpr uint32_t DEPTH = (NCH - 1u) * kMaxLevels<D> + NCH;  // a pop frees one slot, an open adds <= 2^D
-  __shared__ uint32_t stack[GPW][DEPTH];
   const uint32_t g = threadIdx.x / NCH, cc = threadIdx.x % NCH;
   // `list`: the owned bodies in key order (neighbours share most of their walk: cache); XCD-contiguous blocks
   const uint32_t t    = ot_xcd_contiguous_block(blockIdx.x, gridDim.x) * GPW + g;
@@ -2196,7 +2200,7 @@ __device__ __forceinline__ void ot_walk(Terms terms, const ot_node<T>* __restric
   for (int k = 0; k < D; ++k) xi[k] = valid ? x[uint64_t(body) * D + k] : T(0);
   terms.zero();
   uint32_t c_nodes = 0, c_terms = 0;
-  uint32_t cur = 0, sp = 0;
+  uint32_t cur = 0;
   bool more = false;
   if (valid) {  // the root is examined alone (by every lane of the group; lane 0 keeps the result)
     const ot_node<T> nd = *rootrec;
@@ -2220,36 +2224,42 @@ __device__ __forceinline__ void ot_walk(Terms terms, const ot_node<T>* __restric
     more = !take;
     cur  = nd.fc;  // the root's stored fc is already a sibling-group number, like every fl[][0] below
   }
-  uint32_t guard = capacity;  // a well-formed tree is left after < capacity steps; never spin on a damaged one
-  while (more && guard-- != 0u) {  // the lanes of a group leave together
-    const ot_node<T> nd = groups[cur].load(cc);  // this lane's child: two or three 16-/8-byte loads
-    T di[D];
+  if constexpr (ISA) {
+    ot_isa_rounds<T, D, COUNT>::run(terms, groups, xi, th, root_side, cur, more, c_nodes, c_terms, capacity, flags);
+  } else {
+    __shared__ uint32_t stack[GPW][DEPTH];
+    uint32_t sp = 0;
+    uint32_t guard = capacity;  // a well-formed tree is left after < capacity steps; never spin on a damaged one
+    while (more && guard-- != 0u) {  // the lanes of a group leave together
+      const ot_node<T> nd = groups[cur].load(cc);  // this lane's child: two or three 16-/8-byte loads
+      T di[D];
 #pragma unroll
-    for (int k = 0; k < D; ++k) di[k] = nd.p[k] - xi[k];
-    const T d2f     = ot_dist2_fused<T, D>(di);
-    const T y0      = ot_rsq(d2f);
-    const bool leaf = nd.fc >= kOtBody;
-    const bool take = leaf || ot_accept<T, D>(!leaf, ot_ldexp(root_side, -int(nd.lvl)), di, y0, th);
-    if (COUNT) {
-      ++c_nodes;
-      c_terms += take;
+      for (int k = 0; k < D; ++k) di[k] = nd.p[k] - xi[k];
+      const T d2f     = ot_dist2_fused<T, D>(di);
+      const T y0      = ot_rsq(d2f);
+      const bool leaf = nd.fc >= kOtBody;
+      const bool take = leaf || ot_accept<T, D>(!leaf, ot_ldexp(root_side, -int(nd.lvl)), di, y0, th);
+      if (COUNT) {
+        ++c_nodes;
+        c_terms += take;
+      }
+      const uint64_t take_mask = __builtin_amdgcn_ballot_w64(take);
+      if (take_mask != 0ull) terms.node(take, take_mask, di, nd.m, d2f, y0);
+      terms.cell(take && !leaf, di, d2f, y0, 1u + cur * NCH + cc);
+      const uint32_t open_mask = uint32_t((__ballot(!take) >> (g * NCH)) & ((1ull << NCH) - 1ull));
+      if (sp + uint32_t(__builtin_popcount(open_mask)) > DEPTH) {  // only below the key depth can a walk hold this many
+        if (cc == 0) atomicOr(flags, kFlagStack);                  // pending nodes; reported by nbody_octree_info
+        break;
+      }
+      if (!take) stack[g][sp + uint32_t(__builtin_popcount(open_mask >> (cc + 1u)))] = nd.fc;  // reverse child order
+      sp += uint32_t(__builtin_popcount(open_mask));
+      if (sp == 0u) break;
+      __builtin_amdgcn_wave_barrier();  // one lane pushed, all lanes of the group pop: keep the LDS write before the read
+      cur = stack[g][--sp];
+      __builtin_amdgcn_wave_barrier();  // ... and this read before the next round's push into the same slot
     }
-    const uint64_t take_mask = __builtin_amdgcn_ballot_w64(take);
-    if (take_mask != 0ull) terms.node(take, take_mask, di, nd.m, d2f, y0);
-    terms.cell(take && !leaf, di, d2f, y0, 1u + cur * NCH + cc);
-    const uint32_t open_mask = uint32_t((__ballot(!take) >> (g * NCH)) & ((1ull << NCH) - 1ull));
-    if (sp + uint32_t(__builtin_popcount(open_mask)) > DEPTH) {  // only below the key depth can a walk hold this many
-      if (cc == 0) atomicOr(flags, kFlagStack);                  // pending nodes; reported by nbody_octree_info
-      break;
-    }
-    if (!take) stack[g][sp + uint32_t(__builtin_popcount(open_mask >> (cc + 1u)))] = nd.fc;  // reverse child order
-    sp += uint32_t(__builtin_popcount(open_mask));
-    if (sp == 0u) break;
-    __builtin_amdgcn_wave_barrier();  // one lane pushed, all lanes of the group pop: keep the LDS write before the read
-    cur = stack[g][--sp];
-    __builtin_amdgcn_wave_barrier();  // ... and this read before the next round's push into the same slot
+    if (more && guard == 0xffffffffu && cc == 0) atomicOr(flags, kFlagWalk);  // step budget spent: the tree is damaged
   }
-  if (more && guard == 0xffffffffu && cc == 0) atomicOr(flags, kFlagWalk);  // step budget spent: the tree is damaged
   // combine the 2^D partial sums of a body (fixed order)
 #pragma unroll
   for (uint32_t off = NCH / 2; off > 0; off >>= 1) {
@@ -2331,41 +2341,95 @@ __global__ __launch_bounds__(64) void ot_potential_quadrupole_kernel(const ot_no
                        capacity, root, flags, counters);
 }
 
-// the accepted term's weight for d2 >= 2^-46 (ot_accumulate's far form, same operations in the same order); v[60:61] = mass
-#define OT_FAR                                                                                                            \
-  "v_mul_f64 %[y2], %[y], %[y]\n\t"                                                                                       \
-  "v_fma_f64 %[e], -%[r2], %[y2], 1.0\n\t"                                                                                \
-  "v_mul_f64 %[y2], %[y], %[y2]\n\t"                                                                                      \
-  "v_fma_f64 %[p], %[k1875], %[e], %[k15]\n\t"                                                                            \
-  "v_mul_f64 %[g], %[y], %[m3eps]\n\t"                                                                                    \
-  "v_fmac_f64_e32 %[g], %[p], %[e]\n\t"                                                                                   \
-  "v_mul_f64 %[w], v[60:61], %[y2]\n\t"                                                                                   \
-  "v_fmac_f64_e32 %[w], %[w], %[g]\n\t"
-
-// One visit round of ot_force_kernel written out as ISA (double, 3D): see ot_force_isa_kernel.
+// ---- the visit round written as ISA (walk form 2): one skeleton, the arithmetic of each precision as its pieces -------------------
+// OT_ROUND holds everything a round does that is not arithmetic, once: entry and the EXEC save, the record addresses, decided ->
+// take / open, the reverse-order push, the pop, the ONE unsigned compare for "stack empty or full", the step budget, the near
+// detour's EXEC save and restore, the two exits.  A precision supplies LOADS (the record loads), TEST (the distance and the quick
+// test, leaving the lanes it accepts in st and the lanes it opens in so: the skeleton goes to EXACT if a non-leaf lane is in
+// neither), FAR (the accepted term's weight and the compare that finds near lanes), EXACT (the reference's opening test for every
+// lane, into st) and NEAR (the guarded weight);
+// FP is the type suffix of the three accumulates.  Z keeps (3D) or drops (2D) the third coordinate; MASK, SSH: the 2^D child mask
+// and log2 of the stack's entry stride, 4 * GPW; CNT_N, CNT_T: the counters' increments, or nothing.
 #define OT_KEEP(...) __VA_ARGS__
 #define OT_DROP(...) ""
-// record loads of a round: 3D (p0,p1) | (p2,m) | (fc,depth) from a 320-byte group; 2D (p0,p1) | m | (fc,depth) from a 128-byte one
-#define OT_LOADS_F64_D3                                                                                                   \
-  "v_mad_u32_u24 %[oa], %[cur], %[gsz], %[cc16]\n\t"                                                                      \
-  "v_mad_u32_u24 %[of], %[cur], %[gsz], %[cc8]\n\t"                                                                       \
-  "global_load_dwordx4 v[54:57], %[oa], %[groups]\n\t"                                                                    \
-  "global_load_dwordx4 v[58:61], %[oa], %[groups] offset:128\n\t"                                                         \
-  "global_load_dwordx2 v[62:63], %[of], %[groups]\n\t"
-#define OT_LOADS_F64_D2                                                                                                   \
-  "v_mad_u32_u24 %[oa], %[cur], %[gsz], %[cc16]\n\t"                                                                      \
-  "v_mad_u32_u24 %[of], %[cur], %[gsz], %[cc8]\n\t"                                                                       \
-  "global_load_dwordx4 v[54:57], %[oa], %[groups]\n\t"                                                                    \
-  "global_load_dwordx2 v[60:61], %[of], %[groups] offset:-32\n\t"                                                         \
-  "global_load_dwordx2 v[62:63], %[of], %[groups]\n\t"
-#define OT_ISA_TEXT(Z, LOADS, MASK, SSH, CNT_N, CNT_T)                                                                                      \
+#define OT_CN "v_add_u32_e32 %[cn], 1, %[cn]\n\t"
+#define OT_CT "v_add_u32_e32 %[ct], 1, %[ct]\n\t"
+#define OT_ROUND(Z, FP, LOADS, TEST, FAR, EXACT, NEAR, MASK, SSH, CNT_N, CNT_T)                                           \
   "s_mov_b64 %[sv], exec\n\t"                                                                                             \
   "v_cmp_ne_u32_e32 vcc, 0, %[more]\n\t"                                                                                  \
   "s_and_b64 exec, exec, vcc\n\t"                                                                                         \
   "s_cbranch_execz .LOTend%=\n"                                                                                           \
   ".LOTtop%=:\n\t"                                                                                                        \
+  "v_mad_u32_u24 %[oa], %[cur], %[gsz], %[cc16]\n\t"                                                                      \
+  "v_mad_u32_u24 %[of], %[cur], %[gsz], %[cc8]\n\t"                                                                       \
   LOADS                                                                                                                   \
   CNT_N                                                                                                                   \
+  TEST                                                                                                                    \
+  "s_or_b64 %[so], %[so], %[st]\n\t"                                                                                      \
+  "s_andn2_b64 %[so], %[nonleaf], %[so]\n\t"                                                                              \
+  "s_cbranch_scc1 .LOTexact%=\n"                                                                                          \
+  ".LOTdecided%=:\n\t"                                                                                                    \
+  "s_andn2_b64 %[take], exec, %[nonleaf]\n\t"                                                                             \
+  "s_or_b64 %[take], %[take], %[st]\n\t"                                                                                  \
+  "s_mov_b64 %[act], exec\n\t"                                                                                            \
+  "s_andn2_b64 %[open], exec, %[take]\n\t"                                                                                \
+  "s_and_b64 exec, %[take], %[take]\n\t"                                                                                  \
+  "s_cbranch_scc0 .LOTnotake%=\n\t"                                                                                       \
+  FAR                                                                                                                     \
+  CNT_T                                                                                                                   \
+  "s_cmp_lg_u64 %[near], 0\n\t"                                                                                           \
+  "s_cbranch_scc1 .LOTnear%=\n"                                                                                           \
+  ".LOTacc%=:\n\t"                                                                                                        \
+  "v_fmac_" FP "_e32 %[acc0], %[w], %[d0]\n\t"                                                                            \
+  "v_fmac_" FP "_e32 %[acc1], %[w], %[d1]\n\t"                                                                            \
+  Z("v_fmac_" FP "_e32 %[acc2], %[w], %[d2]\n\t")                                                                         \
+  ".LOTnotake%=:\n\t"                                                                                                     \
+  /* the children to open go on the body's stack in reverse child order; the 2^D lanes of a body pop the same entry */    \
+  "s_mov_b64 exec, %[act]\n\t"                                                                                            \
+  "v_lshrrev_b64 v[52:53], %[gshift], %[open]\n\t"                                                                        \
+  "v_and_b32_e32 v52, " MASK ", v52\n\t"                                                                                  \
+  "v_bcnt_u32_b32 %[nsp], v52, %[sp]\n\t"                                                                                 \
+  "s_and_b64 exec, %[open], %[open]\n\t"                                                                                  \
+  "v_lshrrev_b32_e32 v53, %[ccp1], v52\n\t"                                                                               \
+  "v_bcnt_u32_b32 v53, v53, %[sp]\n\t"                                                                                    \
+  "v_lshl_add_u32 v53, v53, " SSH ", %[stk]\n\t"                                                                          \
+  "ds_write_b32 v53, v62\n\t"                                                                                             \
+  "s_mov_b64 exec, %[act]\n\t"                                                                                            \
+  "v_add_u32_e32 %[sp], -1, %[nsp]\n\t"                                                                                   \
+  "v_cmpx_gt_u32_e64 %[act], %[depth], %[sp]\n\t"                                                                         \
+  "s_cbranch_execz .LOTend%=\n\t"                                                                                         \
+  "v_lshl_add_u32 v53, %[sp], " SSH ", %[stk]\n\t"                                                                        \
+  "ds_read_b32 %[cur], v53\n\t"                                                                                           \
+  "s_add_i32 %[guard], %[guard], -1\n\t"                                                                                  \
+  "s_cmp_lg_u32 %[guard], 0\n\t"                                                                                          \
+  "s_waitcnt lgkmcnt(0)\n\t"                                                                                              \
+  "s_cbranch_scc1 .LOTtop%=\n\t"                                                                                          \
+  "s_mov_b32 %[gflag], 1\n\t"                                                                                             \
+  "s_branch .LOTend%=\n"                                                                                                  \
+  ".LOTexact%=:\n\t" /* some non-leaf lane is inside the guard band: the reference's expression, for every lane (ot_accept) */ \
+  EXACT                                                                                                                   \
+  "s_branch .LOTdecided%=\n"                                                                                              \
+  ".LOTnear%=:\n\t" /* an accepted child below the near distance (the body's own leaf, coincident bodies): the guarded form, per lane */ \
+  "s_mov_b64 %[so], exec\n\t"                                                                                             \
+  "s_mov_b64 exec, %[near]\n\t"                                                                                           \
+  NEAR                                                                                                                    \
+  "s_mov_b64 exec, %[so]\n\t"                                                                                             \
+  "s_branch .LOTacc%=\n"                                                                                                  \
+  ".LOTend%=:\n\t"                                                                                                        \
+  "s_mov_b64 exec, %[sv]"
+
+// -- double.  The records of the round live in v[52:63] (their halves are addressed separately, which an asm operand cannot
+// express).  Record loads: 3D (p0,p1) | (p2,m) | (fc,depth) from a 320-byte group; 2D (p0,p1) | m | (fc,depth) from a 128-byte one.
+#define OT_LOADS_F64_D3                                                                                                   \
+  "global_load_dwordx4 v[54:57], %[oa], %[groups]\n\t"                                                                    \
+  "global_load_dwordx4 v[58:61], %[oa], %[groups] offset:128\n\t"                                                         \
+  "global_load_dwordx2 v[62:63], %[of], %[groups]\n\t"
+#define OT_LOADS_F64_D2                                                                                                   \
+  "global_load_dwordx4 v[54:57], %[oa], %[groups]\n\t"                                                                    \
+  "global_load_dwordx2 v[60:61], %[of], %[groups] offset:-32\n\t"                                                         \
+  "global_load_dwordx2 v[62:63], %[of], %[groups]\n\t"
+// d = p - xi, r2 = |d|^2 + tiny, y = rsq(r2), w = side y: st = w < lo (accept), so = w > hi with y < 2^35 (open)
+#define OT_TEST_F64(Z)                                                                                                    \
   "s_waitcnt vmcnt(2)\n\t"                                                                                                \
   "v_add_f64 %[d0], v[54:55], -%[xi0]\n\t"                                                                                \
   "v_add_f64 %[d1], v[56:57], -%[xi1]\n\t"                                                                                \
@@ -2383,50 +2447,20 @@ __global__ __launch_bounds__(64) void ot_potential_quadrupole_kernel(const ot_no
   "v_cmp_lt_f64_e64 %[st], %[w], %[lo]\n\t"                                                                               \
   "v_cmp_gt_f64_e64 %[so], %[w], %[hi]\n\t"                                                                               \
   "v_cmp_lt_f64_e64 %[so2], %[y], %[c35]\n\t"                                                                             \
-  "s_and_b64 %[so], %[so], %[so2]\n\t"                                                                                    \
-  "s_or_b64 %[so], %[so], %[st]\n\t"                                                                                      \
-  "s_andn2_b64 %[so], %[nonleaf], %[so]\n\t"                                                                              \
-  "s_cbranch_scc1 .LOTexact%=\n"                                                                                          \
-  ".LOTdecided%=:\n\t"                                                                                                    \
-  "s_andn2_b64 %[take], exec, %[nonleaf]\n\t"                                                                             \
-  "s_or_b64 %[take], %[take], %[st]\n\t"                                                                                  \
-  "s_mov_b64 %[act], exec\n\t"                                                                                            \
-  "s_andn2_b64 %[open], exec, %[take]\n\t"                                                                                \
-  "s_and_b64 exec, %[take], %[take]\n\t"                                                                                  \
-  "s_cbranch_scc0 .LOTnotake%=\n\t"                                                                                       \
-  OT_FAR                                                                                                                  \
-  "v_cmp_gt_u64_e64 %[near], %[nearhi], %[r2]\n\t"                                                                        \
-  CNT_T                                                                                                                   \
-  "s_cmp_lg_u64 %[near], 0\n\t"                                                                                           \
-  "s_cbranch_scc1 .LOTnear%=\n"                                                                                           \
-  ".LOTacc%=:\n\t"                                                                                                        \
-  "v_fmac_f64_e32 %[acc0], %[w], %[d0]\n\t"                                                                               \
-  "v_fmac_f64_e32 %[acc1], %[w], %[d1]\n\t"                                                                               \
-  Z("v_fmac_f64_e32 %[acc2], %[w], %[d2]\n\t")                                                                            \
-  ".LOTnotake%=:\n\t"                                                                                                     \
-  /* the children to open go on the body's stack in reverse child order; the 2^D lanes of a body pop the same entry */    \
-  "s_mov_b64 exec, %[act]\n\t"                                                                                            \
-  "v_lshrrev_b64 v[52:53], %[gshift], %[open]\n\t"                                                                        \
-  "v_and_b32_e32 v52, " MASK ", v52\n\t"                                                                                    \
-  "v_bcnt_u32_b32 %[nsp], v52, %[sp]\n\t"                                                                                 \
-  "s_and_b64 exec, %[open], %[open]\n\t"                                                                                  \
-  "v_lshrrev_b32_e32 v53, %[ccp1], v52\n\t"                                                                               \
-  "v_bcnt_u32_b32 v53, v53, %[sp]\n\t"                                                                                    \
-  "v_lshl_add_u32 v53, v53, " SSH ", %[stk]\n\t"                                                                            \
-  "ds_write_b32 v53, v62\n\t"                                                                                             \
-  "s_mov_b64 exec, %[act]\n\t"                                                                                            \
-  "v_add_u32_e32 %[sp], -1, %[nsp]\n\t"                                                                                   \
-  "v_cmpx_gt_u32_e64 %[act], %[depth], %[sp]\n\t"                                                                         \
-  "s_cbranch_execz .LOTend%=\n\t"                                                                                         \
-  "v_lshl_add_u32 v53, %[sp], " SSH ", %[stk]\n\t"                                                                            \
-  "ds_read_b32 %[cur], v53\n\t"                                                                                           \
-  "s_add_i32 %[guard], %[guard], -1\n\t"                                                                                  \
-  "s_cmp_lg_u32 %[guard], 0\n\t"                                                                                          \
-  "s_waitcnt lgkmcnt(0)\n\t"                                                                                              \
-  "s_cbranch_scc1 .LOTtop%=\n\t"                                                                                          \
-  "s_mov_b32 %[gflag], 1\n\t"                                                                                             \
-  "s_branch .LOTend%=\n"                                                                                                  \
-  ".LOTexact%=:\n\t" /* some lane is inside the guard band: the reference's expression with IEEE sqrt and divide, for every lane (ot_accept) */\
+  "s_and_b64 %[so], %[so], %[so2]\n\t"
+// the accepted term's weight for d2 >= 2^-46 (ot_accumulate's far form, same operations in the same order); v[60:61] = mass
+#define OT_FAR_F64                                                                                                        \
+  "v_mul_f64 %[y2], %[y], %[y]\n\t"                                                                                       \
+  "v_fma_f64 %[e], -%[r2], %[y2], 1.0\n\t"                                                                                \
+  "v_mul_f64 %[y2], %[y], %[y2]\n\t"                                                                                      \
+  "v_fma_f64 %[p], %[k1875], %[e], %[k15]\n\t"                                                                            \
+  "v_mul_f64 %[g], %[y], %[m3eps]\n\t"                                                                                    \
+  "v_fmac_f64_e32 %[g], %[p], %[e]\n\t"                                                                                   \
+  "v_mul_f64 %[w], v[60:61], %[y2]\n\t"                                                                                   \
+  "v_fmac_f64_e32 %[w], %[w], %[g]\n\t"                                                                                   \
+  "v_cmp_gt_u64_e64 %[near], %[nearhi], %[r2]\n\t"
+// side / (sqrt(d2) + eps) < theta with IEEE sqrt and divide
+#define OT_EXACT_F64(Z)                                                                                                   \
   "v_mul_f64 v[52:53], %[d0], %[d0]\n\t"                                                                                  \
   "v_mul_f64 v[54:55], %[d1], %[d1]\n\t"                                                                                  \
   "v_add_f64 v[52:53], v[52:53], v[54:55]\n\t"                                                                            \
@@ -2434,12 +2468,12 @@ __global__ __launch_bounds__(64) void ot_potential_quadrupole_kernel(const ot_no
     "v_add_f64 v[52:53], v[54:55], v[52:53]\n\t")                                                                         \
   "v_cmp_gt_f64_e32 vcc, %[sqmin], v[52:53]\n\t"                                                                          \
   "s_nop 1\n\t"                                                                                                           \
-  "v_mov_b32_e32 %[oa], 0x100\n\t"                                                                                          \
-  "v_cndmask_b32_e32 %[t], 0, %[oa], vcc\n\t"                                                                           \
+  "v_mov_b32_e32 %[oa], 0x100\n\t"                                                                                        \
+  "v_cndmask_b32_e32 %[t], 0, %[oa], vcc\n\t"                                                                             \
   "v_ldexp_f64 v[52:53], v[52:53], %[t]\n\t"                                                                              \
   "v_rsq_f64_e32 v[54:55], v[52:53]\n\t"                                                                                  \
-  "v_mov_b32_e32 %[oa], 0xffffff80\n\t"                                                                                     \
-  "v_cndmask_b32_e32 %[t], 0, %[oa], vcc\n\t"                                                                           \
+  "v_mov_b32_e32 %[oa], 0xffffff80\n\t"                                                                                   \
+  "v_cndmask_b32_e32 %[t], 0, %[oa], vcc\n\t"                                                                             \
   "v_cmp_class_f64_e64 vcc, v[52:53], %[c260]\n\t"                                                                        \
   "v_mul_f64 v[56:57], v[52:53], v[54:55]\n\t"                                                                            \
   "v_mul_f64 v[54:55], v[54:55], 0.5\n\t"                                                                                 \
@@ -2467,11 +2501,9 @@ __global__ __launch_bounds__(64) void ot_potential_quadrupole_kernel(const ot_no
   "s_nop 1\n\t"                                                                                                           \
   "v_div_fmas_f64 v[54:55], v[54:55], v[56:57], %[w]\n\t"                                                                 \
   "v_div_fixup_f64 v[52:53], v[54:55], v[52:53], %[g]\n\t"                                                                \
-  "v_cmp_gt_f64_e64 %[st], %[theta], v[52:53]\n\t"                                                                        \
-  "s_branch .LOTdecided%=\n"                                                                                              \
-  ".LOTnear%=:\n\t" /* an accepted child closer than 2^-23 (the body's own leaf, coincident bodies): the guarded form, per lane */\
-  "s_mov_b64 %[so], exec\n\t"                                                                                             \
-  "s_mov_b64 exec, %[near]\n\t"                                                                                           \
+  "v_cmp_gt_f64_e64 %[st], %[theta], v[52:53]\n\t"
+// closer than 2^-23: w = m / (sqrt(d2) + eps)^3 (ot_accumulate's guarded form)
+#define OT_NEAR_F64                                                                                                       \
   "v_mul_f64 %[y2], %[r2], %[y]\n\t"                                                                                      \
   "v_fma_f64 %[e], -%[y2], %[y], 1.0\n\t"                                                                                 \
   "v_mul_f64 %[p], %[y2], 0.5\n\t"                                                                                        \
@@ -2483,156 +2515,91 @@ __global__ __launch_bounds__(64) void ot_potential_quadrupole_kernel(const ot_no
   "s_nop 0\n\t"                                                                                                           \
   "v_fma_f64 %[y2], -%[y2], %[e], 1.0\n\t"                                                                                \
   "v_fmac_f64_e32 %[e], %[e], %[y2]\n\t"                                                                                  \
-  "v_mul_f64 %[w], v[60:61], %[e]\n\t"                                                                                    \
-  "s_mov_b64 exec, %[so]\n\t"                                                                                             \
-  "s_branch .LOTacc%=\n"                                                                                                  \
-  ".LOTend%=:\n\t"                                                                                                        \
-  "s_mov_b64 exec, %[sv]"
+  "v_mul_f64 %[w], v[60:61], %[e]\n\t"
+#define OT_ROUND_F64(Z, LOADS, MASK, SSH, CNT_N, CNT_T) \
+  OT_ROUND(Z, "f64", LOADS, OT_TEST_F64(Z), OT_FAR_F64, OT_EXACT_F64(Z), OT_NEAR_F64, MASK, SSH, CNT_N, CNT_T)
 
-// The walk of ot_force_kernel for double precision in 3D with its visit round written as ISA — the same tests, the same
+// The walk of ot_force_kernel for double precision with its visit round written as ISA — the same tests, the same
 // arithmetic in the same order, bitwise the same results, counters and flags.  hipcc's schedule of the C++ round is ~96
 // instructions (50 VALU): predicated weights, mask round trips through v_cndmask/v_cmp, one saveexec/branch pair per `if`.
 // Here a round is ~60 (36 VALU): record addresses are 32-bit offsets from an SGPR base (two v_mad_u32_u24 instead of 64-bit
 // multiply-adds), the conditions live in scalar masks and EXEC (accepted term under EXEC = take, push under EXEC = open), the
 // step budget is one scalar counter for the wave (its lanes make the same rounds), and "stack empty" and "stack full" are ONE
 // unsigned compare on sp - 1 (the stacks are entry-major in LDS, so a round that overflows writes past the END of the block's
-// LDS, where the hardware drops it; the lane then leaves and reports kFlagStack).  The records of the round live in v[52:63] (their halves are addressed
-// separately, which an asm operand cannot express).  Group offsets are 32 bits: the host uses this kernel while the group
-// array is below 4 GiB (N <= 1.3e7).
+// LDS, where the hardware drops it; the lane then leaves and reports kFlagStack).  Group offsets are 32 bits: the host uses this
+// kernel while the group array is below 4 GiB (N <= 1.3e7).
+// run() is called by ot_walk between the root and the end, with the walk's own lane state: the body's sums in terms.acc, xi, the group
+// to examine first in cur, and more = the root was opened.
 template <int D, bool COUNT>
-__global__ __launch_bounds__(64) void ot_force_isa_kernel(const ot_node<double>* __restrict__ rootrec,
-                                                          const ot_group<double, D>* __restrict__ groups,
-                                                          const uint32_t* __restrict__ list, uint32_t nlist,
-                                                          const double* __restrict__ x, double* __restrict__ a, double c,
-                                                          uint32_t first, double theta, uint32_t capacity,
-                                                          const double* __restrict__ root, uint32_t* __restrict__ flags,
-                                                          uint32_t* __restrict__ counters) {
-  using T = double;
-  constexpr uint32_t NCH = 1u << D, GPW = 64u / NCH;
-  constexpr uint32_t DEPTH = (NCH - 1u) * kMaxLevels<D> + NCH;
-  static_assert(sizeof(ot_group<double, 3>) == 320 && sizeof(ot_group<double, 2>) == 128, "the round addresses 320- / 128-byte sibling groups");
-  __shared__ uint32_t stack[DEPTH][GPW];  // entry-major: slot i of body g at (i * GPW + g) * 4
-  const uint32_t g = threadIdx.x / NCH, cc = threadIdx.x % NCH;
-  const uint32_t t    = ot_xcd_contiguous_block(blockIdx.x, gridDim.x) * GPW + g;
-  const bool valid    = t < nlist;
-  const uint32_t body = valid ? list[t] : first;
-  const ot_theta<T> th(theta);
-  const pair_consts<T> pc;
-  const T root_side = root[D];
-  T xi[3] = {T(0), T(0), T(0)}, acc[3] = {T(0), T(0), T(0)};  // (the third pair is an unused operand in 2D)
-#pragma unroll
-  for (int k = 0; k < D; ++k) xi[k] = valid ? x[uint64_t(body) * D + k] : T(0);
-  uint32_t c_nodes = 0, c_terms = 0;
-  uint32_t cur = 0;
-  bool more = false;
-  if (valid) {  // the root is examined alone, exactly as in ot_force_kernel
-    const ot_node<T> nd = *rootrec;
-    T di[D], a0[D];
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-      di[k] = nd.p[k] - xi[k];
-      a0[k] = T(0);
-    }
-    const T d2f     = ot_dist2_fused<T, D>(di);
-    const T y0      = ot_rsq(d2f);
-    const bool leaf = nd.fc >= kOtBody;
-    const bool take = leaf || ot_accept<T, D>(!leaf, root_side, di, y0, th);
-    {
-      const bool on0    = take && cc == 0;
-      const uint64_t m0 = __builtin_amdgcn_ballot_w64(on0);
-      if (m0 != 0ull) ot_accumulate<T, D>(on0, m0, a0, di, nd.m, d2f, y0, pc);
-    }
-#pragma unroll
-    for (int k = 0; k < D; ++k) acc[k] = a0[k];
-    if (COUNT && cc == 0) {
-      c_nodes = 1;
-      c_terms = take;
-    }
-    more = !take;
-    cur  = nd.fc;
-  }
-  // the rounds
-  uint32_t more_v = more ? 1u : 0u, sp = 0, nsp = 0, gflag = 0, guard = capacity;
-  const uint32_t cc16 = cc * 16u, cc8 = (D == 3 ? 256u : 96u) + cc * 8u, gshift = threadIdx.x & (64u - NCH), ccp1 = cc + 1u;
-  const uint32_t stk = uint32_t(reinterpret_cast<uintptr_t>(&stack[0][g]));  // LDS byte address (low word of the flat one)
-  double lo = to_sgpr(th.lo), hi = to_sgpr(th.hi), thx = to_sgpr(th.exact), c35 = 0x1p35, tiny = ot_consts<T>::tiny,
-         eps = ot_consts<T>::eps, m3eps = -(3.0 * ot_consts<T>::eps), sqmin = 0x1p-767, rs = to_sgpr(root_side);
-  uint64_t nearhi = uint64_t(ot_near<T>::bits) << 32;
-  uint32_t gsz = uint32_t(sizeof(ot_group<double, D>)), depth = DEPTH, c260 = 0x260u;
-  asm volatile("" : "+s"(c35), "+s"(tiny), "+s"(eps), "+s"(m3eps), "+s"(sqmin), "+s"(nearhi), "+s"(gsz), "+s"(depth), "+s"(c260));
-  double d0, d1, d2, r2, y, y2, e, p, gq, w;
-  uint32_t oa, of, tt;
-  uint64_t nonleaf, st, so, so2, take, open, act, sv, near;
+struct ot_isa_rounds<double, D, COUNT> {
+  template <typename Terms>
+  static __device__ __forceinline__ void run(Terms& terms, const ot_group<double, D>* __restrict__ groups, const double (&xi)[D],
+                                             const ot_theta<double>& th, double root_side, uint32_t cur, bool more, uint32_t& c_nodes,
+                                             uint32_t& c_terms, uint32_t capacity, uint32_t* __restrict__ flags) {
+    using T = double;
+    constexpr uint32_t NCH = 1u << D, GPW = 64u / NCH;
+    constexpr uint32_t DEPTH = (NCH - 1u) * kMaxLevels<D> + NCH;
+    static_assert(sizeof(ot_group<double, 3>) == 320 && sizeof(ot_group<double, 2>) == 128, "the round addresses 320- / 128-byte sibling groups");
+    __shared__ uint32_t stack[DEPTH][GPW];  // entry-major: slot i of body g at (i * GPW + g) * 4
+    const uint32_t g = threadIdx.x / NCH, cc = threadIdx.x % NCH;
+    T spare = T(0);  // (the third coordinate's pair of operands is unused in 2D)
+    T& acc2 = D == 3 ? terms.acc[D - 1] : spare;
+    const T xi2 = D == 3 ? xi[D - 1] : T(0);
+    uint32_t more_v = more ? 1u : 0u, sp = 0, nsp = 0, gflag = 0, guard = capacity;
+    const uint32_t cc16 = cc * 16u, cc8 = (D == 3 ? 256u : 96u) + cc * 8u, gshift = threadIdx.x & (64u - NCH), ccp1 = cc + 1u;
+    const uint32_t stk = uint32_t(reinterpret_cast<uintptr_t>(&stack[0][g]));  // LDS byte address (low word of the flat one)
+    double lo = to_sgpr(th.lo), hi = to_sgpr(th.hi), thx = to_sgpr(th.exact), c35 = 0x1p35, tiny = ot_consts<T>::tiny,
+           eps = ot_consts<T>::eps, m3eps = -(3.0 * ot_consts<T>::eps), sqmin = 0x1p-767, rs = to_sgpr(root_side);
+    uint64_t nearhi = uint64_t(ot_near<T>::bits) << 32;
+    uint32_t gsz = uint32_t(sizeof(ot_group<double, D>)), depth = DEPTH, c260 = 0x260u;
+    asm volatile("" : "+s"(c35), "+s"(tiny), "+s"(eps), "+s"(m3eps), "+s"(sqmin), "+s"(nearhi), "+s"(gsz), "+s"(depth), "+s"(c260));
+    double d0, d1, d2, r2, y, y2, e, p, gq, w;
+    uint32_t oa, of, tt;
+    uint64_t nonleaf, st, so, so2, take, open, act, sv, near;
 #define OT_OPERANDS                                                                                                        \
-  : [acc0] "+v"(acc[0]), [acc1] "+v"(acc[1]), [acc2] "+v"(acc[2]), [cur] "+v"(cur), [sp] "+v"(sp), [nsp] "+v"(nsp),          \
+  : [acc0] "+v"(terms.acc[0]), [acc1] "+v"(terms.acc[1]), [acc2] "+v"(acc2), [cur] "+v"(cur), [sp] "+v"(sp), [nsp] "+v"(nsp), \
     OT_CNT_OPERANDS [guard] "+s"(guard), [gflag] "+s"(gflag), [d0] "=&v"(d0), [d1] "=&v"(d1),       \
     [d2] "=&v"(d2), [r2] "=&v"(r2), [y] "=&v"(y), [y2] "=&v"(y2), [e] "=&v"(e), [p] "=&v"(p), [g] "=&v"(gq), [w] "=&v"(w),  \
     [oa] "=&v"(oa), [of] "=&v"(of), [t] "=&v"(tt), [nonleaf] "=&s"(nonleaf), [st] "=&s"(st), [so] "=&s"(so),               \
     [so2] "=&s"(so2), [take] "=&s"(take), [open] "=&s"(open), [act] "=&s"(act), [sv] "=&s"(sv), [near] "=&s"(near)          \
-  : [more] "v"(more_v), [groups] "s"(groups), [xi0] "v"(xi[0]), [xi1] "v"(xi[1]), [xi2] "v"(xi[2]), [cc16] "v"(cc16),     \
-    [cc8] "v"(cc8), [gshift] "v"(gshift), [ccp1] "v"(ccp1), [stk] "v"(stk), [k15] "v"(pc.k15), [k1875] "s"(pc.k1875),       \
+  : [more] "v"(more_v), [groups] "s"(groups), [xi0] "v"(xi[0]), [xi1] "v"(xi[1]), [xi2] "v"(xi2), [cc16] "v"(cc16), \
+    [cc8] "v"(cc8), [gshift] "v"(gshift), [ccp1] "v"(ccp1), [stk] "v"(stk), [k15] "v"(terms.pc.k15),                      \
+    [k1875] "s"(terms.pc.k1875),                                                                                          \
     [lo] "s"(lo), [hi] "s"(hi), [theta] "s"(thx), [c35] "s"(c35), [tiny] "s"(tiny), [eps] "s"(eps), [m3eps] "s"(m3eps),    \
-    [sqmin] "s"(sqmin), [nearhi] "s"(nearhi), [rootside] "s"(rs), [gsz] "s"(gsz), [depth] "s"(depth), [c260] "s"(c260)                                                                                     \
+    [sqmin] "s"(sqmin), [nearhi] "s"(nearhi), [rootside] "s"(rs), [gsz] "s"(gsz), [depth] "s"(depth), [c260] "s"(c260)     \
   : "vcc", "scc", "memory", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63"
 #define OT_CNT_OPERANDS [cn] "+v"(c_nodes), [ct] "+v"(c_terms),
-#define OT_CN "v_add_u32_e32 %[cn], 1, %[cn]\n\t"
-#define OT_CT "v_add_u32_e32 %[ct], 1, %[ct]\n\t"
-  if constexpr (COUNT && D == 3) asm volatile(OT_ISA_TEXT(OT_KEEP, OT_LOADS_F64_D3, "0xff", "5", OT_CN, OT_CT) OT_OPERANDS);
-  if constexpr (COUNT && D == 2) asm volatile(OT_ISA_TEXT(OT_DROP, OT_LOADS_F64_D2, "0xf", "6", OT_CN, OT_CT) OT_OPERANDS);
+    if constexpr (COUNT && D == 3) asm volatile(OT_ROUND_F64(OT_KEEP, OT_LOADS_F64_D3, "0xff", "5", OT_CN, OT_CT) OT_OPERANDS);
+    if constexpr (COUNT && D == 2) asm volatile(OT_ROUND_F64(OT_DROP, OT_LOADS_F64_D2, "0xf", "6", OT_CN, OT_CT) OT_OPERANDS);
 #undef OT_CNT_OPERANDS
 #define OT_CNT_OPERANDS
-  if constexpr (!COUNT && D == 3) asm volatile(OT_ISA_TEXT(OT_KEEP, OT_LOADS_F64_D3, "0xff", "5", "", "") OT_OPERANDS);
-  if constexpr (!COUNT && D == 2) asm volatile(OT_ISA_TEXT(OT_DROP, OT_LOADS_F64_D2, "0xf", "6", "", "") OT_OPERANDS);
+    if constexpr (!COUNT && D == 3) asm volatile(OT_ROUND_F64(OT_KEEP, OT_LOADS_F64_D3, "0xff", "5", "", "") OT_OPERANDS);
+    if constexpr (!COUNT && D == 2) asm volatile(OT_ROUND_F64(OT_DROP, OT_LOADS_F64_D2, "0xf", "6", "", "") OT_OPERANDS);
 #undef OT_CNT_OPERANDS
 #undef OT_OPERANDS
-  if (more && nsp > DEPTH && cc == 0) atomicOr(flags, kFlagStack);  // a stack ran full: reported by nbody_octree_info
-  if (gflag != 0u && threadIdx.x == 0) atomicOr(flags, kFlagWalk);             // step budget spent: the tree is damaged
-  // combine the 2^D partial sums of a body (fixed order)
-#pragma unroll
-  for (uint32_t off = NCH / 2; off > 0; off >>= 1) {
-#pragma unroll
-    for (int k = 0; k < D; ++k) acc[k] += __shfl_xor(acc[k], int(off), 64);
-    if (COUNT) {
-      c_nodes += __shfl_xor(c_nodes, int(off), 64);
-      c_terms += __shfl_xor(c_terms, int(off), 64);
-    }
+    if (more && nsp > DEPTH && cc == 0) atomicOr(flags, kFlagStack);  // a stack ran full: reported by nbody_octree_info
+    if (gflag != 0u && threadIdx.x == 0) atomicOr(flags, kFlagWalk);  // step budget spent: the tree is damaged
   }
-  if (valid && cc == 0) {
-#pragma unroll
-    for (int k = 0; k < D; ++k) a[uint64_t(body - first) * D + k] = c * acc[k];
-    if (COUNT) {
-      counters[uint64_t(body) * 2 + 0] = c_nodes;
-      counters[uint64_t(body) * 2 + 1] = c_terms;
-    }
-  }
-}
+};
+#undef OT_ROUND_F64
+#undef OT_NEAR_F64
+#undef OT_EXACT_F64
+#undef OT_FAR_F64
+#undef OT_TEST_F64
+#undef OT_LOADS_F64_D2
+#undef OT_LOADS_F64_D3
 
-
-// ---- the same visit round for single precision in 3D (the reference's DEFAULT run: float, octree) ------------------------------
-// 192-byte sibling groups: (p0, p1, p2, m) x 8 | (fc, depth) x 8 — two loads per round.  Same tests, same arithmetic in the same
-// order as ot_force_kernel<float, 3>: the quick test q = side * rsq(d2), ql = q - q (eps y) against theta (1 -+ 2^-16); if a
+// -- single (the reference's DEFAULT run: float, octree).  192-byte sibling groups in 3D, 128-byte ones in 2D:
+// (p0, p1, p2, m) x 2^D | (fc, depth) x 2^D — two loads per round.  Same tests, same arithmetic in the same order as
+// ot_force_kernel<float, D>: the quick test q = side * rsq(d2), ql = q - q (eps y) against theta (1 -+ 2^-16); if a
 // non-leaf lane is inside the band the wave evaluates the reference's side / (sqrt(d2) + eps) < theta with the correctly rounded
 // f32 square root and quotient (v_sqrt_f32 / v_rcp_f32 seeds + the fix-up sequences hipcc emits for them, instruction for
 // instruction); the accepted term m y^3 (1 - 3 eps y), the guarded form below d2 = 2^-18 per lane.  The record lives in v[54:57]
 // and v[62:63], temporaries in v52, v53, v58-v61.
-#define OT_FAR_F32                                                                                                        \
-  "v_mul_f32_e32 %[t], %[y], %[y]\n\t"                                                                                    \
-  "v_mul_f32_e32 %[t], %[y], %[t]\n\t"                                                                                    \
-  "v_mul_f32_e32 %[w], v57, %[t]\n\t"                                                                                     \
-  "v_mul_f32_e32 %[t], %[m3eps], %[y]\n\t"                                                                                \
-  "v_fmac_f32_e32 %[w], %[w], %[t]\n\t"
-
-#define OT_ISA_TEXT_F32(Z, MASK, SSH, CNT_N, CNT_T)                                                                                  \
-  "s_mov_b64 %[sv], exec\n\t"                                                                                             \
-  "v_cmp_ne_u32_e32 vcc, 0, %[more]\n\t"                                                                                  \
-  "s_and_b64 exec, exec, vcc\n\t"                                                                                         \
-  "s_cbranch_execz .LOFend%=\n"                                                                                           \
-  ".LOFtop%=:\n\t"                                                                                                        \
-  "v_mad_u32_u24 %[oa], %[cur], %[gsz], %[cc16]\n\t"                                                                      \
-  "v_mad_u32_u24 %[of], %[cur], %[gsz], %[cc8]\n\t"                                                                       \
+#define OT_LOADS_F32                                                                                                      \
   "global_load_dwordx4 v[54:57], %[oa], %[groups]\n\t"                                                                    \
-  "global_load_dwordx2 v[62:63], %[of], %[groups]\n\t"                                                                    \
-  CNT_N                                                                                                                   \
+  "global_load_dwordx2 v[62:63], %[of], %[groups]\n\t"
+#define OT_TEST_F32(Z)                                                                                                    \
   "s_waitcnt vmcnt(1)\n\t"                                                                                                \
   "v_sub_f32_e32 %[d0], v54, %[xi0]\n\t"                                                                                  \
   "v_sub_f32_e32 %[d1], v55, %[xi1]\n\t"                                                                                  \
@@ -2649,49 +2616,15 @@ __global__ __launch_bounds__(64) void ot_force_isa_kernel(const ot_node<double>*
   "v_mul_f32_e32 %[t], %[meps], %[y]\n\t"                                                                                 \
   "v_cmp_lt_f32_e64 %[st], %[w], %[lo]\n\t"                                                                               \
   "v_fmac_f32_e32 %[w], %[w], %[t]\n\t"                                                                                   \
-  "v_cmp_gt_f32_e64 %[so], %[w], %[hi]\n\t"                                                                               \
-  "s_or_b64 %[so], %[so], %[st]\n\t"                                                                                      \
-  "s_andn2_b64 %[so], %[nonleaf], %[so]\n\t"                                                                              \
-  "s_cbranch_scc1 .LOFexact%=\n"                                                                                          \
-  ".LOFdecided%=:\n\t"                                                                                                    \
-  "s_andn2_b64 %[take], exec, %[nonleaf]\n\t"                                                                             \
-  "s_or_b64 %[take], %[take], %[st]\n\t"                                                                                  \
-  "s_mov_b64 %[act], exec\n\t"                                                                                            \
-  "s_andn2_b64 %[open], exec, %[take]\n\t"                                                                                \
-  "s_and_b64 exec, %[take], %[take]\n\t"                                                                                  \
-  "s_cbranch_scc0 .LOFnotake%=\n\t"                                                                                       \
-  OT_FAR_F32                                                                                                              \
-  "v_cmp_gt_u32_e64 %[near], %[nearbits], %[r2]\n\t"                                                                      \
-  CNT_T                                                                                                                   \
-  "s_cmp_lg_u64 %[near], 0\n\t"                                                                                           \
-  "s_cbranch_scc1 .LOFnear%=\n"                                                                                           \
-  ".LOFacc%=:\n\t"                                                                                                        \
-  "v_fmac_f32_e32 %[acc0], %[w], %[d0]\n\t"                                                                               \
-  "v_fmac_f32_e32 %[acc1], %[w], %[d1]\n\t"                                                                               \
-  Z("v_fmac_f32_e32 %[acc2], %[w], %[d2]\n\t")                                                                            \
-  ".LOFnotake%=:\n\t"                                                                                                     \
-  "s_mov_b64 exec, %[act]\n\t"                                                                                            \
-  "v_lshrrev_b64 v[52:53], %[gshift], %[open]\n\t"                                                                        \
-  "v_and_b32_e32 v52, " MASK ", v52\n\t"                                                                                    \
-  "v_bcnt_u32_b32 %[nsp], v52, %[sp]\n\t"                                                                                 \
-  "s_and_b64 exec, %[open], %[open]\n\t"                                                                                  \
-  "v_lshrrev_b32_e32 v53, %[ccp1], v52\n\t"                                                                               \
-  "v_bcnt_u32_b32 v53, v53, %[sp]\n\t"                                                                                    \
-  "v_lshl_add_u32 v53, v53, " SSH ", %[stk]\n\t"                                                                            \
-  "ds_write_b32 v53, v62\n\t"                                                                                             \
-  "s_mov_b64 exec, %[act]\n\t"                                                                                            \
-  "v_add_u32_e32 %[sp], -1, %[nsp]\n\t"                                                                                   \
-  "v_cmpx_gt_u32_e64 %[act], %[depth], %[sp]\n\t"                                                                         \
-  "s_cbranch_execz .LOFend%=\n\t"                                                                                         \
-  "v_lshl_add_u32 v53, %[sp], " SSH ", %[stk]\n\t"                                                                            \
-  "ds_read_b32 %[cur], v53\n\t"                                                                                           \
-  "s_add_i32 %[guard], %[guard], -1\n\t"                                                                                  \
-  "s_cmp_lg_u32 %[guard], 0\n\t"                                                                                          \
-  "s_waitcnt lgkmcnt(0)\n\t"                                                                                              \
-  "s_cbranch_scc1 .LOFtop%=\n\t"                                                                                          \
-  "s_mov_b32 %[gflag], 1\n\t"                                                                                             \
-  "s_branch .LOFend%=\n"                                                                                                  \
-  ".LOFexact%=:\n\t" /* the reference's expression with correctly rounded sqrt and quotient, for every lane (ot_accept) */  \
+  "v_cmp_gt_f32_e64 %[so], %[w], %[hi]\n\t"
+#define OT_FAR_F32                                                                                                        \
+  "v_mul_f32_e32 %[t], %[y], %[y]\n\t"                                                                                    \
+  "v_mul_f32_e32 %[t], %[y], %[t]\n\t"                                                                                    \
+  "v_mul_f32_e32 %[w], v57, %[t]\n\t"                                                                                     \
+  "v_mul_f32_e32 %[t], %[m3eps], %[y]\n\t"                                                                                \
+  "v_fmac_f32_e32 %[w], %[w], %[t]\n\t"                                                                                   \
+  "v_cmp_gt_u32_e64 %[near], %[nearbits], %[r2]\n\t"
+#define OT_EXACT_F32(Z)                                                                                                   \
   "v_mul_f32_e32 v52, %[d0], %[d0]\n\t"                                                                                   \
   "v_mul_f32_e32 v53, %[d1], %[d1]\n\t"                                                                                   \
   "v_add_f32_e32 v52, v52, v53\n\t"                                                                                       \
@@ -2733,11 +2666,9 @@ __global__ __launch_bounds__(64) void ot_force_isa_kernel(const ot_node<double>*
   "s_nop 0\n\t"                                                                                                           \
   "v_div_fmas_f32 v53, v53, v58, v60\n\t"                                                                                 \
   "v_div_fixup_f32 v52, v53, v52, %[g]\n\t"                                                                               \
-  "v_cmp_gt_f32_e64 %[st], %[theta], v52\n\t"                                                                             \
-  "s_branch .LOFdecided%=\n"                                                                                              \
-  ".LOFnear%=:\n\t" /* an accepted child closer than 2^-9 (the body's own leaf, coincident bodies): the guarded form, per lane */\
-  "s_mov_b64 %[so], exec\n\t"                                                                                             \
-  "s_mov_b64 exec, %[near]\n\t"                                                                                           \
+  "v_cmp_gt_f32_e64 %[st], %[theta], v52\n\t"
+// closer than 2^-9
+#define OT_NEAR_F32                                                                                                       \
   "v_mul_f32_e32 %[t], %[r2], %[y]\n\t"                                                                                   \
   "v_fma_f32 v52, -%[t], %[y], 1.0\n\t"                                                                                   \
   "v_mul_f32_e32 v53, 0.5, %[t]\n\t"                                                                                      \
@@ -2749,12 +2680,83 @@ __global__ __launch_bounds__(64) void ot_force_isa_kernel(const ot_node<double>*
   "s_nop 0\n\t"                                                                                                           \
   "v_fma_f32 %[t], -%[t], v52, 1.0\n\t"                                                                                   \
   "v_fmac_f32_e32 v52, v52, %[t]\n\t"                                                                                     \
-  "v_mul_f32_e32 %[w], v57, v52\n\t"                                                                                      \
-  "s_mov_b64 exec, %[so]\n\t"                                                                                             \
-  "s_branch .LOFacc%=\n"                                                                                                  \
-  ".LOFend%=:\n\t"                                                                                                        \
-  "s_mov_b64 exec, %[sv]"
+  "v_mul_f32_e32 %[w], v57, v52\n\t"
+#define OT_ROUND_F32(Z, MASK, SSH, CNT_N, CNT_T) \
+  OT_ROUND(Z, "f32", OT_LOADS_F32, OT_TEST_F32(Z), OT_FAR_F32, OT_EXACT_F32(Z), OT_NEAR_F32, MASK, SSH, CNT_N, CNT_T)
 
+template <int D, bool COUNT>
+struct ot_isa_rounds<float, D, COUNT> {
+  template <typename Terms>
+  static __device__ __forceinline__ void run(Terms& terms, const ot_group<float, D>* __restrict__ groups, const float (&xi)[D],
+                                             const ot_theta<float>& th, float root_side, uint32_t cur, bool more, uint32_t& c_nodes,
+                                             uint32_t& c_terms, uint32_t capacity, uint32_t* __restrict__ flags) {
+    using T = float;
+    constexpr uint32_t NCH = 1u << D, GPW = 64u / NCH;
+    constexpr uint32_t DEPTH = (NCH - 1u) * kMaxLevels<D> + NCH;
+    static_assert(sizeof(ot_group<float, 3>) == 192 && sizeof(ot_group<float, 2>) == 128, "the round addresses 192- / 128-byte sibling groups");
+    __shared__ uint32_t stack[DEPTH][GPW];  // entry-major: slot i of body g at (i * GPW + g) * 4
+    const uint32_t g = threadIdx.x / NCH, cc = threadIdx.x % NCH;
+    T spare = T(0);  // (the third coordinate's pair of operands is unused in 2D)
+    T& acc2 = D == 3 ? terms.acc[D - 1] : spare;
+    const T xi2 = D == 3 ? xi[D - 1] : T(0);
+    uint32_t more_v = more ? 1u : 0u, sp = 0, nsp = 0, gflag = 0, guard = capacity;
+    const uint32_t cc16 = cc * 16u, cc8 = (D == 3 ? 128u : 64u) + cc * 8u, gshift = threadIdx.x & (64u - NCH), ccp1 = cc + 1u;
+    const uint32_t stk = uint32_t(reinterpret_cast<uintptr_t>(&stack[0][g]));  // LDS byte address (low word of the flat one)
+    float lo = to_sgpr(th.lo), hi = to_sgpr(th.hi), thx = to_sgpr(th.exact), tiny = ot_consts<T>::tiny, eps = ot_consts<T>::eps,
+          meps = -ot_consts<T>::eps, m3eps = -(3.0f * ot_consts<T>::eps), sqmin = 0x1p-96f, rs = to_sgpr(root_side);
+    uint32_t nearbits = ot_near<T>::bits, gsz = uint32_t(sizeof(ot_group<float, D>)), depth = DEPTH;
+    asm volatile("" : "+s"(tiny), "+s"(eps), "+s"(meps), "+s"(m3eps), "+s"(sqmin), "+s"(nearbits), "+s"(gsz), "+s"(depth));
+    float d0, d1, d2, r2, y, gq, w, tt;
+    uint32_t oa, of;
+    uint64_t nonleaf, st, so, so2, take, open, act, sv, near;
+#define OT_OPERANDS                                                                                                        \
+  : [acc0] "+v"(terms.acc[0]), [acc1] "+v"(terms.acc[1]), [acc2] "+v"(acc2), [cur] "+v"(cur), [sp] "+v"(sp), [nsp] "+v"(nsp), \
+    OT_CNT_OPERANDS [guard] "+s"(guard), [gflag] "+s"(gflag), [d0] "=&v"(d0), [d1] "=&v"(d1), [d2] "=&v"(d2),              \
+    [r2] "=&v"(r2), [y] "=&v"(y), [g] "=&v"(gq), [w] "=&v"(w), [t] "=&v"(tt), [oa] "=&v"(oa), [of] "=&v"(of),             \
+    [nonleaf] "=&s"(nonleaf), [st] "=&s"(st), [so] "=&s"(so), [so2] "=&s"(so2), [take] "=&s"(take), [open] "=&s"(open),     \
+    [act] "=&s"(act), [sv] "=&s"(sv), [near] "=&s"(near)                                                                   \
+  : [more] "v"(more_v), [groups] "s"(groups), [xi0] "v"(xi[0]), [xi1] "v"(xi[1]), [xi2] "v"(xi2), [cc16] "v"(cc16), \
+    [cc8] "v"(cc8), [gshift] "v"(gshift), [ccp1] "v"(ccp1), [stk] "v"(stk), [lo] "s"(lo), [hi] "s"(hi), [theta] "s"(thx),  \
+    [tiny] "s"(tiny), [eps] "s"(eps), [meps] "s"(meps), [m3eps] "s"(m3eps), [sqmin] "s"(sqmin), [nearbits] "s"(nearbits),  \
+    [rootside] "s"(rs), [gsz] "s"(gsz), [depth] "s"(depth)                                                              \
+  : "vcc", "scc", "memory", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63"
+#define OT_CNT_OPERANDS [cn] "+v"(c_nodes), [ct] "+v"(c_terms),
+    if constexpr (COUNT && D == 3) asm volatile(OT_ROUND_F32(OT_KEEP, "0xff", "5", OT_CN, OT_CT) OT_OPERANDS);
+    if constexpr (COUNT && D == 2) asm volatile(OT_ROUND_F32(OT_DROP, "0xf", "6", OT_CN, OT_CT) OT_OPERANDS);
+#undef OT_CNT_OPERANDS
+#define OT_CNT_OPERANDS
+    if constexpr (!COUNT && D == 3) asm volatile(OT_ROUND_F32(OT_KEEP, "0xff", "5", "", "") OT_OPERANDS);
+    if constexpr (!COUNT && D == 2) asm volatile(OT_ROUND_F32(OT_DROP, "0xf", "6", "", "") OT_OPERANDS);
+#undef OT_CNT_OPERANDS
+#undef OT_OPERANDS
+    if (more && nsp > DEPTH && cc == 0) atomicOr(flags, kFlagStack);
+    if (gflag != 0u && threadIdx.x == 0) atomicOr(flags, kFlagWalk);
+  }
+};
+#undef OT_ROUND_F32
+#undef OT_NEAR_F32
+#undef OT_EXACT_F32
+#undef OT_FAR_F32
+#undef OT_TEST_F32
+#undef OT_LOADS_F32
+#undef OT_ROUND
+#undef OT_CT
+#undef OT_CN
+#undef OT_DROP
+#undef OT_KEEP
+
+// The two kernels of walk form 2: ot_force_kernel's call with the rounds as ISA.
+template <int D, bool COUNT>
+__global__ __launch_bounds__(64) void ot_force_isa_kernel(const ot_node<double>* __restrict__ rootrec,
+                                                          const ot_group<double, D>* __restrict__ groups,
+                                                          const uint32_t* __restrict__ list, uint32_t nlist,
+                                                          const double* __restrict__ x, double* __restrict__ a, double c,
+                                                          uint32_t first, double theta, uint32_t capacity,
+                                                          const double* __restrict__ root, uint32_t* __restrict__ flags,
+                                                          uint32_t* __restrict__ counters) {
+  ot_walk<double, D, COUNT, true>(ot_force_terms<double, D, kOtMono>{a, c}, rootrec, groups, list, nlist, x, first, theta, capacity,
+                                  root, flags, counters);
+}
 template <int D, bool COUNT>
 __global__ __launch_bounds__(64) void ot_force_isa_f32_kernel(const ot_node<float>* __restrict__ rootrec,
                                                               const ot_group<float, D>* __restrict__ groups,
@@ -2763,99 +2765,8 @@ __global__ __launch_bounds__(64) void ot_force_isa_f32_kernel(const ot_node<floa
                                                               uint32_t first, float theta, uint32_t capacity,
                                                               const float* __restrict__ root, uint32_t* __restrict__ flags,
                                                               uint32_t* __restrict__ counters) {
-  using T = float;
-  constexpr uint32_t NCH = 1u << D, GPW = 64u / NCH;
-  constexpr uint32_t DEPTH = (NCH - 1u) * kMaxLevels<D> + NCH;
-  static_assert(sizeof(ot_group<float, 3>) == 192 && sizeof(ot_group<float, 2>) == 128, "the round addresses 192- / 128-byte sibling groups");
-  __shared__ uint32_t stack[DEPTH][GPW];  // entry-major: slot i of body g at (i * GPW + g) * 4
-  const uint32_t g = threadIdx.x / NCH, cc = threadIdx.x % NCH;
-  const uint32_t t    = ot_xcd_contiguous_block(blockIdx.x, gridDim.x) * GPW + g;
-  const bool valid    = t < nlist;
-  const uint32_t body = valid ? list[t] : first;
-  const ot_theta<T> th(theta);
-  const pair_consts<T> pc;
-  const T root_side = root[D];
-  T xi[3] = {T(0), T(0), T(0)}, acc[3] = {T(0), T(0), T(0)};  // (the third pair is an unused operand in 2D)
-#pragma unroll
-  for (int k = 0; k < D; ++k) xi[k] = valid ? x[uint64_t(body) * D + k] : T(0);
-  uint32_t c_nodes = 0, c_terms = 0;
-  uint32_t cur = 0;
-  bool more = false;
-  if (valid) {  // the root is examined alone, exactly as in ot_force_kernel
-    const ot_node<T> nd = *rootrec;
-    T di[D], a0[D];
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-      di[k] = nd.p[k] - xi[k];
-      a0[k] = T(0);
-    }
-    const T d2f     = ot_dist2_fused<T, D>(di);
-    const T y0      = ot_rsq(d2f);
-    const bool leaf = nd.fc >= kOtBody;
-    const bool take = leaf || ot_accept<T, D>(!leaf, root_side, di, y0, th);
-    {
-      const bool on0    = take && cc == 0;
-      const uint64_t m0 = __builtin_amdgcn_ballot_w64(on0);
-      if (m0 != 0ull) ot_accumulate<T, D>(on0, m0, a0, di, nd.m, d2f, y0, pc);
-    }
-#pragma unroll
-    for (int k = 0; k < D; ++k) acc[k] = a0[k];
-    if (COUNT && cc == 0) {
-      c_nodes = 1;
-      c_terms = take;
-    }
-    more = !take;
-    cur  = nd.fc;
-  }
-  uint32_t more_v = more ? 1u : 0u, sp = 0, nsp = 0, gflag = 0, guard = capacity;
-  const uint32_t cc16 = cc * 16u, cc8 = (D == 3 ? 128u : 64u) + cc * 8u, gshift = threadIdx.x & (64u - NCH), ccp1 = cc + 1u;
-  const uint32_t stk = uint32_t(reinterpret_cast<uintptr_t>(&stack[0][g]));
-  float lo = to_sgpr(th.lo), hi = to_sgpr(th.hi), thx = to_sgpr(th.exact), tiny = ot_consts<T>::tiny, eps = ot_consts<T>::eps,
-        meps = -ot_consts<T>::eps, m3eps = -(3.0f * ot_consts<T>::eps), sqmin = 0x1p-96f, rs = to_sgpr(root_side);
-  uint32_t nearbits = ot_near<T>::bits, gsz = uint32_t(sizeof(ot_group<float, D>)), depth = DEPTH;
-  asm volatile("" : "+s"(tiny), "+s"(eps), "+s"(meps), "+s"(m3eps), "+s"(sqmin), "+s"(nearbits), "+s"(gsz), "+s"(depth));
-  float d0, d1, d2, r2, y, gq, w, tt;
-  uint32_t oa, of;
-  uint64_t nonleaf, st, so, so2, take, open, act, sv, near;
-#define OT_OPERANDS                                                                                                        \
-  : [acc0] "+v"(acc[0]), [acc1] "+v"(acc[1]), [acc2] "+v"(acc[2]), [cur] "+v"(cur), [sp] "+v"(sp), [nsp] "+v"(nsp),          \
-    OT_CNT_OPERANDS [guard] "+s"(guard), [gflag] "+s"(gflag), [d0] "=&v"(d0), [d1] "=&v"(d1), [d2] "=&v"(d2),              \
-    [r2] "=&v"(r2), [y] "=&v"(y), [g] "=&v"(gq), [w] "=&v"(w), [t] "=&v"(tt), [oa] "=&v"(oa), [of] "=&v"(of),             \
-    [nonleaf] "=&s"(nonleaf), [st] "=&s"(st), [so] "=&s"(so), [so2] "=&s"(so2), [take] "=&s"(take), [open] "=&s"(open),     \
-    [act] "=&s"(act), [sv] "=&s"(sv), [near] "=&s"(near)                                                                   \
-  : [more] "v"(more_v), [groups] "s"(groups), [xi0] "v"(xi[0]), [xi1] "v"(xi[1]), [xi2] "v"(xi[2]), [cc16] "v"(cc16),     \
-    [cc8] "v"(cc8), [gshift] "v"(gshift), [ccp1] "v"(ccp1), [stk] "v"(stk), [lo] "s"(lo), [hi] "s"(hi), [theta] "s"(thx),  \
-    [tiny] "s"(tiny), [eps] "s"(eps), [meps] "s"(meps), [m3eps] "s"(m3eps), [sqmin] "s"(sqmin), [nearbits] "s"(nearbits),  \
-    [rootside] "s"(rs), [gsz] "s"(gsz), [depth] "s"(depth)                                                              \
-  : "vcc", "scc", "memory", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63"
-#define OT_CNT_OPERANDS [cn] "+v"(c_nodes), [ct] "+v"(c_terms),
-  if constexpr (COUNT && D == 3) asm volatile(OT_ISA_TEXT_F32(OT_KEEP, "0xff", "5", OT_CN, OT_CT) OT_OPERANDS);
-  if constexpr (COUNT && D == 2) asm volatile(OT_ISA_TEXT_F32(OT_DROP, "0xf", "6", OT_CN, OT_CT) OT_OPERANDS);
-#undef OT_CNT_OPERANDS
-#define OT_CNT_OPERANDS
-  if constexpr (!COUNT && D == 3) asm volatile(OT_ISA_TEXT_F32(OT_KEEP, "0xff", "5", "", "") OT_OPERANDS);
-  if constexpr (!COUNT && D == 2) asm volatile(OT_ISA_TEXT_F32(OT_DROP, "0xf", "6", "", "") OT_OPERANDS);
-#undef OT_CNT_OPERANDS
-#undef OT_OPERANDS
-  if (more && nsp > DEPTH && cc == 0) atomicOr(flags, kFlagStack);
-  if (gflag != 0u && threadIdx.x == 0) atomicOr(flags, kFlagWalk);
-#pragma unroll
-  for (uint32_t off = NCH / 2; off > 0; off >>= 1) {
-#pragma unroll
-    for (int k = 0; k < D; ++k) acc[k] += __shfl_xor(acc[k], int(off), 64);
-    if (COUNT) {
-      c_nodes += __shfl_xor(c_nodes, int(off), 64);
-      c_terms += __shfl_xor(c_terms, int(off), 64);
-    }
-  }
-  if (valid && cc == 0) {
-#pragma unroll
-    for (int k = 0; k < D; ++k) a[uint64_t(body - first) * D + k] = c * acc[k];
-    if (COUNT) {
-      counters[uint64_t(body) * 2 + 0] = c_nodes;
-      counters[uint64_t(body) * 2 + 1] = c_terms;
-    }
-  }
+  ot_walk<float, D, COUNT, true>(ot_force_terms<float, D, kOtMono>{a, c}, rootrec, groups, list, nlist, x, first, theta, capacity, root,
+                                 flags, counters);
 }
 
 }  // namespace nbody

@@ -644,43 +644,47 @@ def test_sharded_octree_torch_path(nb):
     assert np.array_equal(np.concatenate([s.a.cpu().numpy() for s in sims]), ref.a)
 
 
-def _deep_chain(nb, levels):
-    """A legal but pathological system: the root cube is [-8, 8]^3, centred on the origin (bodies at -7 and +7 in every
-    coordinate are the scalar extremes, +-1: src/octree.h:93-112), and a chain of cells [0, 16/2^k]^3, k = 1..levels, converges
-    on the origin.  In every cell of the chain two octants hold a
-    pair of bodies (cells that a theta = 0 walk must open) and the low octant continues the chain, so a walk that descends
-    the chain first — child 0 is popped first — holds 2 more pending cells per level."""
-    pts = [(-7.0, -7.0, -7.0), (7.0, 7.0, 7.0)]
+def _deep_chain(nb, dtype, dim, levels, open_per_level):
+    """A legal but pathological system: the root cube is [-8, 8]^D, centred on the origin (bodies at -7 and +7 in every
+    coordinate are the scalar extremes, +-1: src/octree.h:93-112), and a chain of cells [0, 16/2^k]^D, k = 1..levels, converges
+    on the origin.  In every cell of the chain, of side s, the first `open_per_level` children after child 0 (in child-index
+    order, bit i = coordinate i high) hold a pair of bodies, at (0.75 | 0.25) s and (0.80 | 0.20) s (cells that a theta = 0 walk
+    must open), and child 0 continues the chain, so a walk that descends the chain first — child 0 is popped first — holds
+    `open_per_level` more pending cells per level."""
+    pts = [(-7.0,) * dim, (7.0,) * dim]
     for k in range(1, levels + 1):
         s = 16.0 / 2.0 ** k
-        pts += [(0.75 * s, 0.25 * s, 0.25 * s), (0.80 * s, 0.20 * s, 0.20 * s),
-                (0.25 * s, 0.75 * s, 0.25 * s), (0.20 * s, 0.80 * s, 0.20 * s)]
+        for child in range(1, open_per_level + 1):
+            high = [(child >> i) & 1 for i in range(dim)]
+            pts += [tuple((0.75 if h else 0.25) * s for h in high), tuple((0.80 if h else 0.20) * s for h in high)]
     s = 16.0 / 2.0 ** levels
-    pts.append((0.1 * s, 0.1 * s, 0.1 * s))
-    hs = nb.HostSystem(nb.F64, 3, len(pts))
+    pts.append((0.1 * s,) * dim)
+    hs = nb.HostSystem(dtype, dim, len(pts))
     hs.x[:] = np.array(pts)
     hs.m[:] = 1.0
     hs.c, hs.dt = 1.0, 1e-3
     return hs
 
 
-def _walk_with_canaries(nb, hs, theta, form, budget=0):
+def _walk_with_canaries(nb, hs, dtype, dim, theta, form, budget=0):
     """One octree force phase with the accelerations written into the middle of a larger canary-filled buffer: returns
-    (a, the NbodyError message of nbody_octree_info or None) after checking that nothing outside a's rows was written."""
+    (a, the counters, the NbodyError message of nbody_octree_info or None) after checking that nothing outside a's rows was
+    written."""
     import ctypes as C
     import torch
     dev = torch.device("cuda", 0)
+    tt = torch.float64 if dtype == nb.F64 else torch.float32
     n, pad, canary = hs.n, 4096, -7.25
     to = lambda arr: torch.from_numpy(np.ascontiguousarray(arr)).to(dev)
     m, x, v = to(hs.m), to(hs.x), to(hs.v)
-    big = torch.full((n + 2 * pad, 3), canary, dtype=torch.float64, device=dev)
-    ao = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+    big = torch.full((n + 2 * pad, dim), canary, dtype=tt, device=dev)
+    ao = torch.zeros((n, dim), dtype=tt, device=dev)
     st = nb.nbody_state()
     st.m, st.x, st.v, st.ao = m.data_ptr(), x.data_ptr(), v.data_ptr(), ao.data_ptr()
     st.a = big[pad:].data_ptr()
-    st.dt, st.c, st.sz, st.first, st.count, st.dtype, st.dim = hs.dt, hs.c, n, 0, n, nb.F64, 3
+    st.dt, st.c, st.sz, st.first, st.count, st.dtype, st.dim = hs.dt, hs.c, n, 0, n, dtype, dim
     stream = torch.cuda.current_stream(dev).cuda_stream
-    tree = nb.Octree(nb.F64, 3, n, 0)
+    tree = nb.Octree(dtype, dim, n, 0)
     tree.set_walk(form)
     tree.set_step_budget(budget)
     tree.enable_counters(True)
@@ -699,32 +703,43 @@ def _walk_with_canaries(nb, hs, theta, form, budget=0):
     return out[pad:pad + n].copy(), cnt, err
 
 
+# (dtype, dim, cells to open per chain level, chain levels that fit the stack, chain levels that overflow it): a theta = 0 walk
+# holds about open_per_level * levels pending cells, against (2^D - 1) * 21 + 2^D = 155 slots per body in 3D and 100 in 2D.
+# Float cannot reach the 78 levels that two cells per level need (the far weight y^3 would overflow): six per level reach it at 30.
+_EXIT_CASES = [(1, 3, 2, 60, 90), (0, 3, 6, 20, 30), (1, 2, 3, 25, 40), (0, 2, 3, 25, 40)]
+
+
+@pytest.mark.parametrize("dtype,dim,open_per_level,l_fit,l_over", _EXIT_CASES, ids=["f64-3d", "f32-3d", "f64-2d", "f32-2d"])
 @pytest.mark.parametrize("form", [2, 1])   # the visit round as ISA, the compiler-scheduled kernel
-def test_octree_walk_stack_full_and_step_budget_exits(nb, oracle, form):
-    """the two emergency exits of the walk, which no test took.  (1) Stack full: a chain of 90 nested cells
-    with two more cells to open at every level makes a theta = 0 walk hold > 155 pending cells ((2^D - 1) * 21 + 2^D slots per
-    body); the kernel must leave, raise kFlagStack (reported by nbody_octree_info) and write nothing outside a — in the ISA form
-    the overflowing push goes past the end of the block's LDS and is dropped by the hardware.  The same chain 60 levels deep
-    (120 pending) fits: forces within tolerance of the oracle, counters bit-exact.  (2) Step budget: with a budget of 5 visit
-    rounds (nbody_octree_set_step_budget) on an ordinary tree, bodies are abandoned and kFlagWalk is reported; with the default
-    budget the same tree is clean."""
-    a, cnt, err = _walk_with_canaries(nb, _deep_chain(nb, 90), 0.0, form)
+def test_octree_walk_stack_full_and_step_budget_exits(nb, oracle, form, dtype, dim, open_per_level, l_fit, l_over):
+    """the two emergency exits of the walk, in every instantiation of the round (the stack's stride, the
+    child mask and the depth differ by dimension, the arithmetic by precision).  (1) Stack full: a chain of l_over nested cells
+    with open_per_level more cells to open at every level makes a theta = 0 walk hold more pending cells than the
+    (2^D - 1) * 21 + 2^D slots per body (155 in 3D, 100 in 2D); the kernel must leave, raise kFlagStack (reported by
+    nbody_octree_info) and write nothing outside a — in the ISA form the overflowing push goes past the end of the block's LDS
+    and is dropped by the hardware.  The same chain l_fit levels deep fits: forces within tolerance of the oracle, counters
+    bit-exact.  (2) Step budget: with a budget of 5 visit rounds (nbody_octree_set_step_budget) on an ordinary tree, bodies are
+    abandoned and kFlagWalk is reported; with the default budget the same tree is clean."""
+    a, cnt, err = _walk_with_canaries(nb, _deep_chain(nb, dtype, dim, l_over, open_per_level), dtype, dim, 0.0, form)
     assert err is not None and "per-body stack" in err, err
     assert np.all(np.isfinite(a))
-    hs = _deep_chain(nb, 60)
-    a, cnt, err = _walk_with_canaries(nb, hs, 0.0, form)
+    hs = _deep_chain(nb, dtype, dim, l_fit, open_per_level)
+    a, cnt, err = _walk_with_canaries(nb, hs, dtype, dim, 0.0, form)
     assert err is None, err
-    ref = oracle.State(oracle.F64, 3, hs.n)
+    ref = oracle.State(dtype, dim, hs.n)
     ref.m[:], ref.x[:], ref.c, ref.dt = hs.m, hs.x, hs.c, hs.dt
     ocnt, osize, omass = oracle.octree_step_force(ref, 0.0, want_counts=True)
     assert np.array_equal(cnt, ocnt)
-    err_a = np.abs(a - ref.a).max(axis=1)
-    assert np.all(err_a <= 1e-12 * np.maximum(np.abs(ref.a).max(axis=1), 1.0))
-    gal = nb.build_model(nb.F64, 3, "galaxy", 20000)
-    a5, _, err = _walk_with_canaries(nb, gal, 0.5, form, budget=5)
+    a64, r64 = a.astype(np.float64), np.asarray(ref.a, np.float64)
+    err_a = np.abs(a64 - r64).max(axis=1)
+    scale = np.maximum(np.abs(r64).max(axis=1), 1.0)
+    print(f"fitting chain dtype={dtype} dim={dim} form={form}: n={hs.n} max scaled force error {np.max(err_a / scale):.3e}")
+    assert np.all(err_a <= FORCE_TOL[dtype] * scale)
+    gal = nb.build_model(dtype, dim, "galaxy", 20000)
+    a5, _, err = _walk_with_canaries(nb, gal, dtype, dim, 0.5, form, budget=5)
     assert err is not None and "visit rounds" in err and "nbody_octree_set_step_budget" in err, err
     assert np.all(np.isfinite(a5))
-    afull, _, err = _walk_with_canaries(nb, gal, 0.5, form)
+    afull, _, err = _walk_with_canaries(nb, gal, dtype, dim, 0.5, form)
     assert err is None and not np.array_equal(a5, afull)
 
 
@@ -763,12 +778,12 @@ def test_octree_build_forms_are_bitwise_equal(nb, dtype, dim):
         outs = []
         for form in (1, 3, 0):
             # a shallow tree first (a galaxy of as many bodies), then the chain in the same buffers
-            shallow = nb.build_model(1, 3, "galaxy", _deep_chain(nb, 60).n)
+            shallow = nb.build_model(1, 3, "galaxy", _deep_chain(nb, 1, 3, 60, 2).n)
             dev = nb.DeviceSystem.from_host(shallow)
             dev.octree.set_build(form)
             dev.octree_force(0.5)
             dev.octree.info(dev.stream)
-            dev.upload(_deep_chain(nb, 60))
+            dev.upload(_deep_chain(nb, 1, 3, 60, 2))
             dev.octree_force(0.0)
             dev.sync()
             outs.append((dev.octree.info(dev.stream), dev.download().a.copy()))
