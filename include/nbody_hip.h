@@ -94,7 +94,7 @@ typedef struct nbody_state {
  *      nbody_neighbours_create_on, nbody_neighbours_destroy, nbody_neighbours_compute, nbody_neighbours_read,
  *      nbody_neighbours_closest_pair.  Additive, same version: all-pairs k nearest neighbours, local densities and the density
  *      centre, nbody_knn_create, nbody_knn_create_on, nbody_knn_destroy, nbody_knn_compute, nbody_knn_read,
- *      nbody_knn_density_centre. */
+ *      nbody_knn_density_centre; nbody_knn_create_method and nbody_knn_method (the tree-pruned method of the same handle). */
 #define NBODY_HIP_ABI_VERSION 2004
 int nbody_abi_version(void);
 
@@ -646,6 +646,25 @@ int  nbody_neighbours_closest_pair(nbody_neighbours* h, uint32_t* i, uint32_t* j
 typedef struct nbody_knn nbody_knn;
 int  nbody_knn_create(nbody_knn** out, int dtype, int dim, uint32_t n, int k);                /* on the current device */
 int  nbody_knn_create_on(nbody_knn** out, int dtype, int dim, uint32_t n, int k, int device); /* device < 0: the current one */
+/* The method of a handle.  ALL_PAIRS (what create and create_on make): every body meets every other one, O(n^2).  TREE: an EXACT
+ * search that prunes with bounding boxes over a space-sorted copy of the bodies, for large n.
+ * Contract of TREE: every output of nbody_knn_read (what = 0, 1, 2) and nbody_knn_density_centre equals, BIT FOR BIT, what an
+ * ALL_PAIRS handle of the same (dtype, dim, n, k) gives on the same state, for any finite positions and any order of the bodies in
+ * the state: the tie rule above is exact, so the result is a set with one correct answer.  That covers exact ties, coincident bodies,
+ * n <= k (unused slots 0xffffffff / +inf, rho = 0) and n = 1.  The state is neither changed nor permuted.  Speed depends on the input
+ * (clustering, the order does not matter: the bodies are sorted along a Morton curve by every compute); results do not.  Non-finite
+ * positions are outside the contract (the call stays memory-safe; the outputs of the two methods may differ).
+ *  - create_method takes the argument checks of create_on in the same order, `method` (NBODY_ERR_ARG outside {0, 1}) after k.  A TREE
+ *    handle allocates the packed records, the sorted records, the boxes, the keys, the permutation and the sort's scratch (sized
+ *    at create from n), the three result arrays and the summary record — and NOT the chunks' partial lists of ALL_PAIRS.
+ *  - compute dispatches on the handle's method; argument errors, state rules, read and density_centre are the same for both.  For
+ *    TREE it is still asynchronous, allocates nothing and may be recorded into a step graph; the number of launches (pack, bounds,
+ *    keys, the sort, gather, upper levels, walk, finish, summary) is a function of n alone.
+ *  - nbody_knn_method: the method the handle was made for; h NULL: -1, and nbody_last_error() says so. */
+#define NBODY_KNN_ALL_PAIRS 0
+#define NBODY_KNN_TREE      1
+int  nbody_knn_create_method(nbody_knn** out, int dtype, int dim, uint32_t n, int k, int method, int device); /* device < 0: current */
+int  nbody_knn_method(const nbody_knn* h);
 void nbody_knn_destroy(nbody_knn* h);                                                         /* NULL: no-op */
 /* The k neighbours, rho of all bodies and the summary at (s->m, s->x), into the handle.  Asynchronous, recordable. */
 int  nbody_knn_compute(nbody_knn* h, const nbody_state* s, void* stream);

@@ -71,6 +71,7 @@ ABI_SYMBOLS = [
     "nbody_neighbours_create", "nbody_neighbours_create_on", "nbody_neighbours_destroy", "nbody_neighbours_compute",
     "nbody_neighbours_read", "nbody_neighbours_closest_pair",
     "nbody_knn_create", "nbody_knn_create_on", "nbody_knn_destroy", "nbody_knn_compute", "nbody_knn_read", "nbody_knn_density_centre",
+    "nbody_knn_create_method", "nbody_knn_method",
 ]
 ABI_MAJOR = 2
 COMM_ID_BYTES = 128
@@ -136,6 +137,8 @@ def lib():
         L.nbody_neighbours_closest_pair.argtypes = [vp, vp, vp, vp, vp]
         L.nbody_knn_create.argtypes = [vp, C.c_int, C.c_int, C.c_uint32, C.c_int]
         L.nbody_knn_create_on.argtypes = [vp, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_int]
+        L.nbody_knn_create_method.argtypes = [vp, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_int]
+        L.nbody_knn_method.argtypes = [vp]
         L.nbody_knn_destroy.restype = None
         L.nbody_knn_destroy.argtypes = [vp]
         L.nbody_knn_compute.argtypes = [vp, vp, vp]
@@ -625,14 +628,28 @@ class Neighbours:
 
 
 class Knn:
-    """All-pairs k nearest neighbours, local densities and the density centre (nbody_knn_*): owns the packed records, the chunks'
-    partial lists and the results.  k is fixed here, 1 <= k <= 16."""
+    """k nearest neighbours, local densities and the density centre (nbody_knn_*): owns the packed records, the method's work
+    arrays and the results.  k is fixed here, 1 <= k <= 16.  method: "all-pairs" (every pair, O(n^2)) or "tree" (exact, pruned with
+    bounding boxes over a space-sorted copy, for large n): the same outputs bit for bit."""
 
-    def __init__(self, dtype, dim, n, k, device=-1):
+    METHODS = {"all-pairs": 0, "tree": 1}
+
+    def __init__(self, dtype, dim, n, k, device=-1, method="all-pairs"):
         """device: where the handle's buffers live (-1: the calling thread's current device)."""
         self.h = C.c_void_p()
         self.dtype, self.dim, self.n, self.k = dtype, dim, n, k
-        _check(lib().nbody_knn_create_on(C.byref(self.h), dtype, dim, C.c_uint32(n), k, device))
+        if method not in self.METHODS:
+            raise ValueError(f"Knn method must be one of {sorted(self.METHODS)}, got {method!r}")
+        _check(lib().nbody_knn_create_method(C.byref(self.h), dtype, dim, C.c_uint32(n), k, self.METHODS[method], device))
+
+    @property
+    def method(self):
+        """The method the handle was made for: "all-pairs" or "tree" (nbody_knn_method)."""
+        m = lib().nbody_knn_method(self.h)
+        for name, v in self.METHODS.items():
+            if v == m:
+                return name
+        raise RuntimeError(lib().nbody_last_error().decode())
 
     def close(self):
         if self.h:
@@ -727,6 +744,7 @@ class DeviceSystem:
         self._hermite6 = None
         self._neighbours = None
         self._knn = {}
+        self._knn_other = {}
 
     @classmethod
     def from_host(cls, hs, device=0):
@@ -753,9 +771,10 @@ class DeviceSystem:
         if self._neighbours is not None:
             self._neighbours.close()
             self._neighbours = None
-        for h in self._knn.values():
+        for h in list(self._knn.values()) + list(self._knn_other.values()):
             h.close()
         self._knn = {}
+        self._knn_other = {}
         if self.h:
             lib().nbody_destroy(self.h)
             self.h = C.c_void_p()
@@ -957,32 +976,35 @@ class DeviceSystem:
         return h.closest_pair(self.stream)
 
     # k nearest neighbours, local densities, density centre (no reference counterpart)
-    def knn_handle(self, k):
-        """The Knn handle of this system for k, made at the first use and closed with the system."""
-        if k not in self._knn:
-            self._knn[k] = Knn(self.dtype, self.dim, self.n, k, self.device)
-        return self._knn[k]
+    def knn_handle(self, k, method="all-pairs"):
+        """The Knn handle of this system for (k, method), made at the first use and closed with the system."""
+        handles = self._knn if method == "all-pairs" else self._knn_other  # _knn: the all-pairs handles, by k
+        key = k if method == "all-pairs" else (k, method)
+        if key not in handles:
+            handles[key] = Knn(self.dtype, self.dim, self.n, k, self.device, method)
+        return handles[key]
 
-    def knn_compute(self, k):
-        """nbody_knn_compute on the state as it is; a StepGraph may record it (the handle for k is made before the recording)."""
-        self.knn_handle(k).compute(self.state(), self.stream)
+    def knn_compute(self, k, method="all-pairs"):
+        """nbody_knn_compute on the state as it is; a StepGraph may record it (the handle for (k, method) is made before the
+        recording)."""
+        self.knn_handle(k, method).compute(self.state(), self.stream)
 
-    def knn(self, k):
+    def knn(self, k, method="all-pairs"):
         """(idx (n, k) uint32, d2 (n, k) of T): the k nearest neighbours of every body, ascending in (d2, index), and their unsoftened
         squared distances; unused slots (n <= k) hold (0xffffffff, +inf) (blocking)."""
-        h = self.knn_handle(k)
+        h = self.knn_handle(k, method)
         h.compute(self.state(), self.stream)
         return h.read(0, self.stream), h.read(1, self.stream)
 
-    def local_density(self, k=6):
+    def local_density(self, k=6, method="all-pairs"):
         """rho (n,) of T: Casertano & Hut's local density from the k-th neighbour (blocking)."""
-        h = self.knn_handle(k)
+        h = self.knn_handle(k, method)
         h.compute(self.state(), self.stream)
         return h.read(2, self.stream)
 
-    def density_centre(self, k=6):
+    def density_centre(self, k=6, method="all-pairs"):
         """(x_dc (dim,), r_c, rho_c): the density centre, core radius and core density from the k-th-neighbour densities (blocking)."""
-        h = self.knn_handle(k)
+        h = self.knn_handle(k, method)
         h.compute(self.state(), self.stream)
         return h.density_centre(self.stream)
 

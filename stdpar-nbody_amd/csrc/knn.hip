@@ -16,6 +16,8 @@
 //           rho_c = sum rho^2 / sum rho.  Accumulated in double for both types, rounded to T at the end.  sum rho = 0 (k = 1, n <= k)
 //           or a non-finite rho (coincident bodies) gives NaN by IEEE rules: not an error.
 //
+// A handle made with NBODY_KNN_TREE computes the same outputs, bit for bit, by the tree-pruned search of nntree.inc (included below);
+// what follows is the ALL_PAIRS method.
 // Four launches per compute, all on the caller's stream, nothing allocated after nbody_knn_create:
 //   pack     pair_sweep.hpp's: one lane per record {x[3], m}, padded with records at the origin to whole tiles.  A padding record
 //            never becomes a neighbour because of an INDEX BOUND: every slice of 64 records that reaches past n runs the checked
@@ -43,6 +45,7 @@
 // Bound: FP64 / FP32 VALU issue; per pair D subtractions, D chain operations, (U - 1) / U min + 1 / U compare, and for a batch that
 // takes the branch U insertions of K compares and 2 K selects (3 K v_cndmask in double).
 #include "pair_sweep.hpp"
+#include "radix_sort.hpp"
 
 #pragma clang fp contract(off)
 
@@ -189,25 +192,12 @@ __global__ __launch_bounds__(kHBlock) void knn_sweep_kernel(const pair_rec<T>* _
   }
 }
 
-// ---- finish --------------------------------------------------------------------------------------------------------------------
+// The tail of a body's list, shared by the all-pairs finish and the tree walk (nntree.inc) so that both write the same bits: row i of
+// idx[n][k] and d2[n][k], and rho[i].
 template <typename T, int D, int K>
-__global__ __launch_bounds__(kHBlock) void knn_finish_kernel(const T* __restrict__ part_d, const uint32_t* __restrict__ part_j,
-                                                             const pair_rec<T>* __restrict__ recs, uint32_t* __restrict__ idx,
-                                                             T* __restrict__ d2, T* __restrict__ rho, uint32_t n, uint32_t chunks, int k) {
-  const uint32_t i = blockIdx.x * kHBlock + threadIdx.x;
-  if (i >= n) return;
-  T ld[K];
-  uint32_t lj[K];
-#pragma unroll
-  for (int s = 0; s < K; ++s) {
-    ld[s] = part_d[uint64_t(i) * K + s];
-    lj[s] = part_j[uint64_t(i) * K + s];
-  }
-  for (uint32_t ch = 1; ch < chunks; ++ch) {
-    const uint64_t row = (uint64_t(ch) * n + i) * K;
-#pragma unroll
-    for (int s = 0; s < K; ++s) knn_insert<T, K, true>(ld, lj, part_d[row + s], part_j[row + s]);
-  }
+__device__ __forceinline__ void knn_finish_tail(const T (&ld)[K], const uint32_t (&lj)[K], const pair_rec<T>* __restrict__ recs,
+                                                uint32_t* __restrict__ idx, T* __restrict__ d2, T* __restrict__ rho, uint32_t i, uint32_t n,
+                                                int k) {
   T M = T(0), dk = pair_inf<T>();
   uint32_t jk = kNoNeighbour;
 #pragma unroll
@@ -228,6 +218,28 @@ __global__ __launch_bounds__(kHBlock) void knn_finish_kernel(const T* __restrict
     else r = M / (T(3.14159265358979323846264338327950288) * dk);
   }
   rho[i] = r;
+}
+
+// ---- finish --------------------------------------------------------------------------------------------------------------------
+template <typename T, int D, int K>
+__global__ __launch_bounds__(kHBlock) void knn_finish_kernel(const T* __restrict__ part_d, const uint32_t* __restrict__ part_j,
+                                                             const pair_rec<T>* __restrict__ recs, uint32_t* __restrict__ idx,
+                                                             T* __restrict__ d2, T* __restrict__ rho, uint32_t n, uint32_t chunks, int k) {
+  const uint32_t i = blockIdx.x * kHBlock + threadIdx.x;
+  if (i >= n) return;
+  T ld[K];
+  uint32_t lj[K];
+#pragma unroll
+  for (int s = 0; s < K; ++s) {
+    ld[s] = part_d[uint64_t(i) * K + s];
+    lj[s] = part_j[uint64_t(i) * K + s];
+  }
+  for (uint32_t ch = 1; ch < chunks; ++ch) {
+    const uint64_t row = (uint64_t(ch) * n + i) * K;
+#pragma unroll
+    for (int s = 0; s < K; ++s) knn_insert<T, K, true>(ld, lj, part_d[row + s], part_j[row + s]);
+  }
+  knn_finish_tail<T, D, K>(ld, lj, recs, idx, d2, rho, i, n, k);
 }
 
 // ---- summary -------------------------------------------------------------------------------------------------------------------
@@ -292,12 +304,14 @@ __global__ __launch_bounds__(kKnnSumBlock) void knn_summary_kernel(const T* __re
   }
 }
 
+#include "nntree.inc"
+
 }  // namespace nbody
 
 using namespace nbody;
 
 // started: nbody_knn_compute has run (host call order, which a recorded step replays).  recs: pair_rec<T>[padded]; part: the chunks'
-// d2 lists, T[chunks][n][K].
+// d2 lists, T[chunks][n][K] (ALL_PAIRS only).
 struct nbody_knn : hermite_handle {
   int k = 0, K = 0;
   uint32_t* part_j = nullptr;  // [chunks][n][K]: the lists' indices
@@ -305,6 +319,15 @@ struct nbody_knn : hermite_handle {
   void* d2         = nullptr;  // T[n][k]
   void* rho        = nullptr;  // T[n]
   void* summary    = nullptr;  // T[kKnnSummaryLen]
+  // NBODY_KNN_TREE only (nntree.inc); part and part_j stay NULL there
+  int method        = NBODY_KNN_ALL_PAIRS;
+  nntree_shape tree{};
+  void* sorted      = nullptr;             // nntree_rec<T>[padded]
+  void* boxes       = nullptr;             // nntree_box<T>[2 leaves], heap order
+  void* bounds      = nullptr;             // nntree_box<T>[bounds_blocks]
+  uint64_t* keys[2] = {nullptr, nullptr};  // [n] each
+  uint32_t* perm[2] = {nullptr, nullptr};  // [n] each: the sort's index buffers
+  uint32_t* hist    = nullptr;             // radix_sort_scratch_words(n)
 };
 
 namespace nbody {
@@ -329,6 +352,43 @@ static int knn_launch(nbody_knn* h, const nbody_state* s, hipStream_t st) {
   return NBODY_OK;
 }
 
+// The TREE method: pack, bounds, keys, sort, gather + bucket boxes, upper levels, walk, finish, summary.  The launch count follows
+// from n alone (the sort's form does).
+template <typename T, int D, int K>
+static int knn_tree_launch(nbody_knn* h, const nbody_state* s, hipStream_t st) {
+  const nntree_shape& t = h->tree;
+  auto* recs            = static_cast<pair_rec<T>*>(h->recs);
+  auto* sorted          = static_cast<nntree_rec<T>*>(h->sorted);
+  auto* boxes           = static_cast<nntree_box<T>*>(h->boxes);
+  auto* bounds          = static_cast<nntree_box<T>*>(h->bounds);
+  T* rho                = static_cast<T*>(h->rho);
+  const uint32_t n      = h->n;
+  hipLaunchKernelGGL((pair_pack_kernel<T, D>), dim3(h->padded / kHBlock), dim3(kHBlock), 0, st, static_cast<const T*>(s->m),
+                     static_cast<const T*>(s->x), recs, n, h->padded);
+  NB_HIP(hipGetLastError());
+  hipLaunchKernelGGL((nntree_bounds_kernel<T, D>), dim3(t.bounds_blocks), dim3(kNtBlock), 0, st, recs, bounds, n);
+  NB_HIP(hipGetLastError());
+  hipLaunchKernelGGL((nntree_keys_kernel<T, D>), dim3((n + kNtBlock - 1) / kNtBlock), dim3(kNtBlock), 0, st, recs, bounds, t.bounds_blocks,
+                     h->keys[0], n);
+  NB_HIP(hipGetLastError());
+  int fin = 0;
+  if (int r = radix_sort_pairs(h->keys, h->perm, n, D == 3 ? 63 : 64, h->hist, st, &fin)) return r;
+  hipLaunchKernelGGL((nntree_gather_kernel<T, D>), dim3(h->padded / kNtBlock), dim3(kNtBlock), 0, st, recs, h->perm[fin], sorted,
+                     boxes + t.leaves, n, t.buckets);
+  NB_HIP(hipGetLastError());
+  hipLaunchKernelGGL((nntree_upper_kernel<T, D>), dim3(1), dim3(kNtUpper), 0, st, boxes, n, t.levels);
+  NB_HIP(hipGetLastError());
+  hipLaunchKernelGGL((nntree_walk_kernel<T, D, K>), dim3(h->padded / kNtBlock), dim3(kNtBlock), 0, st, sorted, boxes, h->idx,
+                     static_cast<T*>(h->d2), n, t.levels, t.buckets, h->k);
+  NB_HIP(hipGetLastError());
+  hipLaunchKernelGGL((nntree_finish_kernel<T, D, K>), dim3((n + kNtBlock - 1) / kNtBlock), dim3(kNtBlock), 0, st, recs, h->idx,
+                     static_cast<T*>(h->d2), rho, n, h->k);
+  NB_HIP(hipGetLastError());
+  hipLaunchKernelGGL((knn_summary_kernel<T, D>), dim3(1), dim3(kKnnSumBlock), 0, st, rho, recs, static_cast<T*>(h->summary), n);
+  NB_HIP(hipGetLastError());
+  return NBODY_OK;
+}
+
 }  // namespace nbody
 
 extern "C" int nbody_knn_create(nbody_knn** out, int dtype, int dim, uint32_t n, int k) {
@@ -336,8 +396,21 @@ extern "C" int nbody_knn_create(nbody_knn** out, int dtype, int dim, uint32_t n,
 }
 
 extern "C" int nbody_knn_create_on(nbody_knn** out, int dtype, int dim, uint32_t n, int k, int device) {
+  return nbody_knn_create_method(out, dtype, dim, n, k, NBODY_KNN_ALL_PAIRS, device);
+}
+
+extern "C" int nbody_knn_method(const nbody_knn* h) {
+  if (!h) {
+    set_error("nbody_knn is NULL");
+    return -1;
+  }
+  return h->method;
+}
+
+extern "C" int nbody_knn_create_method(nbody_knn** out, int dtype, int dim, uint32_t n, int k, int method, int device) {
   if (int r = hermite_create_check_args(out, dtype, dim, n, "knn")) return r;
   NB_ARG(k >= 1 && k <= kKnnMax, "knn needs 1 <= k <= %d (got %d)", kKnnMax, k);
+  NB_ARG(method == NBODY_KNN_ALL_PAIRS || method == NBODY_KNN_TREE, "knn method must be 0 (all-pairs) or 1 (tree), got %d", method);
   if (int r = hermite_create_check_device(&device, "knn")) return r;
   device_guard guard(device);
   auto* h = new nbody_knn;
@@ -345,9 +418,22 @@ extern "C" int nbody_knn_create_on(nbody_knn** out, int dtype, int dim, uint32_t
   h->K    = k <= 4 ? 4 : k <= 8 ? 8 : 16;
   // nothing is cleared: every compute writes all of it before it reads it
   hipError_t e      = pair_handle_alloc(h, dtype, dim, n, device, knn_plan_for(n));
-  const size_t rows = size_t(h->plan.chunks) * size_t(n) * size_t(h->K);
-  if (e == hipSuccess) e = hipMalloc(&h->part, h->tsz * rows);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->part_j), sizeof(uint32_t) * rows);
+  h->method         = method;
+  if (method == NBODY_KNN_TREE) {  // what the tree path needs, and not the chunks' partial lists
+    h->tree = nntree_shape_for(n);
+    if (e == hipSuccess) e = hipMalloc(&h->sorted, h->tsz * 4 * size_t(h->padded));
+    if (e == hipSuccess) e = hipMalloc(&h->boxes, h->tsz * 8 * 2 * size_t(h->tree.leaves));
+    if (e == hipSuccess) e = hipMalloc(&h->bounds, h->tsz * 8 * size_t(h->tree.bounds_blocks));
+    for (int b = 0; b < 2; ++b) {
+      if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->keys[b]), sizeof(uint64_t) * size_t(n));
+      if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->perm[b]), sizeof(uint32_t) * size_t(n));
+    }
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->hist), sizeof(uint32_t) * radix_sort_scratch_words(n));
+  } else {
+    const size_t rows = size_t(h->plan.chunks) * size_t(n) * size_t(h->K);
+    if (e == hipSuccess) e = hipMalloc(&h->part, h->tsz * rows);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->part_j), sizeof(uint32_t) * rows);
+  }
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->idx), sizeof(uint32_t) * size_t(n) * size_t(k));
   if (e == hipSuccess) e = hipMalloc(&h->d2, h->tsz * size_t(n) * size_t(k));
   if (e == hipSuccess) e = hipMalloc(&h->rho, h->tsz * size_t(n));
@@ -371,6 +457,14 @@ extern "C" void nbody_knn_destroy(nbody_knn* h) {
   (void)hipFree(h->d2);
   (void)hipFree(h->rho);
   (void)hipFree(h->summary);
+  (void)hipFree(h->sorted);
+  (void)hipFree(h->boxes);
+  (void)hipFree(h->bounds);
+  for (int b = 0; b < 2; ++b) {
+    (void)hipFree(h->keys[b]);
+    (void)hipFree(h->perm[b]);
+  }
+  (void)hipFree(h->hist);
   delete h;
 }
 
@@ -386,7 +480,10 @@ extern "C" int nbody_knn_compute(nbody_knn* h, const nbody_state* s, void* strea
     using T         = typename decltype(tg)::type;
     constexpr int D = decltype(tg)::dim;
     device_guard guard(h->device);
-    const int r = h->K == 4 ? knn_launch<T, D, 4>(h, s, st) : h->K == 8 ? knn_launch<T, D, 8>(h, s, st) : knn_launch<T, D, 16>(h, s, st);
+    int r;
+    if (h->method == NBODY_KNN_TREE)
+      r = h->K == 4 ? knn_tree_launch<T, D, 4>(h, s, st) : h->K == 8 ? knn_tree_launch<T, D, 8>(h, s, st) : knn_tree_launch<T, D, 16>(h, s, st);
+    else r = h->K == 4 ? knn_launch<T, D, 4>(h, s, st) : h->K == 8 ? knn_launch<T, D, 8>(h, s, st) : knn_launch<T, D, 16>(h, s, st);
     if (r == NBODY_OK) h->started = true;
     return r;
   });

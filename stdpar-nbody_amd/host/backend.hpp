@@ -156,10 +156,12 @@ class Device {
   }
 
   // --save-density K: the local densities from the K-th neighbour of the current (m, x) into rho, and {x_dc[D], r_c, rho_c} into
-  // summary (nbody_knn_*; the reads are blocking)
-  void density(int k, std::vector<T>& rho, T (&summary)[D + 2]) {
+  // summary (nbody_knn_*; the reads are blocking).  tree (--density-tree): the tree-pruned method, the same bits.
+  void density(int k, bool tree, std::vector<T>& rho, T (&summary)[D + 2]) {
     single("--save-density");
-    if (!knn_) backend_check(nbody_knn_create_on(&knn_, dtype, D, host_.n, k, 0), "nbody_knn_create_on");
+    if (!knn_)
+      backend_check(nbody_knn_create_method(&knn_, dtype, D, host_.n, k, tree ? NBODY_KNN_TREE : NBODY_KNN_ALL_PAIRS, 0),
+                    "nbody_knn_create_method");
     backend_check(nbody_knn_compute(knn_, &view_[0], stream()), "nbody_knn_compute");
     rho.resize(host_.n);
     backend_check(nbody_knn_read(knn_, 2, rho.data(), rho.size() * sizeof(T), stream()), "nbody_knn_read");

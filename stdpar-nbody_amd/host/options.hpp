@@ -67,8 +67,12 @@ struct Options {
   bool save_neighbours = false;
   // not in the reference either (nor in --help): --save-density K (2 .. 16), at every frame the run's Saver records, the local
   // densities from the K-th neighbour, the density centre, the core radius and the core density (nbody_knn_*) are appended to
-  // density.bin; independent of --save and of the algorithm, needs no --softening; one GPU
+  // density.bin; independent of --save and of the algorithm (all-pairs kNN whatever --algorithm is, unless --density-tree), needs no
+  // --softening; one GPU
   int save_density = 0;  // 0: off
+  // not in the reference either (nor in --help): --density-tree, --save-density K uses the tree-pruned exact method
+  // (NBODY_KNN_TREE: the same density.bin byte for byte, for the large runs of the tree codes); needs --save-density
+  bool density_tree = false;
 };
 
 namespace detail {
@@ -210,6 +214,8 @@ inline Options parse_options(std::vector<std::string> const& argv) {
         std::exit(EXIT_FAILURE);
       }
       o.save_density = int(v);
+    } else if (f == "--density-tree") {
+      o.density_tree = true;
     } else if (f == "--print-state") {
       o.print_state = true;
     } else if (f == "--print-info") {
@@ -245,6 +251,10 @@ inline Options parse_options(std::vector<std::string> const& argv) {
   }
   if (o.save_density != 0 && o.gpus_given) {
     std::cerr << "--save-density runs on one GPU: it cannot be combined with --gpus." << std::endl;
+    std::exit(EXIT_FAILURE);
+  }
+  if (o.density_tree && o.save_density == 0) {
+    std::cerr << "--density-tree needs --save-density K." << std::endl;
     std::exit(EXIT_FAILURE);
   }
   if (o.block_levels_given && !(o.block_eta > 0.0)) {

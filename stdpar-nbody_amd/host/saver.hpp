@@ -22,7 +22,7 @@ class Saver {
  public:
   explicit Saver(Options const& o)
    : pos_(o.save_pos), energy_(o.save_energy), tree_energy_(o.tree_energy), quadrupole_(o.quadrupole), softening_(o.softening),
-     neighbours_(o.save_neighbours), density_k_(o.save_density), theta_(o.theta), nbodies_(std::uint32_t(o.size)), nsteps_(std::uint32_t(o.steps)) {
+     neighbours_(o.save_neighbours), density_k_(o.save_density), density_tree_(o.density_tree), theta_(o.theta), nbodies_(std::uint32_t(o.size)), nsteps_(std::uint32_t(o.steps)) {
     std::uint32_t const tsz = sizeof(T), dim = D;
     if (pos_) {
       pos_file_.open("positions.bin", std::ios::out | std::ios::binary);
@@ -75,7 +75,7 @@ class Saver {
     }
     if (density_k_ != 0) {
       T summary[D + 2];  // x_dc, r_c, rho_c
-      dev.density(density_k_, rho_, summary);
+      dev.density(density_k_, density_tree_, rho_, summary);
       density_file_.write(reinterpret_cast<char const*>(rho_.data()), std::streamsize(rho_.size() * sizeof(T)));
       density_file_.write(reinterpret_cast<char const*>(summary), std::streamsize(sizeof summary));
     }
@@ -91,6 +91,7 @@ class Saver {
   double softening_;               // --softening: the energies of the softened dynamics
   bool neighbours_;                // --save-neighbours: phi, nn, nnd2 of every recorded frame, softening_ the potential's length
   int density_k_;                  // --save-density K: rho and the density-centre summary of every recorded frame; 0: off
+  bool density_tree_;              // --density-tree: by the tree-pruned method (the same bytes)
   double theta_;
   std::uint32_t nbodies_, nsteps_;
   std::ofstream pos_file_, energy_file_, neighbours_file_, density_file_;
