@@ -237,8 +237,27 @@ def shard_range(n, rank, world):
     return f.value, f.value + c.value
 
 
-class Comm:
+class _Handle:
+    """An opaque handle of the library: self.h, closed by the symbol the class names in _destroy."""
+
+    _destroy = None
+
+    def close(self):
+        if self.h:
+            getattr(lib(), self._destroy)(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Comm(_Handle):
     """nbody_comm: the RCCL communicator of the per-step all-gather of positions (one process per GPU form)."""
+
+    _destroy = "nbody_comm_destroy"
 
     def __init__(self, world, rank, unique_id, device):
         self.h = C.c_void_p()
@@ -258,17 +277,6 @@ class Comm:
 
     def allgather_positions(self, st, stream=None):
         _check(lib().nbody_allgather_positions(self.h, C.byref(st), C.c_void_p(stream)))
-
-    def close(self):
-        if self.h:
-            lib().nbody_comm_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class HostSystem:
@@ -302,8 +310,10 @@ def build_model(dtype, dim, workload, n):
     return s
 
 
-class Bvh:
+class Bvh(_Handle):
     """bvh<T,N> (src/bvh.h:98-325) on the device."""
+
+    _destroy = "nbody_bvh_destroy"
 
     def __init__(self, dtype, dim, n, device=-1):
         """device: where the tree's buffers live (-1: the calling thread's current device)."""
@@ -311,17 +321,6 @@ class Bvh:
         self.dtype, self.dim, self.n = dtype, dim, n
         _check(lib().nbody_bvh_create_on(C.byref(self.h), dtype, dim, C.c_uint32(n), device))
         self.nnodes = int(lib().nbody_bvh_nnodes(self.h))
-
-    def close(self):
-        if self.h:
-            lib().nbody_bvh_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def bounding_box(self, st, stream=None):
         _check(lib().nbody_bvh_bounding_box(self.h, C.byref(st), C.c_void_p(stream)))
@@ -363,8 +362,10 @@ class Bvh:
         return out
 
 
-class Octree:
+class Octree(_Handle):
     """octree<T,N> (src/octree.h) on the device."""
+
+    _destroy = "nbody_octree_destroy"
 
     def __init__(self, dtype, dim, n, device=-1):
         """device: where the tree's buffers live (-1: the calling thread's current device)."""
@@ -384,17 +385,6 @@ class Octree:
     def set_walk(self, mode):
         """0 auto, 1 the compiler-scheduled walk kernel, 2 the visit round as ISA (bitwise identical results)."""
         _check(lib().nbody_octree_set_walk(self.h, mode))
-
-    def close(self):
-        if self.h:
-            lib().nbody_octree_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def clear(self, stream=None):
         _check(lib().nbody_octree_clear(self.h, C.c_void_p(stream)))
@@ -468,25 +458,16 @@ class Octree:
         return out
 
 
-class Hermite:
+class Hermite(_Handle):
     """Fourth-order Hermite integrator for all-pairs (nbody_hermite_*): owns the jerk, the packed predicted state and the partial sums."""
+
+    _destroy = "nbody_hermite_destroy"
 
     def __init__(self, dtype, dim, n, device=-1):
         """device: where the handle's buffers live (-1: the calling thread's current device)."""
         self.h = C.c_void_p()
         self.dtype, self.dim, self.n = dtype, dim, n
         _check(lib().nbody_hermite_create_on(C.byref(self.h), dtype, dim, C.c_uint32(n), device))
-
-    def close(self):
-        if self.h:
-            lib().nbody_hermite_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def force_jerk(self, st, eps, stream=None):
         """a = st.a and the handle's jerk at (st.x, st.v), Plummer softening eps > 0: starts (or restarts) a run."""
@@ -526,26 +507,17 @@ class Hermite:
         return out
 
 
-class Hermite6:
+class Hermite6(_Handle):
     """Sixth-order Hermite integrator for all-pairs (nbody_hermite6_*): owns the jerk, the snap, the crackle, the packed predicted
     state and the partial sums."""
+
+    _destroy = "nbody_hermite6_destroy"
 
     def __init__(self, dtype, dim, n, device=-1):
         """device: where the handle's buffers live (-1: the calling thread's current device)."""
         self.h = C.c_void_p()
         self.dtype, self.dim, self.n = dtype, dim, n
         _check(lib().nbody_hermite6_create_on(C.byref(self.h), dtype, dim, C.c_uint32(n), device))
-
-    def close(self):
-        if self.h:
-            lib().nbody_hermite6_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def start(self, st, eps, stream=None):
         """a = st.a, the jerk and the snap at (st.x, st.v), crackle = 0, Plummer softening eps > 0: starts (or restarts) a run."""
@@ -588,26 +560,17 @@ class Hermite6:
         return out
 
 
-class Neighbours:
+class Neighbours(_Handle):
     """All-pairs per-body potentials, nearest neighbours and the closest pair (nbody_neighbours_*): owns the packed records, the
     chunks' partial arrays and the results."""
+
+    _destroy = "nbody_neighbours_destroy"
 
     def __init__(self, dtype, dim, n, device=-1):
         """device: where the handle's buffers live (-1: the calling thread's current device)."""
         self.h = C.c_void_p()
         self.dtype, self.dim, self.n = dtype, dim, n
         _check(lib().nbody_neighbours_create_on(C.byref(self.h), dtype, dim, C.c_uint32(n), device))
-
-    def close(self):
-        if self.h:
-            lib().nbody_neighbours_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def compute(self, st, eps, stream=None):
         """phi, nn, nnd2 and the closest pair at (st.m, st.x), Plummer softening eps > 0, into the handle.  Asynchronous, recordable."""
@@ -627,10 +590,12 @@ class Neighbours:
         return i.value, j.value, d2[0]
 
 
-class Knn:
+class Knn(_Handle):
     """k nearest neighbours, local densities and the density centre (nbody_knn_*): owns the packed records, the method's work
     arrays and the results.  k is fixed here, 1 <= k <= 16.  method: "all-pairs" (every pair, O(n^2)) or "tree" (exact, pruned with
     bounding boxes over a space-sorted copy, for large n): the same outputs bit for bit."""
+
+    _destroy = "nbody_knn_destroy"
 
     METHODS = {"all-pairs": 0, "tree": 1}
 
@@ -651,17 +616,6 @@ class Knn:
                 return name
         raise RuntimeError(lib().nbody_last_error().decode())
 
-    def close(self):
-        if self.h:
-            lib().nbody_knn_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def compute(self, st, stream=None):
         """idx, d2, rho and the summary at (st.m, st.x), into the handle.  Asynchronous, recordable."""
         _check(lib().nbody_knn_compute(self.h, C.byref(st), stream))
@@ -681,26 +635,17 @@ class Knn:
         return x, rc[0], rhoc[0]
 
 
-class OctreeBlock:
+class OctreeBlock(_Handle):
     """Block (individual) time steps for the octree leapfrog (nbody_octree_block_*): owns the levels, tau, the active lists, the
     predicted positions and the scratch of the active set's forces; the tree is the caller's Octree."""
+
+    _destroy = "nbody_octree_block_destroy"
 
     def __init__(self, dtype, dim, n, device=-1):
         """device: where the handle's buffers live (-1: the calling thread's current device)."""
         self.h = C.c_void_p()
         self.dtype, self.dim, self.n = dtype, dim, n
         _check(lib().nbody_octree_block_create_on(C.byref(self.h), dtype, dim, C.c_uint32(n), device))
-
-    def close(self):
-        if self.h:
-            lib().nbody_octree_block_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def start(self, tree, st, theta, eps, eta, max_level, stream=None):
         """The softened force of all bodies into st.a and the first levels: st.dt is the largest step, st.dt / 2^max_level the smallest."""
@@ -729,20 +674,19 @@ class OctreeBlock:
         return out
 
 
-class DeviceSystem:
+class DeviceSystem(_Handle):
     """Owning device mirror of a System<T,N>; phase methods mirror the calls of the reference drivers."""
+
+    _destroy = "nbody_destroy"
+    _CACHED = ("_bvh", "_octree", "_hermite", "_octree_block", "_hermite6", "_neighbours")  # one handle each, made on first use
 
     def __init__(self, dtype, dim, n, device=0):
         self.h = C.c_void_p()
         self.dtype, self.dim, self.n, self.device = dtype, dim, n, device
         _check(lib().nbody_create(C.byref(self.h), dtype, dim, C.c_uint32(n), device))
         self.stream = lib().nbody_ctx_stream(self.h)
-        self._bvh = None
-        self._octree = None
-        self._hermite = None
-        self._octree_block = None
-        self._hermite6 = None
-        self._neighbours = None
+        for a in self._CACHED:
+            setattr(self, a, None)
         self._knn = {}
         self._knn_other = {}
 
@@ -753,37 +697,15 @@ class DeviceSystem:
         return d
 
     def close(self):
-        if self._bvh is not None:
-            self._bvh.close()
-            self._bvh = None
-        if self._octree is not None:
-            self._octree.close()
-            self._octree = None
-        if self._hermite is not None:
-            self._hermite.close()
-            self._hermite = None
-        if self._octree_block is not None:
-            self._octree_block.close()
-            self._octree_block = None
-        if self._hermite6 is not None:
-            self._hermite6.close()
-            self._hermite6 = None
-        if self._neighbours is not None:
-            self._neighbours.close()
-            self._neighbours = None
-        for h in list(self._knn.values()) + list(self._knn_other.values()):
-            h.close()
+        cached = [getattr(self, a) for a in self._CACHED] + list(self._knn.values()) + list(self._knn_other.values())
+        for h in cached:
+            if h is not None:
+                h.close()
+        for a in self._CACHED:
+            setattr(self, a, None)
         self._knn = {}
         self._knn_other = {}
-        if self.h:
-            lib().nbody_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()  # the context last
 
     def upload(self, hs):
         for k in ("m", "x", "v", "a", "ao"):
@@ -1109,8 +1031,10 @@ def _load_sharded():
 parallel = _load_sharded()
 
 
-class StepGraph:
+class StepGraph(_Handle):
     """Records the phase calls of one step on the device's stream (HIP stream capture) and replays them."""
+
+    _destroy = "nbody_graph_destroy"
 
     def __init__(self, dev, record):
         self.dev, self.h = dev, C.c_void_p()
@@ -1122,17 +1046,6 @@ class StepGraph:
 
     def launch(self):
         _check(lib().nbody_graph_launch(self.h, C.c_void_p(self.dev.stream)))
-
-    def close(self):
-        if self.h:
-            lib().nbody_graph_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def executed_steps(steps, csv_detailed, warmup=10):

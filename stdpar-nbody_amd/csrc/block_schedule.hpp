@@ -216,27 +216,25 @@ struct block_schedule {
 };
 
 // Nothing is cleared: block_schedule_start and the start kernel of the integrator write lev, tau and the schedule words, and every
-// block step writes the lists before it reads them.  On an error the caller frees.
-inline hipError_t block_schedule_alloc(block_schedule* b, uint32_t n) {
+// block step writes the lists before it reads them.  mem: the owner of the part of the handle the schedule belongs to; on an error the
+// caller releases it or destroys the handle.
+inline hipError_t block_schedule_alloc(block_schedule* b, uint32_t n, device_buffers& mem) {
   b->n      = n;
   b->strips = uint32_t((size_t(n) + kSchedStrip - 1) / kSchedStrip);
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&b->lev), sizeof(int32_t) * size_t(n));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&b->tau), sizeof(uint32_t) * size_t(n));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&b->act), sizeof(uint32_t) * size_t(n));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&b->bcount), sizeof(uint32_t) * b->strips);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&b->sched), sizeof(uint32_t) * kSchedWords);
-  if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&b->pin), sizeof(uint32_t) * 2, hipHostMallocMapped);
+  mem.alloc(&b->lev, sizeof(int32_t) * size_t(n));
+  mem.alloc(&b->tau, sizeof(uint32_t) * size_t(n));
+  mem.alloc(&b->act, sizeof(uint32_t) * size_t(n));
+  mem.alloc(&b->bcount, sizeof(uint32_t) * b->strips);
+  mem.alloc(&b->sched, sizeof(uint32_t) * kSchedWords);
+  mem.alloc_pinned(&b->pin, sizeof(uint32_t) * 2, hipHostMallocMapped);
+  hipError_t e = mem.error();
   if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&b->pin_dev), b->pin, 0);
   return e;
 }
 
-inline void block_schedule_free(block_schedule* b) {
-  (void)hipFree(b->lev);
-  (void)hipFree(b->tau);
-  (void)hipFree(b->act);
-  (void)hipFree(b->bcount);
-  (void)hipFree(b->sched);
-  if (b->pin) (void)hipHostFree(b->pin);
+// mem: the owner block_schedule_alloc was given, with whatever else of that part it holds
+inline void block_schedule_free(block_schedule* b, device_buffers& mem) {
+  mem.release();
   *b = block_schedule{};
 }
 

@@ -69,6 +69,7 @@ struct nbody_bvh {
   unsigned long long rec_id = 0;         // the capture whose recorded build / traversal last wrote the thresholds ...
   double rec_th2            = -1.0;      // ... and the theta^2 it wrote them for (valid inside that capture only)
   bool counters_on = false, have_bbox = false, sorted = false, built = false;
+  nbody::device_buffers mem;  // owns every buffer above, counters (nbody_bvh_enable_counters) included
 };
 
 namespace nbody {
@@ -1405,15 +1406,8 @@ extern "C" int nbody_bvh_create(nbody_bvh** out, int dtype, int dim, uint32_t n)
 }
 
 extern "C" int nbody_bvh_create_on(nbody_bvh** out, int dtype, int dim, uint32_t n, int device) {
-  NB_ARG(out != nullptr, "out is NULL");
-  *out = nullptr;
-  NB_ARG(dtype == NBODY_F32 || dtype == NBODY_F64, "bad dtype %d", dtype);
-  NB_ARG(dim == 2 || dim == 3, "bad dim %d", dim);
-  NB_ARG(n >= 2 && n <= (1u << 30), "bvh needs 2 <= n <= 2^30 (got %u)", n);
-  int ndev = 0;
-  NB_HIP(hipGetDeviceCount(&ndev));
-  if (device < 0) device = current_device();
-  NB_ARG(device >= 0 && device < ndev, "device %d out of range (%d HIP devices visible)", device, ndev);
+  if (int r = create_check_args(out, dtype, dim, n, 2, 1u << 30, "bvh needs 2 <= n <= 2^30 (got %u)")) return r;
+  if (int r = create_check_device(&device, "bvh", false)) return r;
   device_guard guard(device);
   auto* t  = new nbody_bvh;
   t->device = device;
@@ -1436,38 +1430,29 @@ extern "C" int nbody_bvh_create_on(nbody_bvh** out, int dtype, int dim, uint32_t
   // tmp doubles as a radix key buffer (u64[n]) and as the gather scratch (T[n*(4D+1)])
   size_t tmp_bytes = t->tsz * size_t(n) * (4 * D + 1);
   if (tmp_bytes < sizeof(uint64_t) * size_t(n)) tmp_bytes = sizeof(uint64_t) * size_t(n);
-  auto fail = [&](hipError_t e, const char* what) {
-    int r = hip_fail(e, what, __FILE__, __LINE__);
-    nbody_bvh_destroy(t);
-    return r;
-  };
-#define NB_ALLOC(ptr, bytes)                                         \
-  do {                                                               \
-    hipError_t e_ = hipMalloc(reinterpret_cast<void**>(&(ptr)), (bytes)); \
-    if (e_ != hipSuccess) return fail(e_, "hipMalloc(" #ptr ")");    \
-  } while (0)
-  NB_ALLOC(t->bbox, t->tsz * 3 * D);
-  NB_ALLOC(t->partials, t->tsz * 2 * D * t->bbox_blocks);
-  NB_ALLOC(t->keys[0], sizeof(uint64_t) * size_t(n));
-  NB_ALLOC(t->keys[1], sizeof(uint64_t) * size_t(n));
-  NB_ALLOC(t->idx[0], sizeof(uint32_t) * size_t(n));
-  NB_ALLOC(t->idx[1], sizeof(uint32_t) * size_t(n));
-  NB_ALLOC(t->hist, sizeof(uint32_t) * radix_sort_scratch_words(n));
-  NB_ALLOC(t->tmp, tmp_bytes);
+  t->mem.alloc(&t->bbox, t->tsz * 3 * D);
+  t->mem.alloc(&t->partials, t->tsz * 2 * D * t->bbox_blocks);
+  t->mem.alloc(&t->keys[0], sizeof(uint64_t) * size_t(n));
+  t->mem.alloc(&t->keys[1], sizeof(uint64_t) * size_t(n));
+  t->mem.alloc(&t->idx[0], sizeof(uint32_t) * size_t(n));
+  t->mem.alloc(&t->idx[1], sizeof(uint32_t) * size_t(n));
+  t->mem.alloc(&t->hist, sizeof(uint32_t) * radix_sort_scratch_words(n));
+  t->mem.alloc(&t->tmp, tmp_bytes);
   // internal nodes + body slots = level-order indices 0 .. 2 nleafs - 2, one record (one s_load_dwordx16 / x8) each.  No padding
   // is needed for the sweep's speculative requests: a descent asks for 2 i + 1 only when some lane OPENS entry i, and a body
   // record (threshold -1, NaN accepts) is never opened; a skip asks for the sibling i + 1 of a left child (i odd, so i + 1 is the
   // even index on the same level) or for parent + 1 = i / 2 <= i of a right child (the root, i = 0, asks for itself); the jump path
   // converts a live key (covered < sz, level <= nlevels) and leaves first if the key is past the tree.  Every request stays in
   // [0, 2 nleafs - 2] (tests: the sweep at theta = 3 accepting the root, n = 2, 3, powers of two — test_gpu_bvh.py).
-  NB_ALLOC(t->node, t->rec_bytes * (size_t(t->nnodes) + size_t(nleafs)));
-  NB_ALLOC(t->box, t->tsz * 2 * D * size_t(t->nnodes));
-  NB_ALLOC(t->order, sizeof(uint32_t) * (((size_t(n) + 63) / 64 / 8 + 1) * 2 + 8) * 8);  // 8 x (longest range + the largest budget)
-  NB_ALLOC(t->order_n, sizeof(uint32_t) * 8);
-#undef NB_ALLOC
-  if (dtype == NBODY_F32 && (uint64_t(t->nnodes) + nleafs) * t->rec_bytes <= kTreeLdsBytes) {  // bvh_force_lds_kernel asks for more dynamic LDS than a kernel gets unasked
-    hipError_t e = hipSuccess;
-    auto allow   = [&](const void* f) {
+  t->mem.alloc(&t->node, t->rec_bytes * (size_t(t->nnodes) + size_t(nleafs)));
+  t->mem.alloc(&t->box, t->tsz * 2 * D * size_t(t->nnodes));
+  t->mem.alloc(&t->order, sizeof(uint32_t) * (((size_t(n) + 63) / 64 / 8 + 1) * 2 + 8) * 8);  // 8 x (longest range + the largest budget)
+  t->mem.alloc(&t->order_n, sizeof(uint32_t) * 8);
+  hipError_t e     = t->mem.error();
+  const char* what = "nbody_bvh_create allocation";
+  if (e == hipSuccess && dtype == NBODY_F32 && (uint64_t(t->nnodes) + nleafs) * t->rec_bytes <= kTreeLdsBytes) {  // bvh_force_lds_kernel asks for more dynamic LDS than a kernel gets unasked
+    what       = "hipFuncSetAttribute(bvh_force_lds_kernel)";
+    auto allow = [&](const void* f) {
       if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, int(kTreeLdsBytes));
     };
 #define NB_ALLOW(T, DD)                                                                  \
@@ -1476,28 +1461,13 @@ extern "C" int nbody_bvh_create_on(nbody_bvh** out, int dtype, int dim, uint32_t
     if (dim == 2) { NB_ALLOW(float, 2); }
     if (dim == 3) { NB_ALLOW(float, 3); }
 #undef NB_ALLOW
-    if (e != hipSuccess) return fail(e, "hipFuncSetAttribute(bvh_force_lds_kernel)");
   }
-  *out = t;
-  return NBODY_OK;
+  return create_finish(out, t, nbody_bvh_destroy, e, what);
 }
 
 extern "C" void nbody_bvh_destroy(nbody_bvh* t) {
   if (!t) return;
   device_guard guard(t->device);
-  (void)hipFree(t->bbox);
-  (void)hipFree(t->partials);
-  (void)hipFree(t->keys[0]);
-  (void)hipFree(t->keys[1]);
-  (void)hipFree(t->idx[0]);
-  (void)hipFree(t->idx[1]);
-  (void)hipFree(t->hist);
-  (void)hipFree(t->tmp);
-  (void)hipFree(t->node);
-  (void)hipFree(t->box);
-  (void)hipFree(t->counters);
-  (void)hipFree(t->order);
-  (void)hipFree(t->order_n);
   delete t;
 }
 
@@ -1506,7 +1476,7 @@ extern "C" uint32_t nbody_bvh_nnodes(const nbody_bvh* t) { return t ? t->nnodes 
 extern "C" int nbody_bvh_enable_counters(nbody_bvh* t, int on) {
   NB_ARG(t != nullptr, "nbody_bvh is NULL");
   device_guard guard(t->device);
-  if (on && !t->counters) NB_HIP(hipMalloc(reinterpret_cast<void**>(&t->counters), sizeof(uint32_t) * 4 * size_t(t->n)));
+  if (on && !t->counters) NB_HIP(t->mem.alloc_late(&t->counters, sizeof(uint32_t) * 4 * size_t(t->n)));
   t->counters_on = on != 0;
   return NBODY_OK;
 }

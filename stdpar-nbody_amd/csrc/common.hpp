@@ -11,6 +11,7 @@
 #include <cstring>
 
 #include "../../include/nbody_hip.h"
+#include "device_buffers.hpp"
 
 namespace nbody {
 
@@ -77,6 +78,52 @@ inline int stream_device(hipStream_t st) {
 inline int check_same_device(int handle_device, hipStream_t st, const char* what) {
   const int sd = stream_device(st);
   NB_ARG(handle_device == sd, "%s was created on device %d but the call's stream belongs to device %d", what, handle_device, sd);
+  return NBODY_OK;
+}
+
+// ---- handles: create and destroy -------------------------------------------------------------------------------------------------
+// Every nbody_*_create: create_check_args, the call's own argument checks if it has any (kNN's k and method), create_check_device,
+// device_guard, `new`, the allocations through the handle's device_buffers, create_finish.  Every nbody_*_destroy: NULL check,
+// device_guard, what is not memory, `delete` — the owner frees.
+// The arguments every handle takes, in the header's order.  n_text: the whole message for n outside [n_min, n_max]; it may print n
+// with one %u.
+template <typename H>
+inline int create_check_args(H** out, int dtype, int dim, uint32_t n, uint32_t n_min, uint32_t n_max, const char* n_text) {
+  NB_ARG(out != nullptr, "out is NULL");
+  *out = nullptr;
+  NB_ARG(dtype == NBODY_F32 || dtype == NBODY_F64, "bad dtype %d", dtype);
+  NB_ARG(dim == 2 || dim == 3, "bad dim %d", dim);
+  NB_ARG(n >= n_min && n <= n_max, n_text, n);
+  return NBODY_OK;
+}
+
+// After all argument checks: that no capture is open on this thread, then the device; resolves *device (-1: the current one, unless
+// !default_to_current: nbody_create takes no -1).
+// refuse_in_capture is false for nbody_create, nbody_bvh_create_on and nbody_octree_create_on: they allocate like the others but
+// have never refused between nbody_graph_begin and nbody_graph_end, and that is kept as it is here, not judged right.
+inline int create_check_device(int* device, const char* api, bool refuse_in_capture, bool default_to_current = true) {
+  if (refuse_in_capture && captures_on_this_thread() != 0) {
+    set_error("nbody_%s_create allocates: it cannot be called between nbody_graph_begin and nbody_graph_end", api);
+    return NBODY_ERR_STATE;
+  }
+  int ndev = 0;
+  NB_HIP(hipGetDeviceCount(&ndev));
+  if (*device < 0 && default_to_current) *device = current_device();
+  NB_ARG(*device >= 0 && *device < ndev, "device %d out of range (%d HIP devices visible)", *device, ndev);
+  return NBODY_OK;
+}
+
+// The end of a create call.  e: the handle's device_buffers::error(), or the error of another runtime call, named by `what`.  On an
+// error the half-made handle is destroyed and *out stays NULL.
+template <typename H>
+inline int create_finish(H** out, H* h, void (*destroy)(H*), hipError_t e, const char* what, const char* file = __builtin_FILE(),
+                         int line = __builtin_LINE()) {
+  if (e != hipSuccess) {
+    const int r = hip_fail(e, what, file, line);
+    destroy(h);
+    return r;
+  }
+  *out = h;
   return NBODY_OK;
 }
 

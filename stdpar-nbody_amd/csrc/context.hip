@@ -39,6 +39,7 @@ struct nbody_ctx {
   hipStream_t stream = nullptr;
   uint32_t first = 0, count = 0;  // owned targets (nbody_ctx_set_shard); whole system by default
   uint32_t tuning = 0;            // K1 launch shape of this context (nbody_ctx_configure_all_pairs)
+  device_buffers mem;             // owns m, x, v, a, ao
 };
 
 extern "C" int nbody_abi_version(void) { return NBODY_HIP_ABI_VERSION; }
@@ -60,14 +61,8 @@ extern "C" int nbody_device_info(int device, char* arch_out, size_t arch_len, in
 }
 
 extern "C" int nbody_create(nbody_ctx** out, int dtype, int dim, uint32_t n, int device) {
-  NB_ARG(out != nullptr, "out is NULL");
-  *out = nullptr;
-  NB_ARG(dtype == NBODY_F32 || dtype == NBODY_F64, "bad dtype %d", dtype);
-  NB_ARG(dim == 2 || dim == 3, "bad dim %d", dim);
-  NB_ARG(n >= 1, "n must be >= 1");
-  int ndev = 0;
-  NB_HIP(hipGetDeviceCount(&ndev));
-  NB_ARG(device >= 0 && device < ndev, "device %d out of range (%d HIP devices visible)", device, ndev);
+  if (int r = create_check_args(out, dtype, dim, n, 1, UINT32_MAX, "n must be >= 1")) return r;
+  if (int r = create_check_device(&device, "", false, false)) return r;
   device_guard guard(device);
   auto* c   = new nbody_ctx;
   c->dtype  = dtype;
@@ -78,34 +73,29 @@ extern "C" int nbody_create(nbody_ctx** out, int dtype, int dim, uint32_t n, int
   c->tsz    = dtype == NBODY_F32 ? 4 : 8;
   const size_t vb = c->tsz * size_t(n) * size_t(dim);
   hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipMalloc(&c->m, c->tsz * size_t(n));
-  if (e == hipSuccess) e = hipMalloc(&c->x, vb);
-  if (e == hipSuccess) e = hipMalloc(&c->v, vb);
-  if (e == hipSuccess) e = hipMalloc(&c->a, vb);
-  if (e == hipSuccess) e = hipMalloc(&c->ao, vb);
-  if (e != hipSuccess) {
-    int r = hip_fail(e, "nbody_create allocation", __FILE__, __LINE__);
-    nbody_destroy(c);
-    return r;
+  if (e == hipSuccess) {
+    c->mem.alloc(&c->m, c->tsz * size_t(n));
+    c->mem.alloc(&c->x, vb);
+    c->mem.alloc(&c->v, vb);
+    c->mem.alloc(&c->a, vb);
+    c->mem.alloc(&c->ao, vb);
+    e = c->mem.error();
   }
-  nbody_state view;
-  (void)nbody_ctx_state(c, &view);
-  if (int r = ap_scratch_reserve(c->stream, &view)) {  // so that a recorded step never allocates
-    nbody_destroy(c);
-    return r;
+  if (e == hipSuccess) {
+    nbody_state view;
+    (void)nbody_ctx_state(c, &view);
+    if (int r = ap_scratch_reserve(c->stream, &view)) {  // so that a recorded step never allocates
+      nbody_destroy(c);
+      return r;
+    }
   }
-  *out = c;
-  return NBODY_OK;
+  return create_finish(out, c, nbody_destroy, e, "nbody_create allocation");
 }
 
 extern "C" void nbody_destroy(nbody_ctx* c) {
   if (!c) return;
   device_guard guard(c->device);
-  (void)hipFree(c->m);
-  (void)hipFree(c->x);
-  (void)hipFree(c->v);
-  (void)hipFree(c->a);
-  (void)hipFree(c->ao);
+  c->mem.release();  // before the stream goes, as ever
   if (c->stream) ap_scratch_release(c->stream);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;

@@ -148,28 +148,19 @@ extern "C" int nbody_hermite_create(nbody_hermite** out, int dtype, int dim, uin
 }
 
 extern "C" int nbody_hermite_create_on(nbody_hermite** out, int dtype, int dim, uint32_t n, int device) {
-  if (int r = hermite_create_check(out, dtype, dim, n, &device, "hermite")) return r;
+  if (int r = create_check_args(out, dtype, dim, n, 1, 1u << 28, "hermite needs 1 <= n <= 2^28 (got %u)")) return r;
+  if (int r = create_check_device(&device, "hermite", true)) return r;
   device_guard guard(device);
-  auto* h      = new nbody_hermite;
-  hipError_t e = hermite_handle_alloc(h, dtype, dim, n, device, 2, 1);
+  auto* h = new nbody_hermite;
+  hermite_handle_alloc(h, dtype, dim, n, device, 2, 1);
   // not cleared either: the jerk is written by nbody_hermite_force_jerk before nbody_hermite_step or nbody_hermite_read may run
-  if (e == hipSuccess) e = hipMalloc(&h->jerk, h->tsz * size_t(dim) * size_t(n));
-  if (e != hipSuccess) {
-    int r = hip_fail(e, "nbody_hermite_create allocation", __FILE__, __LINE__);
-    nbody_hermite_destroy(h);
-    return r;
-  }
-  *out = h;
-  return NBODY_OK;
+  h->mem.alloc(&h->jerk, h->tsz * size_t(dim) * size_t(n));
+  return create_finish(out, h, nbody_hermite_destroy, h->mem.error(), "nbody_hermite_create allocation");
 }
 
 extern "C" void nbody_hermite_destroy(nbody_hermite* h) {
   if (!h) return;
   device_guard guard(h->device);
-  (void)hipFree(h->recs);
-  (void)hipFree(h->part);
-  (void)hipFree(h->jerk);
-  hermite_block_free(&h->blk);
   delete h;
 }
 

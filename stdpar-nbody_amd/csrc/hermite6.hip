@@ -182,34 +182,23 @@ extern "C" int nbody_hermite6_create(nbody_hermite6** out, int dtype, int dim, u
 }
 
 extern "C" int nbody_hermite6_create_on(nbody_hermite6** out, int dtype, int dim, uint32_t n, int device) {
-  if (int r = hermite_create_check(out, dtype, dim, n, &device, "hermite6")) return r;
+  if (int r = create_check_args(out, dtype, dim, n, 1, 1u << 28, "hermite6 needs 1 <= n <= 2^28 (got %u)")) return r;
+  if (int r = create_check_device(&device, "hermite6", true)) return r;
   device_guard guard(device);
-  auto* h          = new nbody_hermite6;
-  hipError_t e     = hermite_handle_alloc(h, dtype, dim, n, device, 3, 2);
+  auto* h = new nbody_hermite6;
+  hermite_handle_alloc(h, dtype, dim, n, device, 3, 2);
   const size_t row = h->tsz * size_t(dim) * size_t(n);
   // not cleared either: the jerk, the snap and the crackle are written by nbody_hermite6_start before nbody_hermite6_step or
   // nbody_hermite6_read may run
-  if (e == hipSuccess) e = hipMalloc(&h->jerk, row);
-  if (e == hipSuccess) e = hipMalloc(&h->snap, row);
-  if (e == hipSuccess) e = hipMalloc(&h->crackle, row);
-  if (e != hipSuccess) {
-    int r = hip_fail(e, "nbody_hermite6_create allocation", __FILE__, __LINE__);
-    nbody_hermite6_destroy(h);
-    return r;
-  }
-  *out = h;
-  return NBODY_OK;
+  h->mem.alloc(&h->jerk, row);
+  h->mem.alloc(&h->snap, row);
+  h->mem.alloc(&h->crackle, row);
+  return create_finish(out, h, nbody_hermite6_destroy, h->mem.error(), "nbody_hermite6_create allocation");
 }
 
 extern "C" void nbody_hermite6_destroy(nbody_hermite6* h) {
   if (!h) return;
   device_guard guard(h->device);
-  (void)hipFree(h->recs);
-  (void)hipFree(h->part);
-  (void)hipFree(h->jerk);
-  (void)hipFree(h->snap);
-  (void)hipFree(h->crackle);
-  hermite_block_free(&h->blk);
   delete h;
 }
 

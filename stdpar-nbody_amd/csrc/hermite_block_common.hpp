@@ -57,20 +57,20 @@ struct hermite_block {
   void* bpart     = nullptr;  // T[bslots][G D]: partial sums of the active set, sized for the worst n_act
   uint64_t bslots = 0;
   bool block_on   = false;  // the block start has run and no fixed-step start since
+  device_buffers mem;       // owns bpart and the schedule's arrays: a part of its own, apart from the handle's
 };
 
 inline void hermite_block_free(hermite_block* b) {
-  block_schedule_free(&b->sched);
-  (void)hipFree(b->bpart);
+  block_schedule_free(&b->sched, b->mem);
   b->bpart = nullptr;
 }
 
 // what: "nbody_hermite_block_start allocation" or its sixth-order twin, for the error
 inline int hermite_block_alloc(hermite_block* b, const hermite_handle* h, int G, uint32_t min_chunks, const char* what) {
   if (b->sched.pin) return NBODY_OK;
-  b->bslots    = hermite_block_part_slots(h->n, min_chunks);
-  hipError_t e = hipMalloc(&b->bpart, h->tsz * G * size_t(h->dim) * size_t(b->bslots));
-  if (e == hipSuccess) e = block_schedule_alloc(&b->sched, h->n);
+  b->bslots = hermite_block_part_slots(h->n, min_chunks);
+  b->mem.alloc(&b->bpart, h->tsz * G * size_t(h->dim) * size_t(b->bslots));
+  const hipError_t e = block_schedule_alloc(&b->sched, h->n, b->mem);
   if (e != hipSuccess) {
     hermite_block_free(b);
     return hip_fail(e, what, __FILE__, __LINE__);

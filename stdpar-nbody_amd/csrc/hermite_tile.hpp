@@ -340,38 +340,8 @@ struct hermite_handle {
   void* recs   = nullptr;  // hermite_rec<T, G>[padded]
   void* part   = nullptr;  // T[chunks][G D][n]
   bool started = false;    // the start call has run (host call order, which a recorded step replays)
+  device_buffers mem;      // owns recs, part and what the handle's own struct adds
 };
-
-// The checks of nbody_<api>_create_on in the header's order, in two halves for a create call with arguments of its own to check in
-// between (kNN's k): the arguments every handle takes ...
-template <typename H>
-inline int hermite_create_check_args(H** out, int dtype, int dim, uint32_t n, const char* api) {
-  NB_ARG(out != nullptr, "out is NULL");
-  *out = nullptr;
-  NB_ARG(dtype == NBODY_F32 || dtype == NBODY_F64, "bad dtype %d", dtype);
-  NB_ARG(dim == 2 || dim == 3, "bad dim %d", dim);
-  NB_ARG(n >= 1 && n <= (1u << 28), "%s needs 1 <= n <= 2^28 (got %u)", api, n);
-  return NBODY_OK;
-}
-
-// ... and, after all argument checks, that no capture is open on this thread, then the device; resolves *device (-1: the current one).
-inline int hermite_create_check_device(int* device, const char* api) {
-  if (captures_on_this_thread() != 0) {
-    set_error("nbody_%s_create allocates: it cannot be called between nbody_graph_begin and nbody_graph_end", api);
-    return NBODY_ERR_STATE;
-  }
-  int ndev = 0;
-  NB_HIP(hipGetDeviceCount(&ndev));
-  if (*device < 0) *device = current_device();
-  NB_ARG(*device >= 0 && *device < ndev, "device %d out of range (%d HIP devices visible)", *device, ndev);
-  return NBODY_OK;
-}
-
-template <typename H>
-inline int hermite_create_check(H** out, int dtype, int dim, uint32_t n, int* device, const char* api) {
-  if (int r = hermite_create_check_args(out, dtype, dim, n, api)) return r;
-  return hermite_create_check_device(device, api);
-}
 
 // The shared fields of a new handle.
 inline void hermite_handle_fill(hermite_handle* h, int dtype, int dim, uint32_t n, int device, const hermite_plan& plan) {
@@ -387,11 +357,10 @@ inline void hermite_handle_fill(hermite_handle* h, int dtype, int dim, uint32_t 
 // Fills the shared fields of a new handle and allocates its records and partial sums (the caller has made `device` current).
 // Nothing is cleared: every launch sequence writes all of recs and part before it reads them.  (A memset here would be ordered
 // against the NULL stream only, not against the non-blocking stream of a context, and could land after the first predict.)
-inline hipError_t hermite_handle_alloc(hermite_handle* h, int dtype, int dim, uint32_t n, int device, int G, uint32_t min_chunks) {
+inline void hermite_handle_alloc(hermite_handle* h, int dtype, int dim, uint32_t n, int device, int G, uint32_t min_chunks) {
   hermite_handle_fill(h, dtype, dim, n, device, hermite_plan_for(n, min_chunks));
-  hipError_t e = hipMalloc(&h->recs, h->tsz * 4 * G * size_t(h->padded));
-  if (e == hipSuccess) e = hipMalloc(&h->part, h->tsz * size_t(h->plan.chunks) * G * size_t(dim) * size_t(n));
-  return e;
+  h->mem.alloc(&h->recs, h->tsz * 4 * G * size_t(h->padded));
+  h->mem.alloc(&h->part, h->tsz * size_t(h->plan.chunks) * G * size_t(dim) * size_t(n));
 }
 
 // The common head of a start or step call, before the dispatch on (dtype, dim): the state (all_arrays: check_state's), then the whole

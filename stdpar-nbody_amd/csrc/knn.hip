@@ -408,63 +408,42 @@ extern "C" int nbody_knn_method(const nbody_knn* h) {
 }
 
 extern "C" int nbody_knn_create_method(nbody_knn** out, int dtype, int dim, uint32_t n, int k, int method, int device) {
-  if (int r = hermite_create_check_args(out, dtype, dim, n, "knn")) return r;
+  if (int r = create_check_args(out, dtype, dim, n, 1, 1u << 28, "knn needs 1 <= n <= 2^28 (got %u)")) return r;
   NB_ARG(k >= 1 && k <= kKnnMax, "knn needs 1 <= k <= %d (got %d)", kKnnMax, k);
   NB_ARG(method == NBODY_KNN_ALL_PAIRS || method == NBODY_KNN_TREE, "knn method must be 0 (all-pairs) or 1 (tree), got %d", method);
-  if (int r = hermite_create_check_device(&device, "knn")) return r;
+  if (int r = create_check_device(&device, "knn", true)) return r;
   device_guard guard(device);
   auto* h = new nbody_knn;
   h->k    = k;
   h->K    = k <= 4 ? 4 : k <= 8 ? 8 : 16;
   // nothing is cleared: every compute writes all of it before it reads it
-  hipError_t e      = pair_handle_alloc(h, dtype, dim, n, device, knn_plan_for(n));
-  h->method         = method;
+  pair_handle_alloc(h, dtype, dim, n, device, knn_plan_for(n));
+  h->method = method;
   if (method == NBODY_KNN_TREE) {  // what the tree path needs, and not the chunks' partial lists
     h->tree = nntree_shape_for(n);
-    if (e == hipSuccess) e = hipMalloc(&h->sorted, h->tsz * 4 * size_t(h->padded));
-    if (e == hipSuccess) e = hipMalloc(&h->boxes, h->tsz * 8 * 2 * size_t(h->tree.leaves));
-    if (e == hipSuccess) e = hipMalloc(&h->bounds, h->tsz * 8 * size_t(h->tree.bounds_blocks));
+    h->mem.alloc(&h->sorted, h->tsz * 4 * size_t(h->padded));
+    h->mem.alloc(&h->boxes, h->tsz * 8 * 2 * size_t(h->tree.leaves));
+    h->mem.alloc(&h->bounds, h->tsz * 8 * size_t(h->tree.bounds_blocks));
     for (int b = 0; b < 2; ++b) {
-      if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->keys[b]), sizeof(uint64_t) * size_t(n));
-      if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->perm[b]), sizeof(uint32_t) * size_t(n));
+      h->mem.alloc(&h->keys[b], sizeof(uint64_t) * size_t(n));
+      h->mem.alloc(&h->perm[b], sizeof(uint32_t) * size_t(n));
     }
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->hist), sizeof(uint32_t) * radix_sort_scratch_words(n));
+    h->mem.alloc(&h->hist, sizeof(uint32_t) * radix_sort_scratch_words(n));
   } else {
     const size_t rows = size_t(h->plan.chunks) * size_t(n) * size_t(h->K);
-    if (e == hipSuccess) e = hipMalloc(&h->part, h->tsz * rows);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->part_j), sizeof(uint32_t) * rows);
+    h->mem.alloc(&h->part, h->tsz * rows);
+    h->mem.alloc(&h->part_j, sizeof(uint32_t) * rows);
   }
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->idx), sizeof(uint32_t) * size_t(n) * size_t(k));
-  if (e == hipSuccess) e = hipMalloc(&h->d2, h->tsz * size_t(n) * size_t(k));
-  if (e == hipSuccess) e = hipMalloc(&h->rho, h->tsz * size_t(n));
-  if (e == hipSuccess) e = hipMalloc(&h->summary, h->tsz * kKnnSummaryLen);
-  if (e != hipSuccess) {
-    int r = hip_fail(e, "nbody_knn_create allocation", __FILE__, __LINE__);
-    nbody_knn_destroy(h);
-    return r;
-  }
-  *out = h;
-  return NBODY_OK;
+  h->mem.alloc(&h->idx, sizeof(uint32_t) * size_t(n) * size_t(k));
+  h->mem.alloc(&h->d2, h->tsz * size_t(n) * size_t(k));
+  h->mem.alloc(&h->rho, h->tsz * size_t(n));
+  h->mem.alloc(&h->summary, h->tsz * kKnnSummaryLen);
+  return create_finish(out, h, nbody_knn_destroy, h->mem.error(), "nbody_knn_create allocation");
 }
 
 extern "C" void nbody_knn_destroy(nbody_knn* h) {
   if (!h) return;
   device_guard guard(h->device);
-  (void)hipFree(h->recs);
-  (void)hipFree(h->part);
-  (void)hipFree(h->part_j);
-  (void)hipFree(h->idx);
-  (void)hipFree(h->d2);
-  (void)hipFree(h->rho);
-  (void)hipFree(h->summary);
-  (void)hipFree(h->sorted);
-  (void)hipFree(h->boxes);
-  (void)hipFree(h->bounds);
-  for (int b = 0; b < 2; ++b) {
-    (void)hipFree(h->keys[b]);
-    (void)hipFree(h->perm[b]);
-  }
-  (void)hipFree(h->hist);
   delete h;
 }
 

@@ -331,39 +331,26 @@ extern "C" int nbody_neighbours_create(nbody_neighbours** out, int dtype, int di
 }
 
 extern "C" int nbody_neighbours_create_on(nbody_neighbours** out, int dtype, int dim, uint32_t n, int device) {
-  if (int r = hermite_create_check(out, dtype, dim, n, &device, "neighbours")) return r;
+  if (int r = create_check_args(out, dtype, dim, n, 1, 1u << 28, "neighbours needs 1 <= n <= 2^28 (got %u)")) return r;
+  if (int r = create_check_device(&device, "neighbours", true)) return r;
   device_guard guard(device);
   auto* h = new nbody_neighbours;
   // nothing is cleared: every compute writes all of it before it reads it
-  hipError_t e      = pair_handle_alloc(h, dtype, dim, n, device, hermite_plan_for(n, 2));
+  pair_handle_alloc(h, dtype, dim, n, device, hermite_plan_for(n, 2));
   const size_t rows = size_t(h->plan.chunks) * size_t(n);
-  if (e == hipSuccess) e = hipMalloc(&h->part, h->tsz * rows);
-  if (e == hipSuccess) e = hipMalloc(&h->part_d, h->tsz * rows);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->part_j), sizeof(uint32_t) * rows);
-  if (e == hipSuccess) e = hipMalloc(&h->phi, h->tsz * size_t(n));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->nn), sizeof(uint32_t) * size_t(n));
-  if (e == hipSuccess) e = hipMalloc(&h->nnd2, h->tsz * size_t(n));
-  if (e == hipSuccess) e = hipMalloc(&h->closest, 16);
-  if (e != hipSuccess) {
-    int r = hip_fail(e, "nbody_neighbours_create allocation", __FILE__, __LINE__);
-    nbody_neighbours_destroy(h);
-    return r;
-  }
-  *out = h;
-  return NBODY_OK;
+  h->mem.alloc(&h->part, h->tsz * rows);
+  h->mem.alloc(&h->part_d, h->tsz * rows);
+  h->mem.alloc(&h->part_j, sizeof(uint32_t) * rows);
+  h->mem.alloc(&h->phi, h->tsz * size_t(n));
+  h->mem.alloc(&h->nn, sizeof(uint32_t) * size_t(n));
+  h->mem.alloc(&h->nnd2, h->tsz * size_t(n));
+  h->mem.alloc(&h->closest, 16);
+  return create_finish(out, h, nbody_neighbours_destroy, h->mem.error(), "nbody_neighbours_create allocation");
 }
 
 extern "C" void nbody_neighbours_destroy(nbody_neighbours* h) {
   if (!h) return;
   device_guard guard(h->device);
-  (void)hipFree(h->recs);
-  (void)hipFree(h->part);
-  (void)hipFree(h->part_d);
-  (void)hipFree(h->part_j);
-  (void)hipFree(h->phi);
-  (void)hipFree(h->nn);
-  (void)hipFree(h->nnd2);
-  (void)hipFree(h->closest);
   delete h;
 }
 

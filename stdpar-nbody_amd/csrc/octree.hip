@@ -2806,6 +2806,7 @@ struct nbody_octree {
   int sorted_buf   = 0;
   bool counters_on = false, have_bounds = false, inserted = false, have_tree = false;
   bool have_quad = false;  // nbody_octree_compute_quadrupoles ran after the latest clear / insert / compute_tree / set_build
+  nbody::device_buffers mem;  // owns every buffer above, counters and quad (allocated after create) included
 };
 
 using namespace nbody;
@@ -3169,15 +3170,8 @@ extern "C" int nbody_octree_set_step_budget(nbody_octree* t, uint32_t steps) {
 }
 
 extern "C" int nbody_octree_create_on(nbody_octree** out, int dtype, int dim, uint32_t n, int device) {
-  NB_ARG(out != nullptr, "out is NULL");
-  *out = nullptr;
-  NB_ARG(dtype == NBODY_F32 || dtype == NBODY_F64, "bad dtype %d", dtype);
-  NB_ARG(dim == 2 || dim == 3, "bad dim %d", dim);
-  NB_ARG(n >= 1 && n <= (1u << 28), "octree needs 1 <= n <= 2^28 (got %u)", n);
-  int ndev = 0;
-  NB_HIP(hipGetDeviceCount(&ndev));
-  if (device < 0) device = current_device();
-  NB_ARG(device >= 0 && device < ndev, "device %d out of range (%d HIP devices visible)", device, ndev);
+  if (int r = create_check_args(out, dtype, dim, n, 1, 1u << 28, "octree needs 1 <= n <= 2^28 (got %u)")) return r;
+  if (int r = create_check_device(&device, "octree", false)) return r;
   device_guard guard(device);
   auto* t  = new nbody_octree;
   t->device = device;
@@ -3192,82 +3186,53 @@ extern "C" int nbody_octree_create_on(nbody_octree** out, int dtype, int dim, ui
   t->bounds_blocks   = uint32_t((uint64_t(n) * dim + kOB * 8 - 1) / (kOB * 8));
   if (t->bounds_blocks > 1024) t->bounds_blocks = 1024;
   const int maxl = dim == 3 ? kMaxLevels<3> : kMaxLevels<2>;
-  auto fail = [&](hipError_t e, const char* what) {
-    int r = hip_fail(e, what, __FILE__, __LINE__);
-    nbody_octree_destroy(t);
-    return r;
-  };
-#define NB_ALLOC(ptr, bytes)                                              \
-  do {                                                                    \
-    hipError_t e_ = hipMalloc(reinterpret_cast<void**>(&(ptr)), (bytes)); \
-    if (e_ != hipSuccess) return fail(e_, "hipMalloc(" #ptr ")");         \
-  } while (0)
-  NB_ALLOC(t->root, t->tsz * (dim + 1));
-  NB_ALLOC(t->partials, t->tsz * 2 * t->bounds_blocks);
-  NB_ALLOC(t->keys[0], sizeof(uint64_t) * size_t(n));
-  NB_ALLOC(t->keys[1], sizeof(uint64_t) * size_t(n));
-  NB_ALLOC(t->idx[0], sizeof(uint32_t) * size_t(n));
-  NB_ALLOC(t->idx[1], sizeof(uint32_t) * size_t(n));
-  NB_ALLOC(t->hist, sizeof(uint32_t) * radix_sort_scratch_words(n));
-  NB_ALLOC(t->rootrec, 64);
+  t->mem.alloc(&t->root, t->tsz * (dim + 1));
+  t->mem.alloc(&t->partials, t->tsz * 2 * t->bounds_blocks);
+  t->mem.alloc(&t->keys[0], sizeof(uint64_t) * size_t(n));
+  t->mem.alloc(&t->keys[1], sizeof(uint64_t) * size_t(n));
+  t->mem.alloc(&t->idx[0], sizeof(uint32_t) * size_t(n));
+  t->mem.alloc(&t->idx[1], sizeof(uint32_t) * size_t(n));
+  t->mem.alloc(&t->hist, sizeof(uint32_t) * radix_sort_scratch_words(n));
+  t->mem.alloc(&t->rootrec, 64);
   t->group_bytes = dtype == NBODY_F32 ? (dim == 3 ? sizeof(ot_group<float, 3>) : sizeof(ot_group<float, 2>))
                                       : (dim == 3 ? sizeof(ot_group<double, 3>) : sizeof(ot_group<double, 2>));
-  NB_ALLOC(t->groups, t->group_bytes * size_t(t->max_cells));
-  NB_ALLOC(t->cells, sizeof(ot_cell) * size_t(t->max_cells));
-  NB_ALLOC(t->lvl_count, sizeof(uint32_t) * size_t(maxl + 8));  // level counts, deep groups, flags, two grid-barrier counters, ...
+  t->mem.alloc(&t->groups, t->group_bytes * size_t(t->max_cells));
+  t->mem.alloc(&t->cells, sizeof(ot_cell) * size_t(t->max_cells));
+  t->mem.alloc(&t->lvl_count, sizeof(uint32_t) * size_t(maxl + 8));  // level counts, deep groups, flags, two grid-barrier counters, ...
   {
     const size_t nblk = size_t(n) / kLcpB + 1;
-    NB_ALLOC(t->tops, sizeof(ot_cell) * (size_t(n) / 2 + 2));
-    NB_ALLOC(t->lcp, size_t(n) + 2);
-    NB_ALLOC(t->plocal, sizeof(uint32_t) * (size_t(n) + 1));
-    NB_ALLOC(t->bsum, sizeof(uint32_t) * nblk);
-    NB_ALLOC(t->bhist, sizeof(uint32_t) * nblk * size_t(maxl + 1));
-    NB_ALLOC(t->rankpos, sizeof(uint32_t) * size_t(t->max_cells));
-    NB_ALLOC(t->later, sizeof(uint32_t) * (size_t(t->max_cells) / kMpChunk + 2) * size_t(maxl));
-    NB_ALLOC(t->later_mask, sizeof(uint32_t) * (size_t(t->max_cells) / kMpChunk + 2));
+    t->mem.alloc(&t->tops, sizeof(ot_cell) * (size_t(n) / 2 + 2));
+    t->mem.alloc(&t->lcp, size_t(n) + 2);
+    t->mem.alloc(&t->plocal, sizeof(uint32_t) * (size_t(n) + 1));
+    t->mem.alloc(&t->bsum, sizeof(uint32_t) * nblk);
+    t->mem.alloc(&t->bhist, sizeof(uint32_t) * nblk * size_t(maxl + 1));
+    t->mem.alloc(&t->rankpos, sizeof(uint32_t) * size_t(t->max_cells));
+    t->mem.alloc(&t->later, sizeof(uint32_t) * (size_t(t->max_cells) / kMpChunk + 2) * size_t(maxl));
+    t->mem.alloc(&t->later_mask, sizeof(uint32_t) * (size_t(t->max_cells) / kMpChunk + 2));
     {
       const size_t blocks2 = ((size_t(t->max_cells) / kMpChunk + 2) * size_t(maxl) + kMpCrown - 1) / kMpCrown + 1;
-      NB_ALLOC(t->later2, sizeof(uint32_t) * blocks2 * size_t(maxl));
-      NB_ALLOC(t->later2_mask, sizeof(uint32_t) * blocks2);
+      t->mem.alloc(&t->later2, sizeof(uint32_t) * blocks2 * size_t(maxl));
+      t->mem.alloc(&t->later2_mask, sizeof(uint32_t) * blocks2);
     }
   }
-#undef NB_ALLOC
-  if (hipError_t e = hipMemset(t->lvl_count, 0, sizeof(uint32_t) * size_t(maxl + 8)); e != hipSuccess) return fail(e, "hipMemset");
-  {
-    hipDeviceProp_t prop;
-    if (hipError_t e = hipGetDeviceProperties(&prop, device); e != hipSuccess) return fail(e, "hipGetDeviceProperties");
-    t->ncu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 1;
+  hipError_t e     = t->mem.error();
+  const char* what = "nbody_octree_create allocation";
+  if (e == hipSuccess) {
+    what = "hipMemset";
+    e    = hipMemset(t->lvl_count, 0, sizeof(uint32_t) * size_t(maxl + 8));
   }
-  *out = t;
-  return NBODY_OK;
+  if (e == hipSuccess) {
+    what = "hipGetDeviceProperties";
+    hipDeviceProp_t prop;
+    e      = hipGetDeviceProperties(&prop, device);
+    t->ncu = e == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 1;
+  }
+  return create_finish(out, t, nbody_octree_destroy, e, what);
 }
 
 extern "C" void nbody_octree_destroy(nbody_octree* t) {
   if (!t) return;
   device_guard guard(t->device);
-  (void)hipFree(t->root);
-  (void)hipFree(t->partials);
-  (void)hipFree(t->keys[0]);
-  (void)hipFree(t->keys[1]);
-  (void)hipFree(t->idx[0]);
-  (void)hipFree(t->idx[1]);
-  (void)hipFree(t->hist);
-  (void)hipFree(t->rootrec);
-  (void)hipFree(t->groups);
-  (void)hipFree(t->cells);
-  (void)hipFree(t->tops);
-  (void)hipFree(t->lcp);
-  (void)hipFree(t->plocal);
-  (void)hipFree(t->bsum);
-  (void)hipFree(t->bhist);
-  (void)hipFree(t->rankpos);
-  (void)hipFree(t->later);
-  (void)hipFree(t->later_mask);
-  (void)hipFree(t->later2);
-  (void)hipFree(t->later2_mask);
-  (void)hipFree(t->lvl_count);
-  (void)hipFree(t->counters);
-  (void)hipFree(t->quad);
   delete t;
 }
 
@@ -3365,7 +3330,7 @@ extern "C" int nbody_octree_compute_softened_force(nbody_octree* t, const nbody_
 extern "C" int nbody_octree_enable_counters(nbody_octree* t, int on) {
   NB_ARG(t != nullptr, "nbody_octree is NULL");
   device_guard guard(t->device);
-  if (on && !t->counters) NB_HIP(hipMalloc(reinterpret_cast<void**>(&t->counters), sizeof(uint32_t) * 2 * size_t(t->n)));
+  if (on && !t->counters) NB_HIP(t->mem.alloc_late(&t->counters, sizeof(uint32_t) * 2 * size_t(t->n)));
   t->counters_on = on != 0;
   return NBODY_OK;
 }
@@ -3458,7 +3423,7 @@ extern "C" int nbody_octree_compute_quadrupoles(nbody_octree* t, void* stream) {
       return NBODY_ERR_STATE;
     }
     const size_t qs = (t->dim == 3 ? 6 : 3) + size_t(t->dim);  // kOtQS: every node the groups can hold, and the root
-    NB_HIP(hipMalloc(&t->quad, t->tsz * qs * (size_t(t->max_cells) * (size_t(1) << t->dim) + 1)));
+    NB_HIP(t->mem.alloc_late(&t->quad, t->tsz * qs * (size_t(t->max_cells) * (size_t(1) << t->dim) + 1)));
   }
   int r = dispatch(t->dtype, t->dim, [&](auto tg) {
     using TG = decltype(tg);

@@ -93,6 +93,7 @@ struct nbody_octree_block {
   void* xp        = nullptr;    // predicted positions of the last block step, T[n][D]
   void* a1        = nullptr;    // the walk's output: rows of the active bodies, T[n][D]
   bool on = false, stepped = false;  // start has run; a block step has run since
+  nbody::device_buffers mem;    // owns the schedule's arrays, wlist, xp and a1
 };
 
 namespace nbody {
@@ -236,19 +237,8 @@ extern "C" int nbody_octree_block_create(nbody_octree_block** out, int dtype, in
 }
 
 extern "C" int nbody_octree_block_create_on(nbody_octree_block** out, int dtype, int dim, uint32_t n, int device) {
-  NB_ARG(out != nullptr, "out is NULL");
-  *out = nullptr;
-  NB_ARG(dtype == NBODY_F32 || dtype == NBODY_F64, "bad dtype %d", dtype);
-  NB_ARG(dim == 2 || dim == 3, "bad dim %d", dim);
-  NB_ARG(n >= 1 && n <= (1u << 28), "octree block steps need 1 <= n <= 2^28 (got %u)", n);
-  if (captures_on_this_thread() != 0) {
-    set_error("nbody_octree_block_create allocates: it cannot be called between nbody_graph_begin and nbody_graph_end");
-    return NBODY_ERR_STATE;
-  }
-  int ndev = 0;
-  NB_HIP(hipGetDeviceCount(&ndev));
-  if (device < 0) device = current_device();
-  NB_ARG(device >= 0 && device < ndev, "device %d out of range (%d HIP devices visible)", device, ndev);
+  if (int r = create_check_args(out, dtype, dim, n, 1, 1u << 28, "octree block steps need 1 <= n <= 2^28 (got %u)")) return r;
+  if (int r = create_check_device(&device, "octree_block", true)) return r;
   device_guard guard(device);
   auto* h   = new nbody_octree_block;
   h->device = device;
@@ -257,28 +247,19 @@ extern "C" int nbody_octree_block_create_on(nbody_octree_block** out, int dtype,
   h->n      = n;
   h->tsz    = dtype == NBODY_F32 ? 4 : 8;
   const size_t rows = h->tsz * size_t(dim) * size_t(n);
-  hipError_t e      = block_schedule_alloc(&h->sched, n);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->wlist), sizeof(uint32_t) * size_t(n));
-  if (e == hipSuccess) e = hipMalloc(&h->xp, rows);
-  if (e == hipSuccess) e = hipMalloc(&h->a1, rows);
+  hipError_t e      = block_schedule_alloc(&h->sched, n, h->mem);
+  h->mem.alloc(&h->wlist, sizeof(uint32_t) * size_t(n));
+  h->mem.alloc(&h->xp, rows);
+  h->mem.alloc(&h->a1, rows);
+  if (e == hipSuccess) e = h->mem.error();
   // nothing is cleared: start writes lev, tau and the schedule words, and every block step writes xp, the lists and the listed rows
   // of a1 before it reads them
-  if (e != hipSuccess) {
-    int r = hip_fail(e, "nbody_octree_block_create allocation", __FILE__, __LINE__);
-    nbody_octree_block_destroy(h);
-    return r;
-  }
-  *out = h;
-  return NBODY_OK;
+  return create_finish(out, h, nbody_octree_block_destroy, e, "nbody_octree_block_create allocation");
 }
 
 extern "C" void nbody_octree_block_destroy(nbody_octree_block* h) {
   if (!h) return;
   device_guard guard(h->device);
-  block_schedule_free(&h->sched);
-  (void)hipFree(h->wlist);
-  (void)hipFree(h->xp);
-  (void)hipFree(h->a1);
   delete h;
 }
 

@@ -117,9 +117,9 @@ __device__ __forceinline__ void pair_sweep_tiles(const pair_rec<T>* __restrict__
 
 // Fills the shared fields of a new handle and allocates its records (the caller has made `device` current).  Nothing is cleared:
 // every compute writes all of them before it reads them.
-inline hipError_t pair_handle_alloc(hermite_handle* h, int dtype, int dim, uint32_t n, int device, const hermite_plan& plan) {
+inline void pair_handle_alloc(hermite_handle* h, int dtype, int dim, uint32_t n, int device, const hermite_plan& plan) {
   hermite_handle_fill(h, dtype, dim, n, device, plan);
-  return hipMalloc(&h->recs, h->tsz * 4 * size_t(h->padded));
+  h->mem.alloc(&h->recs, h->tsz * 4 * size_t(h->padded));
 }
 
 // The head of a compute call: check_state without the arrays it never reads (v, a and ao may be NULL), then the whole system.

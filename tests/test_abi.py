@@ -236,3 +236,37 @@ def test_k9_sweep_fits_eight_waves_per_simd(nb):
     assert len(ks) == 8, len(ks)
     for k in ks:
         assert int(k["sgpr_count"]) <= 78 and int(k["vgpr_count"]) + int(k.get("agpr_count", 0)) <= 64, (k["symbol"], k["sgpr_count"], k["vgpr_count"])
+
+
+# (create function, n below its range, n above it or None, the whole message for that n)
+_TREE_AND_CONTEXT_CREATES = (
+    ("nbody_bvh_create_on", 1, (1 << 30) + 1, "bvh needs 2 <= n <= 2^30 (got %u)"),
+    ("nbody_octree_create_on", 0, (1 << 28) + 1, "octree needs 1 <= n <= 2^28 (got %u)"),
+    ("nbody_create", 0, None, "n must be >= 1"),
+)
+
+
+@pytest.mark.parametrize("api, n_low, n_high, n_text", _TREE_AND_CONTEXT_CREATES, ids=[c[0] for c in _TREE_AND_CONTEXT_CREATES])
+def test_tree_and_context_create_argument_errors(nb, api, n_low, n_high, n_text):
+    """The create calls of the bvh, the octree and the context check out, dtype, dim and n in that order, each earlier error winning
+    over every later one, before any HIP call; the messages are pinned whole.  (The device comes after them and needs the runtime:
+    tests/test_gpu_handle_lifecycle.py.)"""
+    L = nb.lib()
+    create = getattr(L, api)
+    err = lambda: L.nbody_last_error().decode()
+    n = ctypes.c_uint32
+    assert create(None, 7, 4, n(n_low), 99) == 1 and err() == "out is NULL"
+    h = ctypes.c_void_p(0x1000)  # a refused create leaves NULL behind, not what was there
+    assert create(ctypes.byref(h), 7, 4, n(n_low), 99) == 1 and err() == "bad dtype 7"
+    assert h.value is None
+    assert create(ctypes.byref(h), -1, 3, n(16), 0) == 1 and err() == "bad dtype -1"
+    for dim in (1, 4):
+        assert create(ctypes.byref(h), nb.F64, dim, n(n_low), 99) == 1 and err() == f"bad dim {dim}"
+    for bad in (n_low, n_high):
+        if bad is not None:
+            for dtype, dim in ((nb.F32, 2), (nb.F64, 3)):
+                assert create(ctypes.byref(h), dtype, dim, n(bad), 99) == 1 and err() == n_text.replace("%u", str(bad)), (bad, err())
+    assert h.value is None
+    for name in ("nbody_bvh_create", "nbody_octree_create"):  # the forms without a device: the same checks
+        if api.startswith(name):
+            assert getattr(L, name)(ctypes.byref(h), nb.F64, 3, n(n_low)) == 1 and err() == n_text.replace("%u", str(n_low))
