@@ -94,7 +94,9 @@ typedef struct nbody_state {
  *      nbody_neighbours_create_on, nbody_neighbours_destroy, nbody_neighbours_compute, nbody_neighbours_read,
  *      nbody_neighbours_closest_pair.  Additive, same version: all-pairs k nearest neighbours, local densities and the density
  *      centre, nbody_knn_create, nbody_knn_create_on, nbody_knn_destroy, nbody_knn_compute, nbody_knn_read,
- *      nbody_knn_density_centre; nbody_knn_create_method and nbody_knn_method (the tree-pruned method of the same handle). */
+ *      nbody_knn_density_centre; nbody_knn_create_method and nbody_knn_method (the tree-pruned method of the same handle).
+ *      Additive, same version: friends-of-friends groups on the same tree, nbody_fof_create, nbody_fof_create_on,
+ *      nbody_fof_destroy, nbody_fof_compute, nbody_fof_read, nbody_fof_summary. */
 #define NBODY_HIP_ABI_VERSION 2004
 int nbody_abi_version(void);
 
@@ -674,6 +676,54 @@ int  nbody_knn_read(nbody_knn* h, int what, void* host_out, size_t bytes, void* 
 /* Blocking.  The summary of the last compute: centre_out T[dim], the core radius and the core density one T each; any of the three
  * may be NULL. */
 int  nbody_knn_density_centre(nbody_knn* h, void* centre_out, void* core_radius_out, void* core_density_out, void* stream);
+
+/* ---- friends-of-friends groups (no reference counterpart) ---------------------------------------------------------------------------
+ * Which bodies belong together: clumps, sub-clusters, escapers, the core against the halo.  Reads a state's (m, x) and changes nothing
+ * in it; positions only — no softening, no periodic wrap, no velocities.  With T the state's type and D its dimension:
+ *   link       i and j (i != j) are friends iff d2_ij <= b2.  d2_ij is exactly the d2 of the neighbours and kNN sections above (one
+ *              FMA chain in component order, contraction off, bitwise symmetric in (i, j)); b2 = T(b) * T(b), rounded once in T on the
+ *              host; b is a double argument of compute.  b = 0 is legal and links only bodies whose computed d2 is 0.
+ *   group      a connected component of the friend relation.  label[i] is the LOWEST original index among the members of i's group,
+ *              so label[i] <= i, and label[i] == i for exactly one member of each group; size[i] is the member count of i's group.
+ *              Both uint32_t[n] in the state's body order.  They are integers with one correct answer: neither depends on the order
+ *              of the bodies in the state beyond the renaming, nor on how the bodies happen to be scheduled.
+ *   summary    uint32_t[4]: the number of groups, the number of catalogued groups c, the largest size, the label of the largest group
+ *              (among groups of equal largest size the lowest label).
+ *   catalogue  the groups with size >= min_members, in ascending label order; min_members is fixed at create.  Per entry: label
+ *              (uint32), size (uint32), mass (T), com[D] (T).  Mass and sum(m x) are accumulated in DOUBLE for both types in an order
+ *              that is a fixed function of the group's member list in ascending original index (member t goes to partial t mod 64,
+ *              the 64 partials are folded by a fixed tree), com = sum(m x) / sum(m), each converted to T once.
+ *              Masses may be zero (tracers): a catalogued group whose masses sum to 0 has mass 0 and com = 0 / 0 = NaN by IEEE
+ *              rules, which is not an error (label and size do not look at the masses).
+ * The search is exact: the tree of the kNN section's TREE method prunes with a bound that needs no tolerance, and a group is built
+ * with a lock-free union-find over integer indices.  No floating-point atomics anywhere: two computes of the same state give the
+ * same bits for every output, and so do an eager call and a replayed recorded one, and a handle destroyed and made again.  No loop of
+ * any kernel waits for another lane, wave or block.  Non-finite positions are outside the contract (the call stays memory-safe; a NaN
+ * distance links nothing).
+ *  - create allocates everything (packed and sorted records, boxes, keys, the sort's scratch, the union-find arrays, label, size, a
+ *    catalogue of n / min_members entries, the summary) and frees everything again if one allocation fails.  Argument errors in this
+ *    order: out NULL, dtype, dim, n = 0 or n > 2^28, min_members outside 1 .. n (all NBODY_ERR_ARG).  create(_on) between
+ *    nbody_graph_begin and nbody_graph_end: NBODY_ERR_STATE.
+ *  - compute reads s->m and s->x only: s->v, s->a and s->ao may be NULL or garbage.  Asynchronous, allocates nothing, reads nothing
+ *    back, may be recorded into a step graph; the number of launches is a function of n alone.  Whole system only.
+ *  - Argument errors of compute are found before the device is touched, in this order: s NULL; the state's dtype, dim, window,
+ *    tuning; the whole-system rule; h NULL; h made for another dtype, dim or n; b negative, NaN or infinite; b2 not finite in T (all
+ *    NBODY_ERR_ARG).  Then a stream of another device (NBODY_ERR_ARG).
+ *  - read and summary are blocking; NBODY_ERR_STATE before the first compute on that handle and between nbody_graph_begin and
+ *    nbody_graph_end (the capture stays usable).  Every entry switches to the handle's device and restores the caller's. */
+typedef struct nbody_fof nbody_fof;
+int  nbody_fof_create(nbody_fof** out, int dtype, int dim, uint32_t n, uint32_t min_members);                /* on the current device */
+int  nbody_fof_create_on(nbody_fof** out, int dtype, int dim, uint32_t n, uint32_t min_members, int device); /* device < 0: the current one */
+void nbody_fof_destroy(nbody_fof* h);                                                                        /* NULL: no-op */
+/* label, size, the summary and the catalogue at (s->m, s->x) for the linking length b, into the handle.  Asynchronous, recordable. */
+int  nbody_fof_compute(nbody_fof* h, const nbody_state* s, double b, void* stream);
+/* Blocking.  what: 0 label uint32[n] | 1 size uint32[n]: bytes must be n * 4.  2 label uint32[c] | 3 size uint32[c] | 4 mass T[c] |
+ * 5 com T[c][dim] of the catalogue: bytes must be c * the element's size; the call reads c back itself, so nbody_fof_summary need not
+ * have been called (c = 0: bytes = 0, nothing is written, host_out may be NULL).  Order of the argument errors: what, h NULL, then for
+ * 0 / 1 host_out NULL and bytes; the state rules; then for 2 .. 5 bytes and host_out NULL. */
+int  nbody_fof_read(nbody_fof* h, int what, void* host_out, size_t bytes, void* stream);
+/* Blocking.  out4: the summary of the last compute. */
+int  nbody_fof_summary(nbody_fof* h, uint32_t* out4, void* stream);
 
 /* ---- owning context (device mirrors of a host System), used by the C++ CLI host ------------------ */
 

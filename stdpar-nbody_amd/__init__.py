@@ -72,6 +72,7 @@ ABI_SYMBOLS = [
     "nbody_neighbours_read", "nbody_neighbours_closest_pair",
     "nbody_knn_create", "nbody_knn_create_on", "nbody_knn_destroy", "nbody_knn_compute", "nbody_knn_read", "nbody_knn_density_centre",
     "nbody_knn_create_method", "nbody_knn_method",
+    "nbody_fof_create", "nbody_fof_create_on", "nbody_fof_destroy", "nbody_fof_compute", "nbody_fof_read", "nbody_fof_summary",
 ]
 ABI_MAJOR = 2
 COMM_ID_BYTES = 128
@@ -144,6 +145,13 @@ def lib():
         L.nbody_knn_compute.argtypes = [vp, vp, vp]
         L.nbody_knn_read.argtypes = [vp, C.c_int, vp, C.c_size_t, vp]
         L.nbody_knn_density_centre.argtypes = [vp, vp, vp, vp, vp]
+        L.nbody_fof_create.argtypes = [vp, C.c_int, C.c_int, C.c_uint32, C.c_uint32]
+        L.nbody_fof_create_on.argtypes = [vp, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_int]
+        L.nbody_fof_destroy.restype = None
+        L.nbody_fof_destroy.argtypes = [vp]
+        L.nbody_fof_compute.argtypes = [vp, vp, d, vp]
+        L.nbody_fof_read.argtypes = [vp, C.c_int, vp, C.c_size_t, vp]
+        L.nbody_fof_summary.argtypes = [vp, vp, vp]
         _lib = L
     return _lib
 
@@ -635,6 +643,47 @@ class Knn(_Handle):
         return x, rc[0], rhoc[0]
 
 
+class Fof(_Handle):
+    """Friends-of-friends groups (nbody_fof_*): bodies no farther apart than a linking length b are friends, a group is a connected
+    component.  Exact, on the tree of the kNN "tree" method.  min_members (fixed here, 1 .. n) is the smallest group the catalogue
+    lists; label and size cover every body whatever it is."""
+
+    _destroy = "nbody_fof_destroy"
+
+    def __init__(self, dtype, dim, n, min_members=1, device=-1):
+        """device: where the handle's buffers live (-1: the calling thread's current device)."""
+        self.h = C.c_void_p()
+        self.dtype, self.dim, self.n, self.min_members = dtype, dim, n, min_members
+        _check(lib().nbody_fof_create_on(C.byref(self.h), dtype, dim, C.c_uint32(n), C.c_uint32(min_members), device))
+
+    def compute(self, st, b, stream=None):
+        """label, size, the summary and the catalogue at (st.m, st.x) for the linking length b >= 0, into the handle.  Asynchronous,
+        recordable."""
+        _check(lib().nbody_fof_compute(self.h, C.byref(st), C.c_double(b), stream))
+
+    def summary(self, stream=None):
+        """(groups, catalogued groups, largest size, label of the largest group) of the last compute, uint32 (4,) (blocking)."""
+        out = np.zeros(4, np.uint32)
+        _check(lib().nbody_fof_summary(self.h, _p(out), stream))
+        return out
+
+    def read(self, what, stream=None):
+        """0 label (n,) uint32, 1 size (n,) uint32; the catalogue's 2 label (c,) uint32, 3 size (c,) uint32, 4 mass (c,) of T,
+        5 com (c, dim) of T of the last compute (blocking)."""
+        t = np_dtype(self.dtype)
+        if what <= 1:
+            out = np.zeros(self.n, np.uint32)
+        else:
+            c = int(self.summary(stream)[1])
+            out = np.zeros((c, self.dim), t) if what == 5 else np.zeros(c, np.uint32 if what <= 3 else t)
+        _check(lib().nbody_fof_read(self.h, what, _p(out) if out.size else None, out.nbytes, stream))
+        return out
+
+    def catalogue(self, stream=None):
+        """{"label", "size", "mass", "com"}: the groups of at least min_members bodies, in ascending label order (blocking)."""
+        return {name: self.read(what, stream) for what, name in ((2, "label"), (3, "size"), (4, "mass"), (5, "com"))}
+
+
 class OctreeBlock(_Handle):
     """Block (individual) time steps for the octree leapfrog (nbody_octree_block_*): owns the levels, tau, the active lists, the
     predicted positions and the scratch of the active set's forces; the tree is the caller's Octree."""
@@ -689,6 +738,7 @@ class DeviceSystem(_Handle):
             setattr(self, a, None)
         self._knn = {}
         self._knn_other = {}
+        self._fof = {}
 
     @classmethod
     def from_host(cls, hs, device=0):
@@ -698,6 +748,7 @@ class DeviceSystem(_Handle):
 
     def close(self):
         cached = [getattr(self, a) for a in self._CACHED] + list(self._knn.values()) + list(self._knn_other.values())
+        cached += list(self._fof.values())
         for h in cached:
             if h is not None:
                 h.close()
@@ -705,6 +756,7 @@ class DeviceSystem(_Handle):
             setattr(self, a, None)
         self._knn = {}
         self._knn_other = {}
+        self._fof = {}
         super().close()  # the context last
 
     def upload(self, hs):
@@ -929,6 +981,32 @@ class DeviceSystem(_Handle):
         h = self.knn_handle(k, method)
         h.compute(self.state(), self.stream)
         return h.density_centre(self.stream)
+
+    # friends-of-friends groups (no reference counterpart)
+    def fof_handle(self, min_members=1):
+        """The Fof handle of this system for min_members, made at the first use and closed with the system."""
+        if min_members not in self._fof:
+            self._fof[min_members] = Fof(self.dtype, self.dim, self.n, min_members, self.device)
+        return self._fof[min_members]
+
+    def fof_compute(self, b, min_members=1):
+        """nbody_fof_compute on the state as it is; a StepGraph may record it (the handle for min_members is made before the
+        recording)."""
+        self.fof_handle(min_members).compute(self.state(), b, self.stream)
+
+    def fof(self, b, min_members=1):
+        """(label (n,) uint32, size (n,) uint32) of the state as it is for the linking length b: the lowest index in every body's
+        group and the group's member count (blocking)."""
+        h = self.fof_handle(min_members)
+        h.compute(self.state(), b, self.stream)
+        return h.read(0, self.stream), h.read(1, self.stream)
+
+    def fof_groups(self, b, min_members=20):
+        """(catalogue, summary): the groups of at least min_members bodies ({"label", "size", "mass", "com"}, ascending label) and
+        (groups, catalogued groups, largest size, its label) (blocking)."""
+        h = self.fof_handle(min_members)
+        h.compute(self.state(), b, self.stream)
+        return h.catalogue(self.stream), h.summary(self.stream)
 
     def calc_energies(self, softening=0.0):
         """(kinetic, potential) as in System::calc_energies (src/system.h:62-79); blocking.  softening > 0: the potential of the

@@ -46,6 +46,7 @@
 // takes the branch U insertions of K compares and 2 K selects (3 K v_cndmask in double).
 #include "pair_sweep.hpp"
 #include "radix_sort.hpp"
+#include "fof_union.hpp"
 
 #pragma clang fp contract(off)
 
@@ -305,6 +306,7 @@ __global__ __launch_bounds__(kKnnSumBlock) void knn_summary_kernel(const T* __re
 }
 
 #include "nntree.inc"
+#include "fof.inc"
 
 }  // namespace nbody
 
@@ -320,14 +322,8 @@ struct nbody_knn : hermite_handle {
   void* rho        = nullptr;  // T[n]
   void* summary    = nullptr;  // T[kKnnSummaryLen]
   // NBODY_KNN_TREE only (nntree.inc); part and part_j stay NULL there
-  int method        = NBODY_KNN_ALL_PAIRS;
-  nntree_shape tree{};
-  void* sorted      = nullptr;             // nntree_rec<T>[padded]
-  void* boxes       = nullptr;             // nntree_box<T>[2 leaves], heap order
-  void* bounds      = nullptr;             // nntree_box<T>[bounds_blocks]
-  uint64_t* keys[2] = {nullptr, nullptr};  // [n] each
-  uint32_t* perm[2] = {nullptr, nullptr};  // [n] each: the sort's index buffers
-  uint32_t* hist    = nullptr;             // radix_sort_scratch_words(n)
+  int method = NBODY_KNN_ALL_PAIRS;
+  nntree_structure st{};
 };
 
 namespace nbody {
@@ -352,32 +348,17 @@ static int knn_launch(nbody_knn* h, const nbody_state* s, hipStream_t st) {
   return NBODY_OK;
 }
 
-// The TREE method: pack, bounds, keys, sort, gather + bucket boxes, upper levels, walk, finish, summary.  The launch count follows
-// from n alone (the sort's form does).
+// The TREE method: the structure (nntree_structure_launch: pack, bounds, keys, sort, gather + bucket boxes, upper levels), walk,
+// finish, summary.  The launch count follows from n alone (the sort's form does).
 template <typename T, int D, int K>
 static int knn_tree_launch(nbody_knn* h, const nbody_state* s, hipStream_t st) {
-  const nntree_shape& t = h->tree;
+  const nntree_shape& t = h->st.tree;
   auto* recs            = static_cast<pair_rec<T>*>(h->recs);
-  auto* sorted          = static_cast<nntree_rec<T>*>(h->sorted);
-  auto* boxes           = static_cast<nntree_box<T>*>(h->boxes);
-  auto* bounds          = static_cast<nntree_box<T>*>(h->bounds);
+  auto* sorted          = static_cast<nntree_rec<T>*>(h->st.sorted);
+  auto* boxes           = static_cast<nntree_box<T>*>(h->st.boxes);
   T* rho                = static_cast<T*>(h->rho);
   const uint32_t n      = h->n;
-  hipLaunchKernelGGL((pair_pack_kernel<T, D>), dim3(h->padded / kHBlock), dim3(kHBlock), 0, st, static_cast<const T*>(s->m),
-                     static_cast<const T*>(s->x), recs, n, h->padded);
-  NB_HIP(hipGetLastError());
-  hipLaunchKernelGGL((nntree_bounds_kernel<T, D>), dim3(t.bounds_blocks), dim3(kNtBlock), 0, st, recs, bounds, n);
-  NB_HIP(hipGetLastError());
-  hipLaunchKernelGGL((nntree_keys_kernel<T, D>), dim3((n + kNtBlock - 1) / kNtBlock), dim3(kNtBlock), 0, st, recs, bounds, t.bounds_blocks,
-                     h->keys[0], n);
-  NB_HIP(hipGetLastError());
-  int fin = 0;
-  if (int r = radix_sort_pairs(h->keys, h->perm, n, D == 3 ? 63 : 64, h->hist, st, &fin)) return r;
-  hipLaunchKernelGGL((nntree_gather_kernel<T, D>), dim3(h->padded / kNtBlock), dim3(kNtBlock), 0, st, recs, h->perm[fin], sorted,
-                     boxes + t.leaves, n, t.buckets);
-  NB_HIP(hipGetLastError());
-  hipLaunchKernelGGL((nntree_upper_kernel<T, D>), dim3(1), dim3(kNtUpper), 0, st, boxes, n, t.levels);
-  NB_HIP(hipGetLastError());
+  if (int r = nntree_structure_launch<T, D>(&h->st, s, recs, n, h->padded, st)) return r;
   hipLaunchKernelGGL((nntree_walk_kernel<T, D, K>), dim3(h->padded / kNtBlock), dim3(kNtBlock), 0, st, sorted, boxes, h->idx,
                      static_cast<T*>(h->d2), n, t.levels, t.buckets, h->k);
   NB_HIP(hipGetLastError());
@@ -420,15 +401,7 @@ extern "C" int nbody_knn_create_method(nbody_knn** out, int dtype, int dim, uint
   pair_handle_alloc(h, dtype, dim, n, device, knn_plan_for(n));
   h->method = method;
   if (method == NBODY_KNN_TREE) {  // what the tree path needs, and not the chunks' partial lists
-    h->tree = nntree_shape_for(n);
-    h->mem.alloc(&h->sorted, h->tsz * 4 * size_t(h->padded));
-    h->mem.alloc(&h->boxes, h->tsz * 8 * 2 * size_t(h->tree.leaves));
-    h->mem.alloc(&h->bounds, h->tsz * 8 * size_t(h->tree.bounds_blocks));
-    for (int b = 0; b < 2; ++b) {
-      h->mem.alloc(&h->keys[b], sizeof(uint64_t) * size_t(n));
-      h->mem.alloc(&h->perm[b], sizeof(uint32_t) * size_t(n));
-    }
-    h->mem.alloc(&h->hist, sizeof(uint32_t) * radix_sort_scratch_words(n));
+    nntree_structure_alloc(&h->st, h->mem, h->tsz, n, h->padded);
   } else {
     const size_t rows = size_t(h->plan.chunks) * size_t(n) * size_t(h->K);
     h->mem.alloc(&h->part, h->tsz * rows);
@@ -496,5 +469,173 @@ extern "C" int nbody_knn_density_centre(nbody_knn* h, void* centre_out, void* co
   if (centre_out) memcpy(centre_out, raw, t * size_t(h->dim));
   if (core_radius_out) memcpy(core_radius_out, raw + 3 * t, t);
   if (core_density_out) memcpy(core_density_out, raw + 4 * t, t);
+  return NBODY_OK;
+}
+
+// ---- friends-of-friends groups (fof.inc) ---------------------------------------------------------------------------------------
+// recs: pair_rec<T>[padded], original order (the catalogue's masses and positions); st: the structure nbody_knn's tree method builds
+// too.  The catalogue's sort runs in the structure's keys / perm / hist, which are free once the gather has run.
+struct nbody_fof : hermite_handle {
+  uint32_t min_members = 1, cmax = 0, strips = 0;
+  nntree_structure st{};
+  uint32_t* parent    = nullptr;  // [padded], over sorted positions
+  uint32_t* root      = nullptr;  // [padded]
+  uint32_t* minidx    = nullptr;  // [n], by root
+  uint32_t* count     = nullptr;  // [n], by root
+  uint32_t* label     = nullptr;  // [n], original order
+  uint32_t* size      = nullptr;  // [n], original order
+  uint32_t* scount    = nullptr;  // [strips]: heads a strip, then their exclusive scan
+  uint32_t* cat_label = nullptr;  // [cmax] each
+  uint32_t* cat_size  = nullptr;
+  uint32_t* cat_start = nullptr;
+  void* cat_mass      = nullptr;  // T[cmax]
+  void* cat_com       = nullptr;  // T[cmax][dim]
+  uint32_t* summary   = nullptr;  // [4]
+};
+
+namespace nbody {
+
+// init, the structure, link, flatten, labels, summary, the catalogue's sort, count, scan, scatter, sums.
+template <typename T, int D>
+static int fof_launch(nbody_fof* h, const nbody_state* s, T b2, hipStream_t st) {
+  auto* recs       = static_cast<pair_rec<T>*>(h->recs);
+  const void* sorted = h->st.sorted;  // nntree_rec<T>[padded], nntree_box<T>[2 leaves]: untyped on purpose, see the head of fof.inc
+  const void* boxes  = h->st.boxes;
+  const uint32_t n = h->n, mm = h->min_members;
+  const dim3 padded_grid(h->padded / kNtBlock), n_grid((n + kNtBlock - 1) / kNtBlock), block(kNtBlock);
+  hipLaunchKernelGGL(fof_init_kernel, padded_grid, block, 0, st, h->parent, h->minidx, h->count, n);
+  NB_HIP(hipGetLastError());
+  if (int r = nntree_structure_launch<T, D>(&h->st, s, recs, n, h->padded, st)) return r;
+  hipLaunchKernelGGL((fof_link_kernel<T, D>), padded_grid, block, 0, st, sorted, boxes, h->parent, n, h->st.tree.levels, b2);
+  NB_HIP(hipGetLastError());
+  hipLaunchKernelGGL((fof_flatten_kernel<T>), padded_grid, block, 0, st, sorted, h->parent, h->root, h->minidx, h->count, n);
+  NB_HIP(hipGetLastError());
+  hipLaunchKernelGGL((fof_labels_kernel<T>), n_grid, block, 0, st, sorted, h->root, h->minidx, h->count, h->label, h->size, h->st.keys[0], n);
+  NB_HIP(hipGetLastError());
+  hipLaunchKernelGGL(fof_summary_kernel, dim3(1), dim3(kFofSumBlock), 0, st, h->label, h->size, n, mm, h->summary);
+  NB_HIP(hipGetLastError());
+  uint64_t* keys[2] = {h->st.keys[0], h->st.keys[1]};
+  uint32_t* perm[2] = {h->st.perm[0], h->st.perm[1]};
+  int fin           = 0;
+  if (int r = radix_sort_pairs(keys, perm, n, 32, h->st.hist, st, &fin)) return r;
+  hipLaunchKernelGGL(fof_cat_count_kernel, dim3(h->strips), block, 0, st, keys[fin], perm[fin], h->size, n, mm, h->scount);
+  NB_HIP(hipGetLastError());
+  hipLaunchKernelGGL(fof_cat_scan_kernel, dim3(1), dim3(kFofSumBlock), 0, st, h->scount, h->strips);
+  NB_HIP(hipGetLastError());
+  hipLaunchKernelGGL(fof_cat_scatter_kernel, dim3(h->strips), block, 0, st, keys[fin], perm[fin], h->size, n, mm, h->scount, h->cat_label,
+                     h->cat_size, h->cat_start, h->cmax);
+  NB_HIP(hipGetLastError());
+  hipLaunchKernelGGL((fof_cat_sum_kernel<T, D>), dim3((h->cmax + kNtBlock / 64 - 1) / (kNtBlock / 64)), block, 0, st, recs, perm[fin], h->cat_size,
+                     h->cat_start, h->summary, static_cast<T*>(h->cat_mass), static_cast<T*>(h->cat_com), h->cmax);
+  NB_HIP(hipGetLastError());
+  return NBODY_OK;
+}
+
+}  // namespace nbody
+
+extern "C" int nbody_fof_create(nbody_fof** out, int dtype, int dim, uint32_t n, uint32_t min_members) {
+  return nbody_fof_create_on(out, dtype, dim, n, min_members, -1);
+}
+
+extern "C" int nbody_fof_create_on(nbody_fof** out, int dtype, int dim, uint32_t n, uint32_t min_members, int device) {
+  if (int r = create_check_args(out, dtype, dim, n, 1, 1u << 28, "fof needs 1 <= n <= 2^28 (got %u)")) return r;
+  NB_ARG(min_members >= 1 && min_members <= n, "fof needs 1 <= min_members <= n (got %u, n = %u)", min_members, n);
+  if (int r = create_check_device(&device, "fof", true)) return r;
+  device_guard guard(device);
+  auto* h = new nbody_fof;
+  // nothing is cleared: every compute writes all of it before it reads it
+  pair_handle_alloc(h, dtype, dim, n, device, knn_plan_for(n));
+  h->min_members = min_members;
+  h->cmax        = n / min_members;  // there cannot be more groups of min_members bodies
+  h->strips      = (n + kNtBlock - 1) / kNtBlock;
+  nntree_structure_alloc(&h->st, h->mem, h->tsz, n, h->padded);
+  h->mem.alloc(&h->parent, sizeof(uint32_t) * size_t(h->padded));
+  h->mem.alloc(&h->root, sizeof(uint32_t) * size_t(h->padded));
+  h->mem.alloc(&h->minidx, sizeof(uint32_t) * size_t(n));
+  h->mem.alloc(&h->count, sizeof(uint32_t) * size_t(n));
+  h->mem.alloc(&h->label, sizeof(uint32_t) * size_t(n));
+  h->mem.alloc(&h->size, sizeof(uint32_t) * size_t(n));
+  h->mem.alloc(&h->scount, sizeof(uint32_t) * size_t(h->strips));
+  h->mem.alloc(&h->cat_label, sizeof(uint32_t) * size_t(h->cmax));
+  h->mem.alloc(&h->cat_size, sizeof(uint32_t) * size_t(h->cmax));
+  h->mem.alloc(&h->cat_start, sizeof(uint32_t) * size_t(h->cmax));
+  h->mem.alloc(&h->cat_mass, h->tsz * size_t(h->cmax));
+  h->mem.alloc(&h->cat_com, h->tsz * size_t(h->cmax) * size_t(dim));
+  h->mem.alloc(&h->summary, sizeof(uint32_t) * 4);
+  return create_finish(out, h, nbody_fof_destroy, h->mem.error(), "nbody_fof_create allocation");
+}
+
+extern "C" void nbody_fof_destroy(nbody_fof* h) {
+  if (!h) return;
+  device_guard guard(h->device);
+  delete h;
+}
+
+extern "C" int nbody_fof_compute(nbody_fof* h, const nbody_state* s, double b, void* stream) {
+  if (int r = pair_check_state(s, "nbody_fof_compute")) return r;
+  NB_ARG(h != nullptr, "nbody_fof is NULL");
+  NB_ARG(h->dtype == s->dtype && h->dim == s->dim && h->n == s->sz,
+         "nbody_fof was created for (dtype %d, dim %d, n %u), the state is (dtype %d, dim %d, sz %u)", h->dtype, h->dim, h->n, s->dtype,
+         s->dim, s->sz);
+  NB_ARG(b >= 0.0 && b <= DBL_MAX, "linking length b = %g must be finite and >= 0", b);
+  const hipStream_t st = as_stream(stream);
+  return dispatch(s->dtype, s->dim, [&](auto tg) {
+    using T         = typename decltype(tg)::type;
+    constexpr int D = decltype(tg)::dim;
+    // b is compared in double BEFORE it is converted: a finite double beyond T's range has no defined conversion to T
+    NB_ARG(b <= double(sizeof(T) == 4 ? T(FLT_MAX) : T(DBL_MAX)), "linking length b = %g: b^2 is not finite in the state's type", b);
+    const T bt = T(b);
+    const T b2 = bt * bt;  // rounded once in T
+    NB_ARG(b2 <= (sizeof(T) == 4 ? T(FLT_MAX) : T(DBL_MAX)), "linking length b = %g: b^2 is not finite in the state's type", b);
+    if (int r = check_same_device(h->device, st, "nbody_fof")) return r;
+    device_guard guard(h->device);
+    const int r = fof_launch<T, D>(h, s, b2, st);
+    if (r == NBODY_OK) h->started = true;
+    return r;
+  });
+}
+
+// the summary of the last compute, blocking (the callers have checked pair_read_ready)
+static int fof_read_summary(nbody_fof* h, uint32_t (&out)[4], hipStream_t st) {
+  NB_HIP(hipMemcpyAsync(out, h->summary, sizeof out, hipMemcpyDeviceToHost, st));
+  NB_HIP(hipStreamSynchronize(st));
+  return NBODY_OK;
+}
+
+extern "C" int nbody_fof_read(nbody_fof* h, int what, void* host_out, size_t bytes, void* stream) {
+  NB_ARG(what >= 0 && what <= 5, "what must be 0 (label), 1 (size) or 2 .. 5 (the catalogue's label, size, mass, com), got %d", what);
+  NB_ARG(h != nullptr, "nbody_fof is NULL");
+  if (what <= 1) {
+    NB_ARG(host_out != nullptr, "host_out is NULL");
+    NB_ARG(bytes == sizeof(uint32_t) * size_t(h->n), "nbody_fof_read(what = %d) needs %zu bytes, got %zu", what, sizeof(uint32_t) * size_t(h->n), bytes);
+  }
+  const hipStream_t st = as_stream(stream);
+  if (int r = pair_read_ready(h, "nbody_fof", "nbody_fof_read", "nbody_fof_compute", st)) return r;
+  device_guard guard(h->device);
+  const void* src = what == 0 ? h->label : h->size;
+  if (what >= 2) {  // c entries: c is read back here (a replayed recorded compute changes it without a host call)
+    uint32_t sum[4];
+    if (int r = fof_read_summary(h, sum, st)) return r;
+    const size_t elem = what <= 3 ? sizeof(uint32_t) : what == 4 ? h->tsz : h->tsz * size_t(h->dim);
+    NB_ARG(bytes == elem * size_t(sum[1]), "nbody_fof_read(what = %d) needs %zu bytes (%u catalogued groups), got %zu", what, elem * size_t(sum[1]),
+           sum[1], bytes);
+    if (bytes == 0) return NBODY_OK;
+    NB_ARG(host_out != nullptr, "host_out is NULL");
+    src = what == 2 ? static_cast<const void*>(h->cat_label) : what == 3 ? static_cast<const void*>(h->cat_size) : what == 4 ? h->cat_mass : h->cat_com;
+  }
+  NB_HIP(hipMemcpyAsync(host_out, src, bytes, hipMemcpyDeviceToHost, st));
+  NB_HIP(hipStreamSynchronize(st));
+  return NBODY_OK;
+}
+
+extern "C" int nbody_fof_summary(nbody_fof* h, uint32_t* out4, void* stream) {
+  NB_ARG(h != nullptr, "nbody_fof is NULL");
+  NB_ARG(out4 != nullptr, "out4 is NULL");
+  const hipStream_t st = as_stream(stream);
+  if (int r = pair_read_ready(h, "nbody_fof", "nbody_fof_summary", "nbody_fof_compute", st)) return r;
+  device_guard guard(h->device);
+  uint32_t sum[4];
+  if (int r = fof_read_summary(h, sum, st)) return r;
+  memcpy(out4, sum, sizeof sum);
   return NBODY_OK;
 }

@@ -432,3 +432,58 @@ static __global__ __launch_bounds__(kNtBlock) void nntree_finish_kernel(const pa
   }
   knn_finish_tail<T, D, K>(ld, lj, recs, idx, d2, rho, i, n, k);
 }
+
+// ---- host: the structure -------------------------------------------------------------------------------------------------------
+// What every compute over this structure rebuilds, and the buffers it lives in: nbody_knn (NBODY_KNN_TREE) and nbody_fof (fof.inc)
+// both hold one.  keys, perm and hist are the sort's; they are free again once the gather has run.
+struct nntree_structure {
+  nntree_shape tree{};
+  void* sorted      = nullptr;             // nntree_rec<T>[padded]
+  void* boxes       = nullptr;             // nntree_box<T>[2 leaves], heap order
+  void* bounds      = nullptr;             // nntree_box<T>[bounds_blocks]
+  uint64_t* keys[2] = {nullptr, nullptr};  // [n] each
+  uint32_t* perm[2] = {nullptr, nullptr};  // [n] each: the sort's index buffers
+  uint32_t* hist    = nullptr;             // radix_sort_scratch_words(n)
+};
+
+// Sized from n alone, through the handle's owner.  Nothing is cleared: every compute writes all of it before it reads it.
+inline void nntree_structure_alloc(nntree_structure* t, device_buffers& mem, size_t tsz, uint32_t n, uint32_t padded) {
+  t->tree = nntree_shape_for(n);
+  mem.alloc(&t->sorted, tsz * 4 * size_t(padded));
+  mem.alloc(&t->boxes, tsz * 8 * 2 * size_t(t->tree.leaves));
+  mem.alloc(&t->bounds, tsz * 8 * size_t(t->tree.bounds_blocks));
+  for (int b = 0; b < 2; ++b) {
+    mem.alloc(&t->keys[b], sizeof(uint64_t) * size_t(n));
+    mem.alloc(&t->perm[b], sizeof(uint32_t) * size_t(n));
+  }
+  mem.alloc(&t->hist, sizeof(uint32_t) * radix_sort_scratch_words(n));
+}
+
+// pack, bounds, keys, sort, gather + bucket boxes, upper levels: recs (pair_rec<T>[padded], original order), t->sorted and t->boxes
+// are what the walks read.  The launch count follows from n alone (the sort's form does).
+template <typename T, int D>
+static int nntree_structure_launch(const nntree_structure* t, const nbody_state* s, pair_rec<T>* recs, uint32_t n, uint32_t padded,
+                                   hipStream_t st) {
+  const nntree_shape& sh = t->tree;
+  auto* sorted           = static_cast<nntree_rec<T>*>(t->sorted);
+  auto* boxes            = static_cast<nntree_box<T>*>(t->boxes);
+  auto* bounds           = static_cast<nntree_box<T>*>(t->bounds);
+  uint64_t* keys[2]      = {t->keys[0], t->keys[1]};
+  uint32_t* perm[2]      = {t->perm[0], t->perm[1]};
+  hipLaunchKernelGGL((pair_pack_kernel<T, D>), dim3(padded / kHBlock), dim3(kHBlock), 0, st, static_cast<const T*>(s->m),
+                     static_cast<const T*>(s->x), recs, n, padded);
+  NB_HIP(hipGetLastError());
+  hipLaunchKernelGGL((nntree_bounds_kernel<T, D>), dim3(sh.bounds_blocks), dim3(kNtBlock), 0, st, recs, bounds, n);
+  NB_HIP(hipGetLastError());
+  hipLaunchKernelGGL((nntree_keys_kernel<T, D>), dim3((n + kNtBlock - 1) / kNtBlock), dim3(kNtBlock), 0, st, recs, bounds, sh.bounds_blocks,
+                     keys[0], n);
+  NB_HIP(hipGetLastError());
+  int fin = 0;
+  if (int r = radix_sort_pairs(keys, perm, n, D == 3 ? 63 : 64, t->hist, st, &fin)) return r;
+  hipLaunchKernelGGL((nntree_gather_kernel<T, D>), dim3(padded / kNtBlock), dim3(kNtBlock), 0, st, recs, perm[fin], sorted,
+                     boxes + sh.leaves, n, sh.buckets);
+  NB_HIP(hipGetLastError());
+  hipLaunchKernelGGL((nntree_upper_kernel<T, D>), dim3(1), dim3(kNtUpper), 0, st, boxes, n, sh.levels);
+  NB_HIP(hipGetLastError());
+  return NBODY_OK;
+}

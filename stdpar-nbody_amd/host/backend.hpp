@@ -47,6 +47,7 @@ class Device {
   ~Device() {
     if (neighbours_) nbody_neighbours_destroy(neighbours_);
     if (knn_) nbody_knn_destroy(knn_);
+    if (fof_) nbody_fof_destroy(fof_);
     if (hermite_) nbody_hermite_destroy(hermite_);
     if (hermite6_) nbody_hermite6_destroy(hermite6_);
     if (octree_block_) nbody_octree_block_destroy(octree_block_);
@@ -168,6 +169,30 @@ class Device {
     backend_check(nbody_knn_density_centre(knn_, &summary[0], &summary[D], &summary[D + 1], stream()), "nbody_knn_density_centre");
   }
 
+  // --save-groups B: the friends-of-friends groups of the current x for the linking length b (nbody_fof_*; the reads are blocking):
+  // the summary, label and size of every body, and the catalogue of the groups of at least min_members bodies
+  void groups(double b, std::uint32_t min_members, std::uint32_t (&summary)[4], std::vector<std::uint32_t>& label,
+              std::vector<std::uint32_t>& size, std::vector<std::uint32_t>& cat_label, std::vector<std::uint32_t>& cat_size,
+              std::vector<T>& cat_mass, std::vector<T>& cat_com) {
+    single("--save-groups");
+    if (!fof_) backend_check(nbody_fof_create_on(&fof_, dtype, D, host_.n, min_members, 0), "nbody_fof_create_on");
+    backend_check(nbody_fof_compute(fof_, &view_[0], b, stream()), "nbody_fof_compute");
+    backend_check(nbody_fof_summary(fof_, summary, stream()), "nbody_fof_summary");
+    label.resize(host_.n);
+    size.resize(host_.n);
+    backend_check(nbody_fof_read(fof_, 0, label.data(), label.size() * sizeof(std::uint32_t), stream()), "nbody_fof_read");
+    backend_check(nbody_fof_read(fof_, 1, size.data(), size.size() * sizeof(std::uint32_t), stream()), "nbody_fof_read");
+    std::size_t const c = summary[1];
+    cat_label.resize(c);
+    cat_size.resize(c);
+    cat_mass.resize(c);
+    cat_com.resize(c * D);
+    backend_check(nbody_fof_read(fof_, 2, cat_label.data(), c * sizeof(std::uint32_t), stream()), "nbody_fof_read");
+    backend_check(nbody_fof_read(fof_, 3, cat_size.data(), c * sizeof(std::uint32_t), stream()), "nbody_fof_read");
+    backend_check(nbody_fof_read(fof_, 4, cat_mass.data(), c * sizeof(T), stream()), "nbody_fof_read");
+    backend_check(nbody_fof_read(fof_, 5, cat_com.data(), c * D * sizeof(T), stream()), "nbody_fof_read");
+  }
+
   // Record the phase calls issued by `step` once and return a replayable graph of them (one submission per step).
   template <typename F>
   nbody_graph* record(F&& step) {
@@ -270,6 +295,7 @@ class Device {
   nbody_octree_block* octree_block_ = nullptr;
   nbody_neighbours* neighbours_ = nullptr;
   nbody_knn* knn_               = nullptr;
+  nbody_fof* fof_               = nullptr;
 };
 
 }  // namespace nb

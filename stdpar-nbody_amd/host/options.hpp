@@ -4,6 +4,7 @@
 #include <cstdlib>
 #include <iostream>
 #include <optional>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -73,6 +74,13 @@ struct Options {
   // not in the reference either (nor in --help): --density-tree, --save-density K uses the tree-pruned exact method
   // (NBODY_KNN_TREE: the same density.bin byte for byte, for the large runs of the tree codes); needs --save-density
   bool density_tree = false;
+  // not in the reference either (nor in --help): --save-groups B (a linking length, finite and >= 0), at every frame the run's Saver
+  // records, the friends-of-friends groups of the positions (nbody_fof_*: summary, labels, sizes and the catalogue of the groups of
+  // at least --groups-min M bodies, default 20) are appended to groups.bin; independent of --save and of the algorithm; one GPU
+  bool save_groups     = false;
+  double groups_b      = 0.0;
+  long groups_min      = 20;
+  bool groups_min_given = false;
 };
 
 namespace detail {
@@ -216,6 +224,26 @@ inline Options parse_options(std::vector<std::string> const& argv) {
       o.save_density = int(v);
     } else if (f == "--density-tree") {
       o.density_tree = true;
+    } else if (f == "--save-groups") {
+      std::string const l = k + 1 < argv.size() ? argv[++k] : std::string();
+      char* end           = nullptr;
+      double const v      = std::strtod(l.c_str(), &end);
+      if (l.empty() || end != l.c_str() + l.size() || !(v >= 0.0) || !(v <= std::numeric_limits<double>::max())) {
+        std::cerr << "--save-groups needs a linking length B, finite and >= 0." << std::endl;
+        std::exit(EXIT_FAILURE);
+      }
+      o.save_groups = true;
+      o.groups_b    = v;
+    } else if (f == "--groups-min") {
+      std::string const l = k + 1 < argv.size() ? argv[++k] : std::string();
+      char* end           = nullptr;
+      long const v        = std::strtol(l.c_str(), &end, 10);
+      if (l.empty() || end != l.c_str() + l.size() || v < 1) {
+        std::cerr << "--groups-min needs a member count M >= 1." << std::endl;
+        std::exit(EXIT_FAILURE);
+      }
+      o.groups_min       = v;
+      o.groups_min_given = true;
     } else if (f == "--print-state") {
       o.print_state = true;
     } else if (f == "--print-info") {
@@ -255,6 +283,18 @@ inline Options parse_options(std::vector<std::string> const& argv) {
   }
   if (o.density_tree && o.save_density == 0) {
     std::cerr << "--density-tree needs --save-density K." << std::endl;
+    std::exit(EXIT_FAILURE);
+  }
+  if (o.groups_min_given && !o.save_groups) {
+    std::cerr << "--groups-min needs --save-groups B." << std::endl;
+    std::exit(EXIT_FAILURE);
+  }
+  if (o.save_groups && o.gpus_given) {
+    std::cerr << "--save-groups runs on one GPU: it cannot be combined with --gpus." << std::endl;
+    std::exit(EXIT_FAILURE);
+  }
+  if (o.save_groups && (o.size < 1 || o.groups_min > long(o.size))) {
+    std::cerr << "--groups-min M must not exceed the number of bodies (M = " << o.groups_min << ")." << std::endl;
     std::exit(EXIT_FAILURE);
   }
   if (o.block_levels_given && !(o.block_eta > 0.0)) {

@@ -5,6 +5,10 @@
 //   neighbours.bin: u32 nbodies, u32 steps, u32 sizeof(T), u32 dim, then per save_all phi T[n], nn u32[n], nnd2 T[n]
 // and, with --save-density K,
 //   density.bin:    u32 nbodies, u32 steps, u32 sizeof(T), u32 dim, u32 k, then per save_all rho T[n], x_dc T[dim], r_c T, rho_c T
+// and, with --save-groups B (--groups-min M),
+//   groups.bin:     u32 nbodies, u32 steps, u32 sizeof(T), u32 dim, f64 b, u32 min_members, then per save_all the u32[4] summary
+//                   (groups, catalogued groups c, largest size, its label), label u32[n], size u32[n], then c entries of
+//                   {u32 label, u32 size, T mass, T com[dim]}
 #pragma once
 #include <cstdint>
 #include <cstdlib>
@@ -22,7 +26,8 @@ class Saver {
  public:
   explicit Saver(Options const& o)
    : pos_(o.save_pos), energy_(o.save_energy), tree_energy_(o.tree_energy), quadrupole_(o.quadrupole), softening_(o.softening),
-     neighbours_(o.save_neighbours), density_k_(o.save_density), density_tree_(o.density_tree), theta_(o.theta), nbodies_(std::uint32_t(o.size)), nsteps_(std::uint32_t(o.steps)) {
+     neighbours_(o.save_neighbours), density_k_(o.save_density), density_tree_(o.density_tree), groups_(o.save_groups), groups_b_(o.groups_b),
+     groups_min_(std::uint32_t(o.groups_min)), theta_(o.theta), nbodies_(std::uint32_t(o.size)), nsteps_(std::uint32_t(o.steps)) {
     std::uint32_t const tsz = sizeof(T), dim = D;
     if (pos_) {
       pos_file_.open("positions.bin", std::ios::out | std::ios::binary);
@@ -52,9 +57,18 @@ class Saver {
       put(density_file_, dim);
       put(density_file_, k);
     }
+    if (groups_) {
+      groups_file_.open("groups.bin", std::ios::out | std::ios::binary);
+      put(groups_file_, nbodies_);
+      put(groups_file_, nsteps_);
+      put(groups_file_, tsz);
+      put(groups_file_, dim);
+      put(groups_file_, groups_b_);
+      put(groups_file_, groups_min_);
+    }
   }
 
-  bool active() const { return pos_ || energy_ || neighbours_ || density_k_ != 0; }
+  bool active() const { return pos_ || energy_ || neighbours_ || density_k_ != 0 || groups_; }
 
   // one frame; the device copy is authoritative, so positions are pulled first
   void save_all(System<T, D>& sys, Device<T, D>& dev) {
@@ -79,6 +93,19 @@ class Saver {
       density_file_.write(reinterpret_cast<char const*>(rho_.data()), std::streamsize(rho_.size() * sizeof(T)));
       density_file_.write(reinterpret_cast<char const*>(summary), std::streamsize(sizeof summary));
     }
+    if (groups_) {
+      std::uint32_t summary[4];
+      dev.groups(groups_b_, groups_min_, summary, label_, size_, cat_label_, cat_size_, cat_mass_, cat_com_);
+      groups_file_.write(reinterpret_cast<char const*>(summary), std::streamsize(sizeof summary));
+      groups_file_.write(reinterpret_cast<char const*>(label_.data()), std::streamsize(label_.size() * sizeof(std::uint32_t)));
+      groups_file_.write(reinterpret_cast<char const*>(size_.data()), std::streamsize(size_.size() * sizeof(std::uint32_t)));
+      for (std::size_t e = 0; e < cat_label_.size(); ++e) {
+        put(groups_file_, cat_label_[e]);
+        put(groups_file_, cat_size_[e]);
+        put(groups_file_, cat_mass_[e]);
+        groups_file_.write(reinterpret_cast<char const*>(&cat_com_[e * D]), std::streamsize(sizeof(T) * D));
+      }
+    }
   }
 
  private:
@@ -92,11 +119,15 @@ class Saver {
   bool neighbours_;                // --save-neighbours: phi, nn, nnd2 of every recorded frame, softening_ the potential's length
   int density_k_;                  // --save-density K: rho and the density-centre summary of every recorded frame; 0: off
   bool density_tree_;              // --density-tree: by the tree-pruned method (the same bytes)
+  bool groups_;                    // --save-groups B: the friends-of-friends groups of every recorded frame
+  double groups_b_;                // ... its linking length
+  std::uint32_t groups_min_;       // --groups-min M: the smallest group the catalogue lists
   double theta_;
   std::uint32_t nbodies_, nsteps_;
-  std::ofstream pos_file_, energy_file_, neighbours_file_, density_file_;
+  std::ofstream pos_file_, energy_file_, neighbours_file_, density_file_, groups_file_;
   std::vector<T> phi_, nnd2_, rho_;
-  std::vector<std::uint32_t> nn_;
+  std::vector<std::uint32_t> nn_, label_, size_, cat_label_, cat_size_;
+  std::vector<T> cat_mass_, cat_com_;
 };
 
 }  // namespace nb
