@@ -750,6 +750,11 @@ int  nbody_ctx_set_shard(nbody_ctx* ctx, uint32_t first, uint32_t count);
 /* What K1 will launch for this view, e.g. "all_pairs_force_sgpr_kernel<double,3,R=2,JS=8> tile=512 pair=far3/near2"
  * (bench.py stamps its profiles with it). */
 int  nbody_all_pairs_describe(const nbody_state* s, char* out, size_t len);
+/* What K2 (nbody_all_pairs_collapsed_force) will launch for this state: the kernel and its launch shape on one line, e.g.
+ * "all_pairs_collapsed_stream_kernel<8> hand float 3 padded=33792 nbatches=66 bpc=4 chunks=17" (float: the streamed form; bpc =
+ * batches per source chunk) or "all_pairs_collapsed_kernel<double,3,NT=8,KS=8,NB=1> tile=1024 iblocks=129 ntiles=33 tpb=2
+ * ysplit=17" (double: the tile form; tpb = source tiles per block row).  Host arithmetic only: no stream, no GPU work. */
+int  nbody_all_pairs_collapsed_describe(const nbody_state* s, char* out, size_t len);
 /* Which per-pair rounding form K1 (sz >= 32768) takes for this state — a property of ALL sz positions, the same on every rank
  * and for every shard window: *sparse_out = 1 when the volume (area in 2D; through *volume_out if not NULL) of the uniformly
  * filled box that has the positions' variances, prod_k sqrt(12 var_k), is at least 1.7e5 (6.4e4 in 2D); pairs at r^2 >= 4 then

@@ -52,7 +52,7 @@ ABI_SYMBOLS = [
     "nbody_bvh_create_on", "nbody_octree_create_on", "nbody_octree_set_walk", "nbody_octree_set_build", "nbody_octree_set_step_budget", "nbody_bvh_set_launch_order",
     "nbody_destroy", "nbody_upload", "nbody_download", "nbody_ctx_state", "nbody_ctx_stream", "nbody_stream_sync",
     "nbody_graph_begin", "nbody_graph_end", "nbody_graph_launch", "nbody_graph_destroy",
-    "nbody_ctx_configure_all_pairs", "nbody_ctx_set_shard", "nbody_all_pairs_describe",
+    "nbody_ctx_configure_all_pairs", "nbody_ctx_set_shard", "nbody_all_pairs_describe", "nbody_all_pairs_collapsed_describe",
     "nbody_comm_get_unique_id", "nbody_comm_create", "nbody_comm_create_all", "nbody_comm_destroy", "nbody_comm_world",
     "nbody_comm_rank", "nbody_comm_rccl_version", "nbody_shard_range", "nbody_comm_group_begin", "nbody_comm_group_end",
     "nbody_allgather_positions", "nbody_bvh_opening_thresholds", "nbody_all_pairs_pair_rule", "nbody_all_pairs_status",
@@ -216,6 +216,14 @@ def describe_all_pairs(st):
     """The K1 launch the library will make for this view (kernel template arguments, tile, chunks, pair math)."""
     buf = C.create_string_buffer(256)
     _check(lib().nbody_all_pairs_describe(C.byref(st), buf, C.c_size_t(256)))
+    return buf.value.decode()
+
+
+def describe_all_pairs_collapsed(st):
+    """The K2 launch the library will make for this state (kernel, and padded / nbatches / bpc / chunks of the streamed form or
+    iblocks / ntiles / tpb / ysplit of the tile form).  Host arithmetic only: no GPU needed."""
+    buf = C.create_string_buffer(256)
+    _check(lib().nbody_all_pairs_collapsed_describe(C.byref(st), buf, C.c_size_t(256)))
     return buf.value.decode()
 
 

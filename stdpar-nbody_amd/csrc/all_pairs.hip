@@ -1632,86 +1632,62 @@ __global__ __launch_bounds__(kBlock) void all_pairs_collapsed_stream_cxx_kernel(
   }
 }
 
+// K2's launch as a function of (T, D, sz) and — in -DNBODY_EXPERIMENTS builds — of the two switches the dispatch reads: everything
+// the launches below take from here and nothing else, and what nbody_all_pairs_collapsed_describe prints (the pattern of k1_plan).
+//   form: 20 = float 3D streamed with the hand-scheduled pair, 8 records per lane and batch (21: 4); 22 / 23 / 24 = the streamed
+//   compiler-scheduled kernel with 8 / 4 / 2 records per lane and batch (never fewer than one pair_batch call: 4 in float); any
+//   other value names a tile shape (NT, KS, NB), see below.  What ships: float 3D 20, float 2D 23, double the tile shape 5.
+struct k2_plan {
+  bool stream = false, hand = false;
+  // streamed form: records per lane and batch, the padded record count, its batches of 64 * ks, source chunks (grid.y) and batches
+  // per chunk (even: the kernel takes two per trip)
+  int ks = 0;
+  uint32_t padded = 0, nbatches = 0, chunks = 0, bpc = 0, groups = 0;
+  // tile form: blocks of 256 targets (grid.x), source tiles of kColTileJ, block rows (grid.y) of tpb tiles each
+  int nt = 0, nb = 0;  // with ks: the kernel's (NT, KS, NB)
+  uint32_t iblocks = 0, ntiles = 0, ysplit = 0, tpb = 0;
+};
+
 template <typename T, int D>
-static int collapsed_stream_launch(const nbody_state* s, hipStream_t st, int form, uint32_t want_chunks) {
-  // form: 20 = float 3D with the hand-scheduled pair, 8 records per lane and batch (21: 4); 22 / 23 / 24 = the compiler-scheduled
-  // kernel with 8 / 4 / 2 records per lane and batch
-  using rec_t = src_rec<T, D>;
-  constexpr bool kHand = sizeof(T) == 4 && D == 3;
-  constexpr int NT     = sizeof(T) == 4 ? 16 : 8;
-  constexpr int U      = 64 / int(sizeof(rec_t));
-  int ks = form == 20 || form == 22 ? 8 : (form == 24 ? 2 : 4);
-  if (ks < U) ks = U;
-  const uint32_t pair_of_batches = 2u * 64u * uint32_t(ks);  // at most 1024 records: what ap_scratch_reserve pads a context's buffer to
-  const uint32_t padded = (s->sz + pair_of_batches - 1) / pair_of_batches * pair_of_batches;
-  void* q = nullptr;
-  if (int r = ap_scratch_get(st, 0, sizeof(rec_t) * size_t(padded), &q)) return r;
-  rec_t* packed        = static_cast<rec_t*>(q);
-  const uint64_t nelem = uint64_t(s->sz) * D;
-  const uint64_t work  = nelem > padded ? nelem : padded;
-  hipLaunchKernelGGL((collapsed_reset_pack_kernel<T, D>), dim3((work + kBlock - 1) / kBlock), dim3(kBlock), 0, st,
-                     static_cast<T*>(s->a), static_cast<const T*>(s->ao), nelem, static_cast<const T*>(s->m),
-                     static_cast<const T*>(s->x), packed, s->sz, padded);
-  NB_HIP(hipGetLastError());
-  const uint32_t groups   = (s->sz + NT - 1) / NT;
-  const uint32_t blocks   = (groups + kWaves - 1) / kWaves;
-  const uint32_t nbatches = padded / uint32_t(64 * ks);
-  // chunks: enough waves for >= 16 rounds of the chip's 4096 wave slots where the system allows, whole batches per chunk
-  uint32_t chunks = want_chunks ? want_chunks : (16u * 4096u + groups - 1) / groups;
-  chunks          = std::max(1u, std::min({chunks, nbatches, 65535u}));
-  uint32_t bpc = (nbatches + chunks - 1) / chunks;
-  bpc += bpc & 1u;  // an even number of batches per chunk (nbatches is even)
-  chunks = (nbatches + bpc - 1) / bpc;
-  const dim3 grid(blocks, chunks), block(kBlock);
-  const T* x = static_cast<const T*>(s->x);
-  T* a       = static_cast<T*>(s->a);
-  const T c  = static_cast<T>(s->c);
-  if constexpr (kHand) {
-    if (form == 20) hipLaunchKernelGGL((all_pairs_collapsed_stream_kernel<8>), grid, block, 0, st, packed, x, a, c, s->sz, bpc, nbatches);
-    if (form == 21) hipLaunchKernelGGL((all_pairs_collapsed_stream_kernel<4>), grid, block, 0, st, packed, x, a, c, s->sz, bpc, nbatches);
-  }
-  if (form >= 22 || !kHand) {
-    if (ks == 8) hipLaunchKernelGGL((all_pairs_collapsed_stream_cxx_kernel<T, D, 8>), grid, block, 0, st, packed, x, a, c, s->sz, bpc, nbatches);
-    else if (ks == 4) hipLaunchKernelGGL((all_pairs_collapsed_stream_cxx_kernel<T, D, 4>), grid, block, 0, st, packed, x, a, c, s->sz, bpc, nbatches);
-    else hipLaunchKernelGGL((all_pairs_collapsed_stream_cxx_kernel<T, D, (U <= 2 ? 2 : 4)>), grid, block, 0, st, packed, x, a, c, s->sz, bpc, nbatches);
-  }
-  NB_HIP(hipGetLastError());
-  return NBODY_OK;
+constexpr int k2_shipped_form() {
+  return sizeof(T) == 4 ? (D == 3 ? 20 : 23) : 5;
 }
 
 template <typename T, int D>
-static int collapsed_dispatch(const nbody_state* s, hipStream_t st) {
-  NB_ARG(s->first == 0 && s->count == s->sz, "all-pairs-collapsed is single-GPU: needs first=0, count=sz");
-  if (s->sz == 0) return NBODY_OK;
-  {
-    // float: the streamed form — 3D (config 3) with the hand-scheduled pair, 2D with the compiled one, 4 records per lane and batch
-    // (N = 10^4 2D: 0.043 ms against the tile form's 0.060, profiles/r06/k2_streamed_form_2.txt); double: the tile form below.
-    // Experiments select the others (tools/time_collapsed.py).
-    int form        = sizeof(T) == 4 ? (D == 3 ? 20 : 23) : -1;
-    uint32_t chunks = 0;
-    if (const char* e = experiment_env("NBODY_K2_CFG")) form = atoi(e);  // -DNBODY_EXPERIMENTS builds only
-    if (const char* e = experiment_env("NBODY_K2_CHUNKS")) chunks = uint32_t(atoi(e));
-    // (float only: in double the per-batch near-pair branch of pair_batch under the full unroll over targets x sources makes hipcc keep
-    // every chain's temporaries alive — 264 ... 512 VGPRs and scratch for <double, 3, 2 ... 8> —; double keeps the tile form below)
-    if constexpr (sizeof(T) == 4) {
-      if (form >= 22 && form <= 24) return collapsed_stream_launch<T, D>(s, st, form, chunks);
-      if constexpr (D == 3)
-        if (form == 20 || form == 21) return collapsed_stream_launch<T, D>(s, st, form, chunks);
-    }
+static void plan_collapsed(uint32_t sz, int form, uint32_t want_chunks, k2_plan* out) {
+  k2_plan p;
+  // (float only: in double the per-batch near-pair branch of pair_batch under the full unroll over targets x sources makes hipcc keep
+  // every chain's temporaries alive — 264 ... 512 VGPRs and scratch for <double, 3, 2 ... 8> —; double keeps the tile form)
+  p.stream = sizeof(T) == 4 && ((form >= 22 && form <= 24) || (D == 3 && (form == 20 || form == 21)));
+  if (p.stream) {
+    using rec_t      = src_rec<T, D>;
+    constexpr int NT = sizeof(T) == 4 ? 16 : 8;
+    constexpr int U  = 64 / int(sizeof(rec_t));
+    p.hand           = form == 20 || form == 21;
+    p.ks             = form == 20 || form == 22 ? 8 : (form == 24 ? 2 : 4);
+    if (p.ks < U) p.ks = U;
+    const uint32_t pair_of_batches = 2u * 64u * uint32_t(p.ks);  // at most 1024 records: what ap_scratch_reserve pads a context's buffer to
+    p.padded   = (sz + pair_of_batches - 1) / pair_of_batches * pair_of_batches;
+    p.groups   = (sz + NT - 1) / NT;
+    p.nbatches = p.padded / uint32_t(64 * p.ks);
+    // chunks: enough waves for >= 16 rounds of the chip's 4096 wave slots where the system allows, whole batches per chunk
+    uint32_t chunks = want_chunks ? want_chunks : (p.groups ? (16u * 4096u + p.groups - 1) / p.groups : 1u);
+    chunks          = std::max(1u, std::min({chunks, p.nbatches, 65535u}));
+    p.bpc           = (p.nbatches + chunks - 1) / chunks;
+    p.bpc += p.bpc & 1u;  // an even number of batches per chunk (nbatches is even)
+    p.chunks = p.bpc ? (p.nbatches + p.bpc - 1) / p.bpc : 0;
+    *out     = p;
+    return;
   }
-  uint64_t nelem = uint64_t(s->sz) * D;
-  hipLaunchKernelGGL((collapsed_reset_kernel<T, D>), dim3((nelem + kBlock - 1) / kBlock), dim3(kBlock), 0, st,
-                     static_cast<T*>(s->a), static_cast<const T*>(s->ao), nelem);
-  NB_HIP(hipGetLastError());
-  uint32_t iblocks = (s->sz + kWaves * 64 - 1) / (kWaves * 64);
-  uint32_t ntiles  = (s->sz + kColTileJ<T> - 1) / kColTileJ<T>;
+  p.iblocks = (sz + kWaves * 64 - 1) / (kWaves * 64);
+  p.ntiles  = (sz + kColTileJ<T> - 1) / kColTileJ<T>;
   // aim for >= 4096 blocks (16 per CU) while keeping >= 1 tile per block
-  uint32_t ysplit = (4096 + iblocks - 1) / iblocks;
-  if (ysplit > ntiles) ysplit = ntiles;
+  uint32_t ysplit = p.iblocks ? (4096 + p.iblocks - 1) / p.iblocks : 1;
+  if (ysplit > p.ntiles) ysplit = p.ntiles;
   if (ysplit < 1) ysplit = 1;
   if (ysplit > 65535) ysplit = 65535;
-  uint32_t tpb = (ntiles + ysplit - 1) / ysplit;
-  ysplit       = (ntiles + tpb - 1) / tpb;
+  p.tpb    = (p.ntiles + ysplit - 1) / ysplit;
+  p.ysplit = p.tpb ? (p.ntiles + p.tpb - 1) / p.tpb : 1;
   // Measured at config 3 (f32, N = 262 144) and on the reference's matrix size (f64, N = 10^5), gpurun_out/r02/k2_times*.txt:
   // every variant with ONE pair chain per lane in flight runs at 24.05 ms (36.3 % of the FP32 vector peak) whatever NT, KS
   // and the occupancy (3 to 6 waves per SIMD); every variant that interleaves 2 or 4 chains runs at 28.7 ms — the interleaved
@@ -1722,34 +1698,138 @@ static int collapsed_dispatch(const nbody_state* s, hipStream_t st) {
   // f64 (N = 10^5, ms): with the guarded rsq+rcp weight everywhere (8, 4, 4) was
   // the fastest at 7.47; with the reciprocal-free weight and a guarded second pass only for the blocks that held a near pair
   // (see the kernel) (8, 8, 1) 6.79, (8, 4, 1) 6.95, (8, 4, 2) 7.00, (8, 2, 2) 7.01, (8, 2, 1) 7.26, (16, 8, 1) 8.03, (8, 4, 4) 9.96.
-  int cfg = sizeof(T) == 4 ? 0 : 5;
-  if (const char* e = experiment_env("NBODY_K2_CFG")) cfg = atoi(e) >= 20 ? cfg : atoi(e);  // -DNBODY_EXPERIMENTS builds only (tools/time_collapsed.py)
-#define NB_K2(NT, KS, NBC)                                                                                              \
-  hipLaunchKernelGGL((all_pairs_collapsed_kernel<T, D, NT, KS, NBC>), dim3(iblocks, ysplit), dim3(kBlock), 0, st,        \
-                     static_cast<const T*>(s->m), static_cast<const T*>(s->x), static_cast<T*>(s->a), static_cast<T>(s->c), \
-                     s->sz, tpb)
-  if constexpr (sizeof(T) == 4 && D == 3) {  // the pair scheduled by hand (k2_pair_step): what ships for float 3D (config 3)
-    switch (cfg) {
-      case 0: NB_K2(16, 8, 0); NB_HIP(hipGetLastError()); return NBODY_OK;
-      case 10: NB_K2(16, 4, 0); NB_HIP(hipGetLastError()); return NBODY_OK;
-      case 11: NB_K2(8, 8, 0); NB_HIP(hipGetLastError()); return NBODY_OK;
-      case 12: NB_K2(8, 4, 0); NB_HIP(hipGetLastError()); return NBODY_OK;
-      case 8: cfg = 0; break;  // experiments: the compiler-scheduled (16, 8, 1), the cross-check of the hand-scheduled form
-      default: break;
-    }
+  const int cfg = form >= 20 ? (sizeof(T) == 4 ? 0 : 5) : form;  // a streamed form this (T, D) does not have: the tile form as shipped
+  auto shape    = [&](int nt, int ks, int nb) { p.nt = nt, p.ks = ks, p.nb = nb; };
+  shape(16, 8, 4);
+  if (sizeof(T) == 4 && D == 3 && (cfg == 0 || (cfg >= 10 && cfg <= 12))) {
+    // NB = 0, the pair scheduled by hand (k2_pair_step): the tile form of float 3D
+    if (cfg == 0) shape(16, 8, 0);
+    if (cfg == 10) shape(16, 4, 0);
+    if (cfg == 11) shape(8, 8, 0);
+    if (cfg == 12) shape(8, 4, 0);
+  } else if (cfg == 0 || (sizeof(T) == 4 && D == 3 && cfg == 8)) {
+    shape(16, 8, 1);  // (float 3D, 8: the compiler-scheduled cross-check of the hand-scheduled form)
+  } else {
+    if (cfg == 1) shape(8, 4, 4);
+    if (cfg == 2) shape(8, 4, 1);
+    if (cfg == 4) shape(8, 4, 2);
+    if (cfg == 5) shape(8, 8, 1);
+    if (cfg == 6) shape(8, 2, 1);
+    if (cfg == 7) shape(8, 2, 2);
   }
-  switch (cfg) {
-    case 0: NB_K2(16, 8, 1); break;
-    case 1: NB_K2(8, 4, 4); break;
-    case 2: NB_K2(8, 4, 1); break;
-    case 4: NB_K2(8, 4, 2); break;
-    case 5: NB_K2(8, 8, 1); break;
-    case 6: NB_K2(8, 2, 1); break;
-    case 7: NB_K2(8, 2, 2); break;
-    default: NB_K2(16, 8, 4); break;
-  }
-#undef NB_K2
+  *out = p;
+}
+
+template <typename T, int D>
+static int collapsed_stream_launch(const nbody_state* s, hipStream_t st, const k2_plan& p) {
+  using rec_t = src_rec<T, D>;
+  void* q     = nullptr;
+  if (int r = ap_scratch_get(st, 0, sizeof(rec_t) * size_t(p.padded), &q)) return r;
+  rec_t* packed        = static_cast<rec_t*>(q);
+  const uint64_t nelem = uint64_t(s->sz) * D;
+  const uint64_t work  = nelem > p.padded ? nelem : p.padded;
+  hipLaunchKernelGGL((collapsed_reset_pack_kernel<T, D>), dim3((work + kBlock - 1) / kBlock), dim3(kBlock), 0, st,
+                     static_cast<T*>(s->a), static_cast<const T*>(s->ao), nelem, static_cast<const T*>(s->m),
+                     static_cast<const T*>(s->x), packed, s->sz, p.padded);
   NB_HIP(hipGetLastError());
+  const uint32_t blocks = (p.groups + kWaves - 1) / kWaves;
+  const dim3 grid(blocks, p.chunks), block(kBlock);
+  const T* x = static_cast<const T*>(s->x);
+  T* a       = static_cast<T*>(s->a);
+  const T c  = static_cast<T>(s->c);
+  if constexpr (sizeof(T) == 4 && D == 3) {
+    if (p.hand && p.ks == 8) hipLaunchKernelGGL((all_pairs_collapsed_stream_kernel<8>), grid, block, 0, st, packed, x, a, c, s->sz, p.bpc, p.nbatches);
+    if (p.hand && p.ks == 4) hipLaunchKernelGGL((all_pairs_collapsed_stream_kernel<4>), grid, block, 0, st, packed, x, a, c, s->sz, p.bpc, p.nbatches);
+  }
+  if (!p.hand) {
+    constexpr int U = 64 / int(sizeof(rec_t));
+    if (p.ks == 8) hipLaunchKernelGGL((all_pairs_collapsed_stream_cxx_kernel<T, D, 8>), grid, block, 0, st, packed, x, a, c, s->sz, p.bpc, p.nbatches);
+    else if (p.ks == 4) hipLaunchKernelGGL((all_pairs_collapsed_stream_cxx_kernel<T, D, 4>), grid, block, 0, st, packed, x, a, c, s->sz, p.bpc, p.nbatches);
+    else hipLaunchKernelGGL((all_pairs_collapsed_stream_cxx_kernel<T, D, (U <= 2 ? 2 : 4)>), grid, block, 0, st, packed, x, a, c, s->sz, p.bpc, p.nbatches);
+  }
+  NB_HIP(hipGetLastError());
+  return NBODY_OK;
+}
+
+template <typename T, int D>
+static int collapsed_tile_launch(const nbody_state* s, hipStream_t st, const k2_plan& p) {
+  uint64_t nelem = uint64_t(s->sz) * D;
+  hipLaunchKernelGGL((collapsed_reset_kernel<T, D>), dim3((nelem + kBlock - 1) / kBlock), dim3(kBlock), 0, st,
+                     static_cast<T*>(s->a), static_cast<const T*>(s->ao), nelem);
+  NB_HIP(hipGetLastError());
+  bool found = false;
+#define NB_K2(NT, KS, NBC)                                                                                                 \
+  if (!found && p.nt == NT && p.ks == KS && p.nb == NBC) {                                                                 \
+    found = true;                                                                                                          \
+    hipLaunchKernelGGL((all_pairs_collapsed_kernel<T, D, NT, KS, NBC>), dim3(p.iblocks, p.ysplit), dim3(kBlock), 0, st,     \
+                       static_cast<const T*>(s->m), static_cast<const T*>(s->x), static_cast<T*>(s->a), static_cast<T>(s->c), \
+                       s->sz, p.tpb);                                                                                      \
+  }
+  if constexpr (sizeof(T) == 4 && D == 3) {  // the pair scheduled by hand (k2_pair_step)
+    NB_K2(16, 8, 0)
+    NB_K2(16, 4, 0)
+    NB_K2(8, 8, 0)
+    NB_K2(8, 4, 0)
+  }
+  NB_K2(16, 8, 1)
+  NB_K2(8, 4, 4)
+  NB_K2(8, 4, 1)
+  NB_K2(8, 4, 2)
+  NB_K2(8, 8, 1)
+  NB_K2(8, 2, 1)
+  NB_K2(8, 2, 2)
+  NB_K2(16, 8, 4)
+#undef NB_K2
+  if (!found) {
+    set_error("all-pairs-collapsed: no kernel for the tile shape (%d, %d, %d)", p.nt, p.ks, p.nb);
+    return NBODY_ERR_ARG;
+  }
+  NB_HIP(hipGetLastError());
+  return NBODY_OK;
+}
+
+// The plan of this build for a state: the shipped form, or in -DNBODY_EXPERIMENTS builds what the two switches select
+// (tools/time_collapsed.py).  float: the streamed form — 3D (config 3) with the hand-scheduled pair, 2D with the compiled one, 4 records
+// per lane and batch (N = 10^4 2D: 0.043 ms against the tile form's 0.060, profiles/r06/k2_streamed_form_2.txt); double: the tile form.
+template <typename T, int D>
+static k2_plan collapsed_plan_of(const nbody_state* s) {
+  int form        = k2_shipped_form<T, D>();
+  uint32_t chunks = 0;
+  if (const char* e = experiment_env("NBODY_K2_CFG")) form = atoi(e);  // -DNBODY_EXPERIMENTS builds only
+  if (const char* e = experiment_env("NBODY_K2_CHUNKS")) chunks = uint32_t(atoi(e));
+  k2_plan p;
+  plan_collapsed<T, D>(s->sz, form, chunks, &p);
+  return p;
+}
+
+template <typename T, int D>
+static int collapsed_dispatch(const nbody_state* s, hipStream_t st) {
+  NB_ARG(s->first == 0 && s->count == s->sz, "all-pairs-collapsed is single-GPU: needs first=0, count=sz");
+  if (s->sz == 0) return NBODY_OK;
+  const k2_plan p = collapsed_plan_of<T, D>(s);
+  if constexpr (sizeof(T) == 4)
+    if (p.stream) return collapsed_stream_launch<T, D>(s, st, p);
+  return collapsed_tile_launch<T, D>(s, st, p);
+}
+
+template <typename T, int D>
+static int collapsed_describe(const nbody_state* s, char* out, size_t len) {
+  NB_ARG(s->first == 0 && s->count == s->sz, "all-pairs-collapsed is single-GPU: needs first=0, count=sz");
+  const char* t = sizeof(T) == 8 ? "double" : "float";
+  if (s->sz == 0) {
+    snprintf(out, len, "all-pairs-collapsed %s %d: no bodies, no launch", t, D);
+    return NBODY_OK;
+  }
+  const k2_plan p = collapsed_plan_of<T, D>(s);
+  if (p.stream && p.hand)
+    snprintf(out, len, "all_pairs_collapsed_stream_kernel<%d> hand %s %d padded=%u nbatches=%u bpc=%u chunks=%u", p.ks, t, D, p.padded,
+             p.nbatches, p.bpc, p.chunks);
+  else if (p.stream)
+    snprintf(out, len, "all_pairs_collapsed_stream_cxx_kernel<%s,%d,%d> compiled %s %d padded=%u nbatches=%u bpc=%u chunks=%u", t, D, p.ks, t,
+             D, p.padded, p.nbatches, p.bpc, p.chunks);
+  else
+    snprintf(out, len, "all_pairs_collapsed_kernel<%s,%d,NT=%d,KS=%d,NB=%d> tile=%d iblocks=%u ntiles=%u tpb=%u ysplit=%u", t, D, p.nt, p.ks,
+             p.nb, kColTileJ<T>, p.iblocks, p.ntiles, p.tpb, p.ysplit);
   return NBODY_OK;
 }
 
@@ -1898,6 +1978,15 @@ extern "C" int nbody_all_pairs_collapsed_force(const nbody_state* s, void* strea
   return dispatch(s->dtype, s->dim, [&](auto tg) {
     using TG = decltype(tg);
     return collapsed_dispatch<typename TG::type, TG::dim>(s, as_stream(stream));
+  });
+}
+
+extern "C" int nbody_all_pairs_collapsed_describe(const nbody_state* s, char* out, size_t len) {
+  NB_ARG(out != nullptr && len > 0, "out is NULL");
+  if (int r = check_state(s)) return r;
+  return dispatch(s->dtype, s->dim, [&](auto tg) {
+    using TG = decltype(tg);
+    return collapsed_describe<typename TG::type, TG::dim>(s, out, len);
   });
 }
 

@@ -384,7 +384,8 @@ def test_edge_cases(nb):
 @pytest.mark.parametrize("dtype", [1, 0])
 @pytest.mark.parametrize("dim", [3, 2])
 def test_collapsed_force_vs_oracle(nb, oracle, dtype, dim):
-    """Intended semantics (all D components, 64-bit pair space) == all-pairs up to rounding; a - ao reset included."""
+    """Intended semantics (all D components, 64-bit pair space) == all-pairs up to rounding; a - ao reset included.
+    (A global max-norm check; every target against the wide reference, at every launch shape: tests/test_gpu_collapsed_wide.py.)"""
     for wl, n in (("uniform", 2), ("uniform", 65), ("galaxy", 1000), ("uniform", 4099)):
         ref = oracle.build_model(dtype, dim, wl, n)
         hs = nb.build_model(dtype, dim, wl, n)
@@ -404,7 +405,8 @@ def test_collapsed_streamed_form_at_its_boundaries(nb, oracle, dim):
     batches of 512 (3D) / 256 (2D) per wave, two batches per trip, the record array padded with zero-mass records to whole pairs
     of batches): sizes on both sides of every boundary of that shape — one body, a group of 16, a wave's 64 lanes, one and two
     batches, the padding — with a coincident pair, a pair closer than the float epsilon's cube root and the `a - ao` reset,
-    against the oracle's all-pairs sums.  3D runs the hand-scheduled pair, 2D the compiled one."""
+    against the oracle's all-pairs sums.  3D runs the hand-scheduled pair, 2D the compiled one.  (Every size here is one trip per
+    chunk and the norm is global; the shapes with several trips per chunk and the per-body check: tests/test_gpu_collapsed_wide.py.)"""
     for n in (1, 2, 15, 16, 17, 63, 64, 65, 255, 256, 257, 511, 512, 513, 1023, 1024, 1025, 2047, 2049, 5000, 16385):
         hs = nb.build_model(0, dim, "uniform", n)
         if n >= 17:
