@@ -16,6 +16,7 @@
 // against the oracle; tree COMs/widths are bit-exact too (FP contraction is off in the build and in
 // the opening test), only the accumulated force uses the fast pair math of common.hpp.
 #include "common.hpp"
+#include "bvh_plan.hpp"
 #include "radix_sort.hpp"
 #include "to_sgpr.hpp"
 
@@ -63,11 +64,7 @@ struct nbody_bvh {
   int traversal   = 0;  // 0 = auto (wave-cooperative when nlevels <= 26), 1 = per-lane, 2 = wave-cooperative
   int launch_order = 0; // sweep: 0 = work items (cut groups first), 1 = one block per group in index order
   double theta      = 0.5;   // the opening angle the next build writes thresholds for (the last one a traversal was asked for)
-  double th2_built  = -1.0;  // theta^2 (in T) of the thresholds the records hold; -1: none.  What the HOST believes after its
-                             // own eager calls; a recorded step changes the records whenever it is replayed, so:
-  bool ever_recorded = false;            // a build or traversal of this tree has been recorded: eager traversals always rethreshold
-  unsigned long long rec_id = 0;         // the capture whose recorded build / traversal last wrote the thresholds ...
-  double rec_th2            = -1.0;      // ... and the theta^2 it wrote them for (valid inside that capture only)
+  nbody::k9_thresholds thresholds;  // what the records' opening thresholds hold, and who wrote them
   bool counters_on = false, have_bbox = false, sorted = false, built = false;
   nbody::device_buffers mem;  // owns every buffer above, counters (nbody_bvh_enable_counters) included
 };
@@ -597,8 +594,6 @@ __global__ __launch_bounds__(64) void bvh_force_kernel(const tree_rec<T>* __rest
 // (profiles/r04/tiny_trees_kernel_stats.txt): 75 -> 53 us in float — the walk is a chain of dependent record fetches, but the
 // decision's own arithmetic is most of an iteration — and 128 -> 180 us in double (64-byte records: the lanes' four 16-byte
 // reads land on 4 of the 16 bank groups), so double keeps the walk over global memory.
-constexpr int kTreeLdsThreads    = 256;
-constexpr uint32_t kTreeLdsBytes = 144u << 10;  // of the CU's 160 KB
 template <typename T, int D, bool COUNT>
 __global__ __launch_bounds__(kTreeLdsThreads) void bvh_force_lds_kernel(const tree_rec<T>* __restrict__ node, uint32_t nrec, T* __restrict__ a,
                                                                         const T* __restrict__ x, T c, uint32_t sz, uint32_t first,
@@ -655,17 +650,7 @@ __global__ __launch_bounds__(kTreeLdsThreads) void bvh_force_lds_kernel(const tr
 //   * lists those items first, highest jump first; every other group follows as one item in index order.
 // item = group | first lane << 20 | last lane << 26.  Nothing but grouping and start order changes: a body's result depends
 // on the tree and that body alone.
-constexpr uint32_t kOrderMax = 8192;  // groups per XCD range one block handles (N <= 4.2M bodies); more: plain index order
-constexpr uint32_t kSplitMax = 2048;  // groups per XCD range that may be cut
-__host__ __device__ __forceinline__ void xcd_range(uint32_t xcd, uint32_t nblocks, uint32_t* start, uint32_t* len) {
-  const uint32_t q = nblocks / 8u, r = nblocks % 8u;
-  *start = xcd < r ? xcd * (q + 1u) : r * (q + 1u) + (xcd - r) * q;
-  *len   = q + (xcd < r ? 1u : 0u);
-}
-__host__ __device__ __forceinline__ uint32_t split_budget(uint32_t len, uint32_t den = 16u) {
-  const uint32_t b = len / den;
-  return len > kOrderMax ? 0u : (b < kSplitMax ? b : kSplitMax);
-}
+// (kOrderMax, kSplitMax, xcd_range, split_budget: bvh_plan.hpp — the host sizes the lists with them)
 __device__ __forceinline__ uint32_t pack_item(uint32_t group, uint32_t lo, uint32_t hi) { return group | (lo << 20) | (hi << 26); }
 
 // items of XCD x live at items[x * stride ...], nitems[x] of them; stride = longest range + its budget
@@ -750,7 +735,9 @@ __global__ __launch_bounds__(1024) void bvh_items_kernel(const uint64_t* __restr
 }
 
 #ifdef NBODY_EXPERIMENTS
-#include "experiments/bvh_forms.inc"  // traversal modes 3, 4, 6: measured forms that are not shipped
+#include "experiments/bvh_forms.inc"  // traversal modes 3, 4, 6: measured forms that are not shipped; the environment switches
+#else
+static k9_overrides k9_read_overrides() { return {}; }  // the shipped library reads no environment
 #endif
 
 // ------------------------------------------------------------------------------------------------
@@ -1005,13 +992,6 @@ __global__ __launch_bounds__(1024) void bvh_items_kernel(const uint64_t* __restr
   "s_waitcnt lgkmcnt(0)\n\t" /* a record requested past the end of the walk: it must land before the registers are reused */ \
   "s_mov_b64 exec, %[sv]"
 
-#ifdef NBODY_EXPERIMENTS
-// tools/k9_timeline.py: per work item of a sweep launch (start, end) in 100 MHz ticks and the item, three words per launch block
-__device__ unsigned long long* g_k9_timeline = nullptr;
-static unsigned long long* g_k9_timeline_host = nullptr;  // the same buffer, for nbody_exp_k9_timeline
-static size_t g_k9_timeline_words = 0;
-#endif
-
 template <typename T, int D, bool COUNT>
 __global__ __launch_bounds__(64) void bvh_force_sweep_isa_kernel(const tree_rec<T>* __restrict__ node, T* __restrict__ a,
                                                                  const T* __restrict__ x, T c, uint32_t sz, uint32_t first,
@@ -1028,7 +1008,7 @@ __global__ __launch_bounds__(64) void bvh_force_sweep_isa_kernel(const tree_rec<
     group   = it & 0xfffffu;
     lane_lo = (it >> 20) & 63u;
     lane_hi = it >> 26;
-  } else if (parts > 1u) {  // every group as `parts` equal lane ranges (small systems: see force_run)
+  } else if (parts > 1u) {  // every group as `parts` equal lane ranges (small systems: k9_parts, bvh_plan.hpp)
     lane_lo = (group % parts) * (64u / parts);
     lane_hi = lane_lo + 64u / parts - 1u;
     group /= parts;
@@ -1227,12 +1207,15 @@ static int build_run(nbody_bvh* t, const nbody_state* s, hipStream_t st) {
       l = -1;
     }
   }
-  if (const unsigned long long cap = capture_id(st)) {  // replayed at times the host does not see: th2_built says nothing any more
-    t->ever_recorded = true;
-    t->rec_id        = cap;
-    t->rec_th2       = double(th2);
-  }
-  t->th2_built = double(th2);
+  t->thresholds.written(capture_id(st), double(th2));
+  return NBODY_OK;
+}
+
+// One launch of a K9 form in the plan's shape: the plain or the counting instantiation, as the tree's counters say.
+template <typename K, typename... A>
+static int k9_launch(const nbody_bvh* t, K plain, K counting, const k9_plan& p, hipStream_t st, A... args) {
+  hipLaunchKernelGGL(t->counters_on ? counting : plain, dim3(p.grid), dim3(p.threads), p.lds_bytes, st, args...);
+  NB_HIP(hipGetLastError());
   return NBODY_OK;
 }
 
@@ -1241,159 +1224,57 @@ static int force_run(nbody_bvh* t, const nbody_state* s, double theta, hipStream
   if (s->count == 0) return NBODY_OK;
   const T th  = static_cast<T>(theta);
   const T th2 = th * th;  // src/bvh.h:252, in T
-  auto* node = static_cast<const tree_rec<T>*>(t->node);
-  t->theta   = theta;  // the next build writes the records' opening thresholds for this angle
-  // The sweep trusts the thresholds in the records.  The host knows what they hold only along its own eager calls: a recorded
-  // step rewrites them whenever it is replayed.  So a recorded traversal skips the rewrite only behind a build (or traversal) of
-  // the SAME capture for the same angle, and once anything of this tree has been recorded an eager traversal always rewrites.
+  t->theta    = theta;    // the next build writes the records' opening thresholds for this angle
+  // 1. the opening thresholds in the records, which the sweep trusts (k9_thresholds)
   const unsigned long long cap = capture_id(st);
-  const bool fresh = cap ? (t->rec_id == cap && t->rec_th2 == double(th2)) : (!t->ever_recorded && t->th2_built == double(th2));
-  if (!fresh) {
+  if (!t->thresholds.fresh(cap, double(th2))) {
     hipLaunchKernelGGL((rethreshold_kernel<T, D>), dim3((t->nnodes + kB - 1) / kB), dim3(kB), 0, st,
                        static_cast<tree_rec<T>*>(t->node), t->nnodes, th2);
     NB_HIP(hipGetLastError());
   }
-  if (cap) {
-    t->ever_recorded = true;
-    t->rec_id        = cap;
-    t->rec_th2       = double(th2);
+  t->thresholds.written(cap, double(th2));
+  // 2. the plan (bvh_plan.hpp): every launch below reads it and nothing else
+  k9_request rq;
+  rq.elem = sizeof(T), rq.nlevels = t->nlevels, rq.nnodes = t->nnodes, rq.count = s->count;
+  rq.traversal = t->traversal, rq.launch_order = t->launch_order, rq.sorted = t->sorted, rq.final_buf = t->final_buf;
+  rq.overrides = k9_read_overrides();
+  k9_plan p;
+  const char* refusal = nullptr;
+  if (int r = plan_bvh_force(rq, &p, &refusal)) {
+    set_error(refusal, t->nlevels);
+    return r;
   }
-  t->th2_built = double(th2);
-  // auto: the wave-cooperative sweep needs enough waves in flight to hide its serial chain.  Measured in the CLI's step loop on
-  // 256 CUs (ms per whole bvh step over the first 200 steps of the galaxy, sweep / per-lane): f64 (hand-scheduled sweep) 0.90 / 0.85
-  // at 4*10^4, 1.0 / 1.0 at 6*10^4, 1.1 / 1.15 at 8*10^4, 1.2 / 1.25 at 10^5, 1.3 / 1.5 at 1.3*10^5, 2.05 / 3.45 at 2.5*10^5, 3.45 / 7.1
-  // at 5*10^5; f32 0.90 / 0.65 at 6*10^4, 1.05 / 0.80 at 10^5, 1.25 / 1.15 at 1.6*10^5, 1.5 / 1.9 at 2.5*10^5, 4.45 / 10.6 at 10^6.  A system that has
-  // evolved favours the sweep further: escapers inflate the box, walks get 3x longer and the per-lane form's divergent
-  // gathers pay for every entry (10^5 bodies after 400-1000 steps: sweep 1.7-2.1 ms, per-lane 3.0-3.7 ms per traversal).
-  // f64 below 5*10^4: the first steps of the galaxy favour the per-lane form by 7 % (4*10^4) to 20 % (10^4), its evolved states the
-  // sweep by 25-40 % (whole 1000-step runs, sweep / per-lane: 0.86 / 0.91 s at 10^4, 0.99 / 1.07 at 2*10^4, 1.16 / 1.47 at 3*10^4)
-  // f64 with the finer work items of small systems (below): the sweep wins from the smallest sizes measured (10^4: 0.27 against 0.33 ms)
-  const uint32_t crossover = sizeof(T) == 8 ? 4096u : 180000u;
-  int traversal = t->traversal;
-  if (const char* e = experiment_env("NBODY_K9_MODE"); e && traversal == 0) traversal = atoi(e);  // -DNBODY_EXPERIMENTS builds only
-#ifdef NBODY_EXPERIMENTS
-  if (traversal == 6) {  // four 16-lane row sweeps per wave (experiment; no counters)
-    if (t->counters_on || t->nlevels > 26) {
-      set_error("traversal mode 6 (row sweeps) has no counters and needs nlevels <= 26");
-      return NBODY_ERR_ARG;
-    }
-    const uint32_t rblocks = (s->count + 63u) / 64u;
-    hipLaunchKernelGGL((bvh_force_row_kernel<T, D>), dim3(rblocks), dim3(64), 0, st, node, static_cast<T*>(s->a),
-                       static_cast<const T*>(s->x), static_cast<T>(s->c), s->sz, s->first, s->count, th2, t->nlevels);
+  // 3. the sweep's work items, from the sorted keys
+  if (p.items) {
+    hipLaunchKernelGGL(bvh_items_kernel, dim3(8), dim3(1024), 0, st, t->keys[1], s->first, s->count, t->order, t->order_n, p.groups,
+                       p.stride, p.split_den);
     NB_HIP(hipGetLastError());
-    return NBODY_OK;
   }
-#endif
-  const bool wave = traversal >= 2 || (traversal == 0 && t->nlevels <= 26 && s->count >= crossover);
-  if (wave && t->nlevels > 26) {
-    set_error("wave-cooperative traversal needs nlevels <= 26 (n <= 2^26), tree has %u levels", t->nlevels);
-    return NBODY_ERR_ARG;
-  }
-  // The sweep is the step program written out as ISA (bvh_force_sweep_isa_kernel: auto, 2, 5).  The -DNBODY_EXPERIMENTS build also
-  // has the compiler-scheduled step (3; with 2 bodies per lane: 4 — 128 bodies per wave, config 4 12.2 ms against 9.55) and the
-  // row sweeps (6).  All forms are bitwise identical.
-  const int bpl  = traversal == 4 ? 2 : 1;
-  [[maybe_unused]] const bool isa = wave && (traversal == 0 || traversal == 2 || traversal == 5);
-  const uint32_t per_block = wave ? 64u * uint32_t(bpl) : 64u;
-  const uint32_t blocks    = (s->count + per_block - 1) / per_block;
-#define NB_ARGS                                                                                                   \
-  dim3(blocks), dim3(64), 0, st, node, static_cast<T*>(s->a), static_cast<const T*>(s->x), static_cast<T>(s->c), s->sz, s->first, \
-   s->count, th2, t->nlevels, t->counters
-  const uint32_t *items = nullptr, *nitems = nullptr;
-  uint32_t stride = 0, wave_blocks = blocks, parts = 1;
-  const char* oe = experiment_env("NBODY_K9_ORDER");  // -DNBODY_EXPERIMENTS builds: 0 = one block per group in index order
-  const bool plain = t->launch_order != 0 || (oe && oe[0] == '0');
-  // Finer work items (profiles/r03/k9_parts.txt, ms per traversal of the initial galaxy, f64): every group swept as `parts` equal
-  // lane ranges side by side has shorter unions (16 Hilbert-adjacent walks: 5.7k steps against 7.4k for 64 at config 4) but
-  // more of them.  That pays only while the chip is nearly empty — N = 10^4: 0.40 (1 part) / 0.36 (4) / 0.27 (8), per-lane form
-  // 0.33; N = 3*10^4: 0.64 / 0.56 / 0.56, per-lane 0.58 — and costs from 6*10^4 bodies on (10^5: 1.06 / 1.62 / 1.86; 10^6: 6.96 /
-  // 16.6 / 28.2).  The key-jump cutter below behaves the same way at N = 10^6: 1/16 of the groups cut 6.97 ms, 1/8 7.11, 1/4 7.39,
-  // 1/2 7.84, all 10.3 — the filling and draining of a launch cannot be bought back with more, shorter items.
-  if (wave && bpl == 1 && !plain) {
-    parts = blocks <= 320u ? 8u : (blocks <= 640u ? 4u : 1u);
-    if (const char* pe = experiment_env("NBODY_K9_PARTS")) parts = uint32_t(atoi(pe));  // -DNBODY_EXPERIMENTS builds only
-    if (parts != 1u && parts != 2u && parts != 4u && parts != 8u && parts != 16u) parts = 1u;
-  }
-  if (parts > 1u) {
-    wave_blocks = blocks * parts;
-  } else if (wave && bpl == 1 && t->sorted && t->final_buf == 0 && !plain) {
-    // Work items (bvh_items_kernel): groups that straddle a jump of the key order are cut in two and started first.  Measured
-    // in the CLI's step loop (ms per whole bvh step; index order / start order only / start order + cut): N = 10^6 8.05 / 7.4 /
-    // 7.4, 5*10^5 5.3 / 4.6 / 4.3.  The sorted keys are in keys[1] when the sort ends in the buffer it started from
-    // (final_buf == 0: the splitter sort, the radix sort's 8 passes; not the one-block sort, whose small trees take finer work items instead).
-    uint32_t den = 16;
-    if (const char* de = experiment_env("NBODY_K9_SPLIT")) den = uint32_t(atoi(de)) ? uint32_t(atoi(de)) : 16u;  // experiments only
-    uint32_t s0, l0;
-    xcd_range(0, blocks, &s0, &l0);  // XCD 0 has the longest range
-    stride      = l0 + split_budget(l0, den);
-    wave_blocks = 8u * stride;       // blocks are dealt round-robin over the XCDs: 8 lists of up to `stride` items
-    hipLaunchKernelGGL(bvh_items_kernel, dim3(8), dim3(1024), 0, st, t->keys[1], s->first, s->count, t->order, t->order_n, blocks,
-                       stride, den);
-    NB_HIP(hipGetLastError());
-    items  = t->order;
-    nitems = t->order_n;
-  }
-  const char* le = experiment_env("NBODY_K9_LDS");  // -DNBODY_EXPERIMENTS builds: dynamic LDS bytes per block, to cap the waves per SIMD
-  const uint32_t lds = le ? uint32_t(atoi(le)) : 0u;
-#define NB_WARGS                                                                                                             \
-  dim3(wave_blocks), dim3(64), lds, st, node, static_cast<T*>(s->a), static_cast<const T*>(s->x), static_cast<T>(s->c), s->sz,     \
-   s->first, s->count, th2, t->nlevels, t->counters, items, nitems, stride, parts
+  const uint32_t *items = p.items ? t->order : nullptr, *nitems = p.items ? t->order_n : nullptr;
+  // 4. the traversal
+  auto* node = static_cast<const tree_rec<T>*>(t->node);
+  T* a       = static_cast<T*>(s->a);
+  const T *x = static_cast<const T*>(s->x), c = static_cast<T>(s->c);
 #ifdef NBODY_EXPERIMENTS
-  if (wave && bpl == 2) {
-    if (t->counters_on) hipLaunchKernelGGL((bvh_force_wave_kernel<T, D, 2, true>), NB_WARGS);
-    else hipLaunchKernelGGL((bvh_force_wave_kernel<T, D, 2, false>), NB_WARGS);
-  } else if (wave && !isa) {
-    if (t->counters_on) hipLaunchKernelGGL((bvh_force_wave_kernel<T, D, 1, true>), NB_WARGS);
-    else hipLaunchKernelGGL((bvh_force_wave_kernel<T, D, 1, false>), NB_WARGS);
-  } else
+  bool done = false;  // the forms that are not shipped, from the same plan; the shipped sweep's timeline
+  if (int r = k9_experiment_launch<T, D>(t, s, p, rq.overrides, th2, items, nitems, st, &done); r || done) return r;
 #endif
-  if (wave) {
-#define NB_IARGS                                                                                                             \
-  dim3(wave_blocks), dim3(64), lds, st, node, static_cast<T*>(s->a), static_cast<const T*>(s->x), static_cast<T>(s->c), s->sz,     \
-   s->first, s->count, t->nlevels, t->counters, items, nitems, stride, parts
-#ifdef NBODY_EXPERIMENTS
-    if (const char* e = getenv("NBODY_K9_TIMELINE"); e && e[0] == '1') {  // tools/k9_timeline.py
-      static unsigned long long* buf = nullptr;
-      static size_t cap = 0;
-      if (cap < 3 * size_t(wave_blocks)) {
-        if (buf) (void)hipFree(buf);
-        cap = 3 * size_t(wave_blocks);
-        NB_HIP(hipMalloc(&buf, cap * sizeof(unsigned long long)));
-        NB_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_k9_timeline), &buf, sizeof buf));
-      }
-      NB_HIP(hipMemsetAsync(buf, 0, cap * sizeof(unsigned long long), st));
-      g_k9_timeline_host = buf;
-      g_k9_timeline_words = 3 * size_t(wave_blocks);
-    }
-#endif
-    if (t->counters_on) hipLaunchKernelGGL((bvh_force_sweep_isa_kernel<T, D, true>), NB_IARGS);
-    else hipLaunchKernelGGL((bvh_force_sweep_isa_kernel<T, D, false>), NB_IARGS);
-#undef NB_IARGS
-  } else {
-    bool in_lds = false;
-    if constexpr (sizeof(T) == 4) {  // (nbody_bvh_set_traversal(t, 1) keeps the walk over global memory: the tests compare the two bit for bit)
-      const uint32_t nrec = t->nnodes + (1u << t->nlevels);
-      if (traversal == 0 && uint64_t(nrec) * sizeof(tree_rec<T>) <= kTreeLdsBytes) {
-        const uint32_t lblocks = (s->count + kTreeLdsThreads - 1) / kTreeLdsThreads;
-        const uint32_t bytes   = nrec * uint32_t(sizeof(tree_rec<T>));
-#define NB_LARGS                                                                                                              \
-  dim3(lblocks), dim3(kTreeLdsThreads), bytes, st, node, nrec, static_cast<T*>(s->a), static_cast<const T*>(s->x), static_cast<T>(s->c), \
-   s->sz, s->first, s->count, th2, t->nlevels, t->counters
-        if (t->counters_on) hipLaunchKernelGGL((bvh_force_lds_kernel<T, D, true>), NB_LARGS);
-        else hipLaunchKernelGGL((bvh_force_lds_kernel<T, D, false>), NB_LARGS);
-#undef NB_LARGS
-        in_lds = true;
-      }
-    }
-    if (!in_lds) {
-      if (t->counters_on) hipLaunchKernelGGL((bvh_force_kernel<T, D, true>), NB_ARGS);
-      else hipLaunchKernelGGL((bvh_force_kernel<T, D, false>), NB_ARGS);
-    }
+  switch (p.form) {
+    case k9_form::lane_global:
+      return k9_launch(t, bvh_force_kernel<T, D, false>, bvh_force_kernel<T, D, true>, p, st, node, a, x, c, s->sz, s->first, s->count,
+                       th2, t->nlevels, t->counters);
+    case k9_form::lane_lds:
+      if constexpr (sizeof(T) == 4)
+        return k9_launch(t, bvh_force_lds_kernel<T, D, false>, bvh_force_lds_kernel<T, D, true>, p, st, node,
+                         t->nnodes + (1u << t->nlevels), a, x, c, s->sz, s->first, s->count, th2, t->nlevels, t->counters);
+      break;
+    case k9_form::sweep:
+      return k9_launch(t, bvh_force_sweep_isa_kernel<T, D, false>, bvh_force_sweep_isa_kernel<T, D, true>, p, st, node, a, x, c, s->sz,
+                       s->first, s->count, t->nlevels, t->counters, items, nitems, p.stride, p.parts);
+    default: break;
   }
-#undef NB_ARGS
-#undef NB_WARGS
-  NB_HIP(hipGetLastError());
-  return NBODY_OK;
+  set_error("bvh traversal: form %d of the plan has no kernel in this build", int(p.form));
+  return NBODY_ERR_STATE;
 }
 
 }  // namespace nbody
@@ -1446,21 +1327,18 @@ extern "C" int nbody_bvh_create_on(nbody_bvh** out, int dtype, int dim, uint32_t
   // [0, 2 nleafs - 2] (tests: the sweep at theta = 3 accepting the root, n = 2, 3, powers of two — test_gpu_bvh.py).
   t->mem.alloc(&t->node, t->rec_bytes * (size_t(t->nnodes) + size_t(nleafs)));
   t->mem.alloc(&t->box, t->tsz * 2 * D * size_t(t->nnodes));
-  t->mem.alloc(&t->order, sizeof(uint32_t) * (((size_t(n) + 63) / 64 / 8 + 1) * 2 + 8) * 8);  // 8 x (longest range + the largest budget)
+  t->mem.alloc(&t->order, sizeof(uint32_t) * k9_items_capacity(n));
   t->mem.alloc(&t->order_n, sizeof(uint32_t) * 8);
   hipError_t e     = t->mem.error();
   const char* what = "nbody_bvh_create allocation";
-  if (e == hipSuccess && dtype == NBODY_F32 && (uint64_t(t->nnodes) + nleafs) * t->rec_bytes <= kTreeLdsBytes) {  // bvh_force_lds_kernel asks for more dynamic LDS than a kernel gets unasked
-    what       = "hipFuncSetAttribute(bvh_force_lds_kernel)";
-    auto allow = [&](const void* f) {
-      if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, int(kTreeLdsBytes));
-    };
-#define NB_ALLOW(T, DD)                                                                  \
-  allow(reinterpret_cast<const void*>(&bvh_force_lds_kernel<T, DD, false>)); \
-  allow(reinterpret_cast<const void*>(&bvh_force_lds_kernel<T, DD, true>))
-    if (dim == 2) { NB_ALLOW(float, 2); }
-    if (dim == 3) { NB_ALLOW(float, 3); }
-#undef NB_ALLOW
+  if (e == hipSuccess && k9_lds_fits(dtype, nl)) {  // bvh_force_lds_kernel asks for more dynamic LDS than a kernel gets unasked
+    what = "hipFuncSetAttribute(bvh_force_lds_kernel)";
+    dispatch(dtype, dim, [&](auto tg) {
+      constexpr int DD = decltype(tg)::dim;
+      for (auto* f : {&bvh_force_lds_kernel<float, DD, false>, &bvh_force_lds_kernel<float, DD, true>})
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, int(kTreeLdsBytes));
+      return NBODY_OK;
+    });
   }
   return create_finish(out, t, nbody_bvh_destroy, e, what);
 }
@@ -1595,7 +1473,7 @@ extern "C" int nbody_bvh_read(nbody_bvh* t, int what, void* host_out, size_t byt
     case 0: return copy_out(t->keys[0], sizeof(uint64_t) * size_t(t->n));
     case 1: return copy_out(t->idx[t->final_buf], sizeof(uint32_t) * size_t(t->n));
     case 6:
-      if (t->th2_built < 0.0) {
+      if (t->thresholds.th2_built < 0.0) {
         set_error("nbody_bvh_read(what=6) before nbody_bvh_build_tree");
         return NBODY_ERR_STATE;
       }
@@ -1630,12 +1508,3 @@ extern "C" int nbody_bvh_read(nbody_bvh* t, int what, void* host_out, size_t byt
   }
 }
 
-#ifdef NBODY_EXPERIMENTS
-// experiments library only (not in nbody_hip.h): the timeline of the last sweep launch made with NBODY_K9_TIMELINE=1
-extern "C" long long nbody_exp_k9_timeline(unsigned long long* out, size_t max_words) {
-  if (!nbody::g_k9_timeline_host || max_words < nbody::g_k9_timeline_words) return -1;
-  if (hipDeviceSynchronize() != hipSuccess) return -2;
-  if (hipMemcpy(out, nbody::g_k9_timeline_host, nbody::g_k9_timeline_words * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return -3;
-  return (long long)nbody::g_k9_timeline_words;
-}
-#endif

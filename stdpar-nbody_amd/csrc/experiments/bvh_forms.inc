@@ -52,7 +52,7 @@ __global__ __launch_bounds__(64) void bvh_force_wave_kernel(const tree_rec<T>* _
     group   = it & 0xfffffu;
     lane_lo = (it >> 20) & 63u;
     lane_hi = it >> 26;
-  } else if (parts > 1u) {  // every group as `parts` equal lane ranges (small systems: see force_run)
+  } else if (parts > 1u) {  // every group as `parts` equal lane ranges (small systems: k9_parts, bvh_plan.hpp)
     lane_lo = (group % parts) * (64u / parts);
     lane_hi = lane_lo + 64u / parts - 1u;
     group /= parts;
@@ -277,3 +277,77 @@ __global__ __launch_bounds__(64) void bvh_force_row_kernel(const tree_rec<T>* __
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// host side: the sweep's timeline, and the launch of the forms above from force_run's plan
+// ------------------------------------------------------------------------------------------------
+// tools/k9_timeline.py: per work item of a sweep launch (start, end) in 100 MHz ticks and the item, three words per launch block
+__device__ unsigned long long* g_k9_timeline = nullptr;
+static unsigned long long* g_k9_timeline_host = nullptr;  // the same buffer, for nbody_exp_k9_timeline
+static size_t g_k9_timeline_words = 0, g_k9_timeline_cap = 0;
+
+static int k9_timeline_prepare(uint32_t grid, hipStream_t st) {
+  if (g_k9_timeline_cap < 3 * size_t(grid)) {
+    if (g_k9_timeline_host) (void)hipFree(g_k9_timeline_host);
+    g_k9_timeline_host = nullptr;
+    g_k9_timeline_cap  = 3 * size_t(grid);
+    NB_HIP(hipMalloc(&g_k9_timeline_host, g_k9_timeline_cap * sizeof(unsigned long long)));
+    NB_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_k9_timeline), &g_k9_timeline_host, sizeof g_k9_timeline_host));
+  }
+  NB_HIP(hipMemsetAsync(g_k9_timeline_host, 0, g_k9_timeline_cap * sizeof(unsigned long long), st));
+  g_k9_timeline_words = 3 * size_t(grid);
+  return NBODY_OK;
+}
+
+// experiments library only (not in nbody_hip.h): the timeline of the last sweep launch made with NBODY_K9_TIMELINE=1
+extern "C" long long nbody_exp_k9_timeline(unsigned long long* out, size_t max_words) {
+  if (!g_k9_timeline_words || max_words < g_k9_timeline_words) return -1;
+  if (hipDeviceSynchronize() != hipSuccess) return -2;
+  if (hipMemcpy(out, g_k9_timeline_host, g_k9_timeline_words * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return -3;
+  return (long long)g_k9_timeline_words;
+}
+
+// K9's switches of this build (tools/README.md), all read here; the shipped library's k9_read_overrides returns the defaults.
+static k9_overrides k9_read_overrides() {
+  k9_overrides o;
+  if (const char* e = experiment_env("NBODY_K9_MODE")) o.mode = atoi(e);
+  if (const char* e = experiment_env("NBODY_K9_ORDER")) o.plain_order = e[0] == '0';
+  if (const char* e = experiment_env("NBODY_K9_PARTS")) {
+    const uint32_t p = uint32_t(atoi(e));
+    o.parts          = p == 2u || p == 4u || p == 8u || p == 16u ? p : 1u;
+  }
+  if (const char* e = experiment_env("NBODY_K9_SPLIT")) o.split_den = uint32_t(atoi(e)) ? uint32_t(atoi(e)) : 16u;
+  if (const char* e = experiment_env("NBODY_K9_LDS")) o.lds_bytes = uint32_t(atoi(e));
+  if (const char* e = experiment_env("NBODY_K9_TIMELINE")) o.timeline = e[0] == '1';
+  return o;
+}
+
+// force_run's one call into this file.  *done: the plan's form was one of the above and has been launched.  The shipped sweep is
+// force_run's own launch; with NBODY_K9_TIMELINE=1 its buffer is made ready here.
+template <typename T, int D>
+static int k9_experiment_launch(const nbody_bvh* t, const nbody_state* s, const k9_plan& p, const k9_overrides& o, T th2,
+                                const uint32_t* items, const uint32_t* nitems, hipStream_t st, bool* done) {
+  auto* node = static_cast<const tree_rec<T>*>(t->node);
+  T* a       = static_cast<T*>(s->a);
+  const T *x = static_cast<const T*>(s->x), c = static_cast<T>(s->c);
+  const auto wave = [&](auto plain, auto counting) {
+    hipLaunchKernelGGL(t->counters_on ? counting : plain, dim3(p.grid), dim3(p.threads), p.lds_bytes, st, node, a, x, c, s->sz, s->first,
+                       s->count, th2, t->nlevels, t->counters, items, nitems, p.stride, p.parts);
+  };
+  switch (p.form) {
+    case k9_form::sweep: return o.timeline ? k9_timeline_prepare(p.grid, st) : NBODY_OK;
+    case k9_form::compiled_sweep: wave(bvh_force_wave_kernel<T, D, 1, false>, bvh_force_wave_kernel<T, D, 1, true>); break;
+    case k9_form::compiled_sweep_2: wave(bvh_force_wave_kernel<T, D, 2, false>, bvh_force_wave_kernel<T, D, 2, true>); break;
+    case k9_form::row_sweeps:
+      if (t->counters_on) {  // (the plan has refused nlevels > 26 with the same words)
+        set_error(kK9RowsRefusal);
+        return NBODY_ERR_ARG;
+      }
+      hipLaunchKernelGGL((bvh_force_row_kernel<T, D>), dim3(p.grid), dim3(p.threads), 0, st, node, a, x, c, s->sz, s->first, s->count, th2,
+                         t->nlevels);
+      break;
+    default: return NBODY_OK;
+  }
+  *done = true;
+  NB_HIP(hipGetLastError());
+  return NBODY_OK;
+}

@@ -1,0 +1,18 @@
+"""CPU: the launch plan of the BVH traversal (csrc/bvh_plan.hpp) — tools/bvh_plan_check.cpp, compiled for the host alone, sweeps the
+plan's invariants over the sizes, pins its shapes and refusals and walks the truth table of the opening thresholds' bookkeeping.  No
+device is opened."""
+import os
+import shutil
+import subprocess
+
+from conftest import ROOT
+
+
+def test_plan_invariants_pinned_shapes_and_thresholds(tmp_path):
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    assert os.path.exists(hipcc), "no hipcc"
+    exe = tmp_path / "bvh_plan_check"
+    subprocess.check_call([hipcc, "-std=c++17", "-O1", "--offload-host-only", "-I", os.path.join(ROOT, "stdpar-nbody_amd", "csrc"), "-I",
+                           os.path.join(ROOT, "include"), os.path.join(ROOT, "tools", "bvh_plan_check.cpp"), "-o", str(exe)])
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.rstrip().endswith("ok"), (r.stdout, r.stderr)
