@@ -3,12 +3,14 @@
 //   build form 4: one launch per level the last tree used, one barrier launch for the rest.
 // Same cells, monopoles, forces and counters bit for bit; measured slower on MI355X (an agent-scope barrier writes back and
 // invalidates the per-XCD L2s, ~12 us against 4.6 us for a dependent launch: N = 10^5 0.82 against 0.35 ms per step,
-// profiles/r04/step_graph.txt).  Included twice: OT_FORMS_PART 1 = the barrier, before the level body; 2 = the kernels, after it.
+// profiles/r04/step_graph.txt).  Included three times: OT_FORMS_PART 1 = the barrier, before the level body; 2 = the kernels, after it;
+// 3 = the host side (what the plan is told, the two all-level launches, nbody_octree_info's part), behind the handle.
 #if OT_FORMS_PART == 1
 // Grid-wide barrier of a kernel whose blocks are all resident (one block per CU at most: ot_grid_blocks).  Every wave reaches an
 // exit: a block that has waited kBarrierSpins polls (seconds; e.g. the GPU is shared and its peers never got a slot) raises
 // kFlagBarrier, which nbody_octree_info reports, and the kernel's level loop ends on every block at its next check.
 constexpr uint32_t kBarrierSpins = 4u << 20;
+constexpr uint32_t kFlagBarrier  = 16u;  // beside kFlagDepth ... kFlagWalk in the tree's flags word
 __device__ __forceinline__ bool ot_grid_barrier(uint32_t* counter, uint32_t& epoch, uint32_t* flags) {
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -31,6 +33,80 @@ __device__ __forceinline__ bool ot_grid_barrier(uint32_t* counter, uint32_t& epo
 }
 __device__ __forceinline__ uint32_t ot_count(const uint32_t* lvl_count, int level) {  // written by other blocks of this kernel
   return __hip_atomic_load(lvl_count + level, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+#elif OT_FORMS_PART == 3
+// ---- host side: octree.hip's hooks, behind struct nbody_octree and ot_replan -------------------------------------------------------
+// The plan (octree_plan.hpp) takes this build's contributions as t->exp: own_levels = 0 for form 2 and the depth hint for form 4, the
+// all-level grids capped at one block per CU, and the compiler-scheduled walk for NBODY_OT_FORM=1 (read when the tree is created).
+static int ot_check_build_form(nbody_octree* t, int mode) {
+  NB_ARG(mode >= 0 && mode <= 4,
+         "build form must be 0 (auto), 1 (one launch per level), 2 (all levels in one launch), 3 (one pass over the sorted keys) or 4 "
+         "(one launch per level the last tree used, one for the rest), got %d", mode);
+  if (mode != 4) t->exp.depth_hint = 64;  // 1: every level its own launch, whatever earlier trees looked like
+  return NBODY_OK;
+}
+
+static hipError_t ot_exp_create(nbody_octree* t) {
+  const char* fe       = experiment_env("NBODY_OT_FORM");
+  t->exp.compiled_walk = fe && fe[0] == '1';
+  hipDeviceProp_t prop;
+  const hipError_t e = hipGetDeviceProperties(&prop, t->device);
+  t->exp.ncu         = e == hipSuccess && prop.multiProcessorCount > 0 ? uint32_t(prop.multiProcessorCount) : 1u;
+  return e;
+}
+
+// nbody_octree_info, between the reports of the node pool and of the walks: the barrier's flag, and form 4's depth hint from a tree
+// that raised no flag
+static int ot_exp_info(nbody_octree* t, uint32_t flags, const uint32_t* lv) {
+  if (flags & kFlagBarrier) {
+    set_error("octree build: a grid barrier of the all-level kernels timed out (the blocks of one launch were not all running "
+              "within seconds: is the GPU shared?); nbody_octree_set_build(t, 1) builds with one launch per level");
+    return NBODY_ERR_STATE;
+  }
+  if (t->build == 4 && !(flags & (kFlagStack | kFlagWalk))) {
+    const int maxl = t->plan.maxl;
+    int deepest    = -1;
+    for (int l = 0; l < maxl; ++l)
+      if (lv[l] != 0) deepest = l;
+    t->exp.depth_hint = deepest + 3 < maxl ? deepest + 3 : maxl;  // the levels the next builds launch one by one
+    ot_replan(t);
+  }
+  return NBODY_OK;
+}
+
+// Levels [0, own_levels) get a launch each; the levels behind them — empty unless the tree has grown deeper than the last
+// nbody_octree_info saw it (+ 2) — share ONE launch that walks them with a grid barrier and normally returns at once.  (All levels
+// behind grid barriers, nbody_octree_set_build(t, 2), is slower on this chip: an agent-scope barrier has to write back and
+// invalidate the per-XCD L2s and costs ~12 us, a dependent launch 4.6 us — N = 10^5: 0.87 against 0.55 ms per step.)
+template <typename T, int D>
+static int ot_exp_build_rest(nbody_octree* t, const nbody_state* s, hipStream_t st) {
+  const ot_plan& p = t->plan;
+  if (p.own_levels >= kMaxLevels<D>) return NBODY_OK;
+  const int fin = t->sorted_buf;
+  hipLaunchKernelGGL((ot_build_all_levels_kernel<T, D>), dim3(p.all_levels_build_grid), dim3(kOBuild), 0, st, t->keys[fin], t->idx[fin],
+                     static_cast<const T*>(s->m), static_cast<const T*>(s->x), ot_view<T, D>(t), t->cells, t->lvl_count, ot_flags(t),
+                     p.capacity, p.max_cells, p.own_levels);
+  NB_HIP(hipGetLastError());
+  return NBODY_OK;
+}
+// the levels below own_levels, deepest first, in one launch, before the launches of the levels above them
+template <typename T, int D>
+static int ot_exp_multipole_rest(nbody_octree* t, hipStream_t st) {
+  const ot_plan& p = t->plan;
+  if (p.own_levels >= kMaxLevels<D>) return NBODY_OK;
+  hipLaunchKernelGGL((ot_multipole_all_levels_kernel<T, D>), dim3(p.all_levels_mp_grid), dim3(kOB), 0, st, ot_view<T, D>(t), t->cells,
+                     t->lvl_count, t->lvl_count + (kMaxLevels<D> + 4), t->lvl_count + (kMaxLevels<D> + 2), p.own_levels, p.max_cells);
+  NB_HIP(hipGetLastError());
+  return NBODY_OK;
+}
+
+// wall_clock64() stamps (100 MHz) of the last ot_insert_small_kernel launch on the current device: entry, keys, sort, numbering,
+// cells, deep cells (tools/time_small_insert_phases.py); C linkage: the name is the same inside the namespace
+extern "C" int nbody_exp_octree_small_stamps(uint64_t* out8) {
+  NB_HIP(hipDeviceSynchronize());
+  NB_HIP(hipMemcpyFromSymbol(out8, HIP_SYMBOL(ot_small_stamps), sizeof(uint64_t) * 8));
+  return NBODY_OK;
 }
 
 #else

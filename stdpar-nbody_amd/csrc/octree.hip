@@ -27,6 +27,7 @@
 // thread each (ot_build_deep_kernel), so the tree has the reference's shape at any depth.
 #include "common.hpp"
 #include "block_schedule.hpp"
+#include "octree_plan.hpp"
 #include "radix_sort.hpp"
 #include "to_sgpr.hpp"
 
@@ -35,17 +36,15 @@
 
 namespace nbody {
 
-constexpr int kOB            = 256;
+// (the launch-shape constants — kOB, kOBuild, kSmallN, kSmallB, kLcpB, kLcpBuildB, kMpChunk, kMpCrown, kMpMaxBlocks, kSmallChunks, kOC,
+// kMaxLevels<D>, kOtNQ<D>, kOtQS<D> — are octree_plan.hpp's: the host's decisions depend on them)
 constexpr uint32_t kOtEmpty  = 0xffffffffu;  // src/octree.h:37
 constexpr uint32_t kOtBody   = 0xfffffffeu;  // src/octree.h:38
-constexpr uint32_t kFlagDepth = 1u, kFlagCapacity = 2u, kFlagStack = 4u, kFlagWalk = 8u, kFlagBarrier = 16u;
+constexpr uint32_t kFlagDepth = 1u, kFlagCapacity = 2u, kFlagStack = 4u, kFlagWalk = 8u;  // (16: experiments/octree_forms.inc)
 constexpr int kOtDeepLevels = 128;  // total depth the deep build follows before it calls the bodies coincident
 // its DFS stack: the cells on the current path stay for their second visit (<= kOtDeepLevels), plus the waiting siblings — the
 // biggest child of a cell is entered LAST, so siblings wait only along the <= log2(n) levels where the path entered a smaller child
 constexpr int kOtDeepFrames = kOtDeepLevels + 7 * 28 + 12;
-
-template <int D>
-constexpr int kMaxLevels = D == 3 ? 21 : 32;
 
 // Per-level build: an internal cell waiting to be split — its node index, its range of sorted bodies and its rank (= sibling group
 // number).  One-pass build: entry r describes the cell of rank r — node index, `start` = its level, `end` = one past the last rank
@@ -255,7 +254,6 @@ __global__ __launch_bounds__(kOB) void ot_bounds_final_kernel(const T* __restric
 // Small systems (n <= kSmallN: the reference's default run is 1000 bodies): one block does both halves.  1024: the step of the
 // one-block kernels below is one CU's work — 0.081 ms at n = 1000 (float) against 0.129 through the launches of the large path, but
 // 0.137 at 2048 where the large path (its kernels spread over the chip) takes ~0.12.
-constexpr uint32_t kSmallN = 1024;
 template <typename T, int D>
 __global__ __launch_bounds__(kOB) void ot_bounds_small_kernel(const T* __restrict__ x, uint32_t nelem, T* __restrict__ root) {
 #pragma clang fp contract(off)
@@ -345,7 +343,6 @@ __global__ void ot_build_init_kernel(uint32_t n, const T* __restrict__ m, const 
 // record each — a cell's sibling group is one contiguous 2^D-record store.  Children that must be split are appended to
 // the next level's cell list with ONE counter bump per 1024-thread block: returning same-address atomics complete at
 // ~12 ns each on this chip whatever else the kernel does (one per wave made the widest level 402 us, 37k atomics).
-constexpr int kOBuild = 1024;
 
 #ifdef NBODY_EXPERIMENTS
 #define OT_FORMS_PART 1
@@ -683,10 +680,6 @@ __global__ __launch_bounds__(kOB) void ot_multipole_level_kernel(int level, ot_t
 // (ot_multipole_round_kernel).  Same children, same order, same arithmetic as
 // ot_multipole_cell: the tree is the per-level build's up to the numbering of the sibling groups, and the walk (which pushes
 // children in slot order) produces bit-identical forces and counters (tests/test_gpu_octree.py::test_octree_build_forms).
-constexpr int kLcpB = 1024;   // positions per block of ot_lcp_kernel
-constexpr int kLcpBuildB = 256;  // ot_build_lcp_kernel: lane groups are independent, small blocks give their slots back early
-constexpr int kMpChunk = 512;  // ot_multipole_chunks_kernel: ranks (= threads) per block (512: a double 3D cell keeps 2^D x 4 values in registers)
-constexpr int kMpCrown = 512;  // ot_multipole_crown_kernel: threads, and cells it finishes out of registers and LDS
 
 template <int D>
 __device__ __forceinline__ int ot_common_levels(uint64_t a, uint64_t b) {
@@ -1014,7 +1007,6 @@ __global__ __launch_bounds__(kLcpBuildB) void ot_build_lcp_kernel(ot_lcp_args<T,
 // the prefix over all positions at once (bbase = 0: rank_at() and the scatter see the same sums as from the blocks of
 // ot_lcp_kernel); the cells are built by rank exactly as ot_build_lcp_kernel does, 2^D lanes each, the deep ones as
 // ot_build_deep_kernel does, a thread each, behind a block barrier with a fence (they read what the block stored).
-constexpr int kSmallB = 1024;
 #ifdef NBODY_EXPERIMENTS
 __device__ uint64_t ot_small_stamps[8];  // wall_clock64() at the phase boundaries of the last launch (100 MHz)
 #define OT_SMALL_STAMP(k) \
@@ -1301,7 +1293,6 @@ __global__ __launch_bounds__(kMpChunk) void ot_multipole_chunks_kernel(ot_tree<T
 // The waiting cells of a round sit in the slots (block, level) that the blocks' masks name; in (block, level) order they are in
 // RANK order, so the compacted list has the property the ranks have: the waiting cells below a waiting cell are an interval of
 // it.  Exclusive prefix of the masks' bit counts into LDS (base[nblocks] = the number of waiting cells); returns that number.
-constexpr uint32_t kMpMaxBlocks = 8192;  // blocks of the previous round a round can compact (32 KB of LDS): trees of up to 4.2 * 10^6 cells
 constexpr uint32_t kMpLater2    = 0x40000000u;
 
 // (written for kMpCrown threads; a larger block passes active = threadIdx.x < kMpCrown: its other threads only keep the barriers)
@@ -1570,7 +1561,6 @@ __global__ __launch_bounds__(kMpCrown) void ot_multipole_crown_kernel(ot_tree<T,
 // or, in float, where a cell's 2^D child records fit the registers of 1024 threads, and the tree has at most 1024
 // cells, ONE chunk of 1024 ranks and nothing left for a crown.  The crown reads what the chunks stored (records, marks, slots): a fence and a
 // full barrier in between.
-constexpr uint32_t kSmallChunks = (kSmallN + 1 + kMpChunk - 1) / kMpChunk;
 static_assert(kMpChunk == kMpCrown, "the small-tree kernel runs both bodies with one block shape");
 template <typename T, int D>
 constexpr int kSmallMpThreads = sizeof(T) == 4 ? 1024 : kMpChunk;  // (double: 3D does not fit the registers, 2D not the 64 KB of static LDS)
@@ -1756,7 +1746,6 @@ __device__ __forceinline__ void ot_accumulate_soft(bool on, T (&acc)[D], const T
 // Shard windows.  The walk takes bodies in key order, the window [first, first + count) is a range of BODY indices, so the
 // owned bodies are scattered over the key order: they are compacted (order kept) into a dense list first, otherwise every
 // wave would carry one owned body among 2^(6-D) and a 1/G shard would cost as much as the whole system.
-constexpr int kOC = 1024;
 __global__ __launch_bounds__(kOC) void ot_owned_count_kernel(const uint32_t* __restrict__ sidx, uint32_t sz, uint32_t first,
                                                              uint32_t count, uint32_t* __restrict__ block_counts) {
   __shared__ uint32_t wsum[kOC / 64];
@@ -1828,10 +1817,6 @@ __global__ __launch_bounds__(kOC) void ot_owned_scatter_kernel(const uint32_t* _
 // system around the origin, 1e-4 of Q in float for a cluster of size 1e-4 |p| (found by the per-body comparison with Q summed from
 // the bodies: tests/test_gpu_octree_wide.py, the deep system).  So each cell also carries P = sum_c (P_c + m_c d_c), a body's own
 // being 0, and adds the owed term; where it does not matter P is rounding noise times eps.
-template <int D>
-constexpr int kOtNQ = D == 3 ? 6 : 3;
-template <int D>
-constexpr int kOtQS = kOtNQ<D> + D;
 
 // One cell, after its monopole and the quadrupoles of its child cells: the same children, the same order and the same operations
 // whichever build form numbered the cells, so both forms give the same bits.
@@ -2772,16 +2757,17 @@ __global__ __launch_bounds__(64) void ot_force_isa_f32_kernel(const ot_node<floa
 }  // namespace nbody
 
 // ---- host side / C ABI -----------------------------------------------------------------------------------------------
+// What is launched, with which grids and buffer sizes, is octree_plan.hpp's: the handle keeps the settings, the buffers and the plan.
 struct nbody_octree {
   int dtype = 0, dim = 0, device = 0;  // device: nbody_octree_create_on's (nbody_octree_create: the current one); every call runs there
   int walk = 0;                        // nbody_octree_set_walk: 0 auto, 1 compiler-scheduled kernel, 2 the visit round as ISA
-  int build = 0;                       // nbody_octree_set_build: 0 auto (= 3), 1 one launch per level, 2 all levels in one launch
-                                       // (grid barrier), 3 one pass over the sorted keys (ot_build_lcp_kernel)
-  int depth_hint = 64;                 // levels launched one by one (the rest share one launch); from the last nbody_octree_info
-  int ncu = 0;                         // compute units of the device (the all-level kernels launch at most one block per CU)
+  int build = 0;                       // nbody_octree_set_build: 0 auto (= 3), 1 one launch per level, 3 one pass over the sorted keys
   uint32_t step_budget = 0;            // nbody_octree_set_step_budget: visit rounds a body may make; 0 = the node pool size
-  uint32_t n = 0, capacity = 0, max_cells = 0, bounds_blocks = 0;
+  uint32_t n = 0;
   size_t tsz = 0;
+  nbody::ot_overrides exp;  // set by the -DNBODY_EXPERIMENTS build only (experiments/octree_forms.inc)
+  nbody::ot_plan plan;      // of (dtype, dim, n) and the three settings: ot_replan
+  nbody::ot_phases phase;
   void* root       = nullptr;  // T[D+1]: root_x (D), root_side_length
   void* partials   = nullptr;
   uint64_t* keys[2] = {nullptr, nullptr};
@@ -2789,7 +2775,6 @@ struct nbody_octree {
   uint32_t* hist   = nullptr;
   void* rootrec    = nullptr;  // ot_node<T>: node 0
   void* groups     = nullptr;  // ot_group<T,D>[max_cells]: sibling group g = nodes 1 + g * 2^D ...
-  size_t group_bytes = 0;
   nbody::ot_cell* cells = nullptr;
   nbody::ot_cell* tops  = nullptr;  // one-pass build: the cells at the key depth, for ot_build_deep_kernel
   int8_t* lcp           = nullptr;  // one-pass build: l_i for positions 0 ... n
@@ -2802,10 +2787,9 @@ struct nbody_octree {
   uint32_t* later2 = nullptr, *later2_mask = nullptr;  //   the same for the blocks of ot_multipole_round_kernel
   uint32_t* lvl_count = nullptr;  // [MAXL + 2] level counts and deep groups, flags, two barrier counters, deep-list cursor, crown count
   uint32_t* counters = nullptr;
-  void* quad         = nullptr;  // T[1 + max_cells * 2^D][NQ]: quadrupoles by node index; allocated by the first nbody_octree_compute_quadrupoles
+  void* quad         = nullptr;  // T[1 + max_cells * 2^D][kOtQS]: quadrupoles by node index; allocated by the first nbody_octree_compute_quadrupoles
   int sorted_buf   = 0;
-  bool counters_on = false, have_bounds = false, inserted = false, have_tree = false;
-  bool have_quad = false;  // nbody_octree_compute_quadrupoles ran after the latest clear / insert / compute_tree / set_build
+  bool counters_on = false;
   nbody::device_buffers mem;  // owns every buffer above, counters and quad (allocated after create) included
 };
 
@@ -2813,11 +2797,39 @@ using namespace nbody;
 
 namespace nbody {
 
-// the flags word (kFlagDepth ... of the build, kFlagStack and kFlagWalk of the walks): behind the level counts and the deep groups
-static uint32_t* ot_flags(const nbody_octree* t) { return t->lvl_count + ((t->dim == 3 ? kMaxLevels<3> : kMaxLevels<2>) + 2); }
-// the tree is built in one pass over the sorted keys (build form 3, which 0 = auto selects)
-static bool ot_one_pass(const nbody_octree* t) { return t->build == 0 || t->build == 3; }
+static_assert(sizeof(ot_cell) == 16 && sizeof(ot_node<double>) <= 64, "the record sizes plan_octree allocates");
+static_assert(sizeof(ot_group<float, 2>) == ot_group_bytes(4, 2) && sizeof(ot_group<float, 3>) == ot_group_bytes(4, 3) &&
+                  sizeof(ot_group<double, 2>) == ot_group_bytes(8, 2) && sizeof(ot_group<double, 3>) == ot_group_bytes(8, 3),
+              "ot_group_bytes");
+static_assert(kSmallMpThreads<float, 3> == 1024 && kSmallMpThreads<double, 3> == kMpChunk, "ot_small_mp_threads");
 
+// the flags word (kFlagDepth ... of the build, kFlagStack and kFlagWalk of the walks): behind the level counts and the deep groups
+static uint32_t* ot_flags(const nbody_octree* t) { return t->lvl_count + (t->plan.maxl + 2); }
+
+static void ot_replan(nbody_octree* t) {
+  ot_request r;
+  r.elem = uint32_t(t->tsz), r.dim = t->dim, r.n = t->n;
+  r.group_bytes = ot_group_bytes(r.elem, r.dim), r.sort_words = radix_sort_scratch_words(t->n);
+  r.build = t->build, r.walk = t->walk, r.step_budget = t->step_budget;
+  r.overrides = t->exp;
+  t->plan     = plan_octree(r);
+}
+
+// the typed views of the handle: the tree, and the arguments of the one-pass build over the sorted pairs in buffer `buf`
+template <typename T, int D>
+static ot_tree<T, D> ot_view(const nbody_octree* t) {
+  return {static_cast<ot_group<T, D>*>(t->groups), static_cast<ot_node<T>*>(t->rootrec)};
+}
+template <typename T, int D>
+static ot_lcp_args<T, D> ot_lcp_view(const nbody_octree* t, const nbody_state* s, int buf) {
+  return {t->keys[buf], t->idx[buf], t->n, t->lcp, t->plocal, t->bsum, t->rankpos, static_cast<const T*>(s->m),
+          static_cast<const T*>(s->x), ot_view<T, D>(t), t->cells, t->tops, t->lvl_count, ot_flags(t), t->plan.capacity, t->plan.max_cells};
+}
+
+static int ot_check_handle(const nbody_octree* t, void* stream) {
+  NB_ARG(t != nullptr, "nbody_octree is NULL");
+  return check_same_device(t->device, as_stream(stream), "nbody_octree");
+}
 static int ot_check(const nbody_octree* t, const nbody_state* s, void* stream) {
   NB_ARG(t != nullptr, "nbody_octree is NULL");
   if (int r = check_state(s)) return r;
@@ -2826,168 +2838,145 @@ static int ot_check(const nbody_octree* t, const nbody_state* s, void* stream) {
          "octree was created for (dtype=%d, dim=%d, n=%u), state is (%d, %d, %u)", t->dtype, t->dim, t->n, s->dtype, s->dim, s->sz);
   return NBODY_OK;
 }
+// the refusal of `what` before the call that makes `phase`
+static int ot_need(const nbody_octree* t, ot_phase phase, const char* what) {
+  if (!t->phase.missing(phase)) return NBODY_OK;
+  set_error(ot_phase_refusal(phase), what);
+  return NBODY_ERR_STATE;
+}
+// eps of a softened call, validated, as e2 of the state's type (widened: the runners narrow it back exactly)
+static int ot_softening(const nbody_state* s, double eps, double* e2_out) {
+  return dispatch(s->dtype, s->dim, [&](auto tg) {
+    typename decltype(tg)::type e2;
+    if (int r = check_softening(eps, &e2)) return r;
+    *e2_out = double(e2);
+    return int(NBODY_OK);
+  });
+}
+
+#ifdef NBODY_EXPERIMENTS
+#define OT_FORMS_PART 3
+#include "experiments/octree_forms.inc"  // the host side of build forms 2 and 4, NBODY_OT_FORM
+#undef OT_FORMS_PART
+#else  // the shipped library builds with forms 0, 1 and 3, reads no environment and asks the device nothing
+static int ot_check_build_form(nbody_octree*, int mode) {
+  NB_ARG(mode == 0 || mode == 1 || mode == 3, "build form must be 0 (auto), 1 (breadth-first, one launch per level) or 3 (one pass over the sorted keys), got %d%s",
+         mode, mode == 2 || mode == 4 ? " — that form exists only in the -DNBODY_EXPERIMENTS build (make experiments)" : "");
+  return NBODY_OK;
+}
+static hipError_t ot_exp_create(nbody_octree*) { return hipSuccess; }
+static int ot_exp_info(nbody_octree*, uint32_t, const uint32_t*) { return NBODY_OK; }
+template <typename T, int D>
+static int ot_exp_build_rest(nbody_octree*, const nbody_state*, hipStream_t) { return NBODY_OK; }
+template <typename T, int D>
+static int ot_exp_multipole_rest(nbody_octree*, hipStream_t) { return NBODY_OK; }
+#endif
 
 template <typename T, int D>
 static int ot_bounds_run(nbody_octree* t, const nbody_state* s, hipStream_t st) {
-  if (s->sz <= kSmallN) {
+  const ot_plan& p = t->plan;
+  if (p.small_bounds) {
     hipLaunchKernelGGL((ot_bounds_small_kernel<T, D>), dim3(1), dim3(kOB), 0, st, static_cast<const T*>(s->x), s->sz * uint32_t(D),
                        static_cast<T*>(t->root));
     NB_HIP(hipGetLastError());
     return NBODY_OK;
   }
-  hipLaunchKernelGGL((ot_bounds_partial_kernel<T>), dim3(t->bounds_blocks), dim3(kOB), 0, st, static_cast<const T*>(s->x),
+  hipLaunchKernelGGL((ot_bounds_partial_kernel<T>), dim3(p.bounds_blocks), dim3(kOB), 0, st, static_cast<const T*>(s->x),
                      uint64_t(s->sz) * D, static_cast<T*>(t->partials));
   NB_HIP(hipGetLastError());
   hipLaunchKernelGGL((ot_bounds_final_kernel<T, D>), dim3(1), dim3(kOB), 0, st, static_cast<const T*>(t->partials),
-                     t->bounds_blocks, static_cast<T*>(t->root));
+                     p.bounds_blocks, static_cast<T*>(t->root));
   NB_HIP(hipGetLastError());
   return NBODY_OK;
 }
 
 template <typename T, int D>
 static int ot_insert_run(nbody_octree* t, const nbody_state* s, hipStream_t st) {
-  constexpr uint32_t NCH = 1u << D;
-  const uint32_t n       = s->sz;
-  const ot_tree<T, D> tree{static_cast<ot_group<T, D>*>(t->groups), static_cast<ot_node<T>*>(t->rootrec)};
-  if (n <= kSmallN && ot_one_pass(t)) {  // one block does everything up to the cells
-    uint32_t* flags = ot_flags(t);
-    const ot_lcp_args<T, D> args{t->keys[0], t->idx[0], n, t->lcp, t->plocal, t->bsum, t->rankpos, static_cast<const T*>(s->m),
-                                 static_cast<const T*>(s->x), tree, t->cells, t->tops, t->lvl_count, flags, t->capacity, t->max_cells};
-    hipLaunchKernelGGL((ot_insert_small_kernel<T, D>), dim3(1), dim3(kSmallB), 0, st, args, static_cast<const T*>(t->root), t->keys[0],
+  const ot_plan& p = t->plan;
+  const uint32_t n = s->sz;
+  const T *m = static_cast<const T*>(s->m), *x = static_cast<const T*>(s->x), *root = static_cast<const T*>(t->root);
+  if (p.small_insert) {  // one block does everything up to the cells
+    hipLaunchKernelGGL((ot_insert_small_kernel<T, D>), dim3(1), dim3(kSmallB), 0, st, ot_lcp_view<T, D>(t, s, 0), root, t->keys[0],
                        t->idx[0], t->idx[1]);
     NB_HIP(hipGetLastError());
     t->sorted_buf = 0;
     return NBODY_OK;
   }
-  hipLaunchKernelGGL((ot_keys_kernel<T, D>), dim3((n + kOB - 1) / kOB), dim3(kOB), 0, st, static_cast<const T*>(s->x), n,
-                     static_cast<const T*>(t->root), t->keys[0]);
+  hipLaunchKernelGGL((ot_keys_kernel<T, D>), dim3(p.keys_grid), dim3(kOB), 0, st, x, n, root, t->keys[0]);
   NB_HIP(hipGetLastError());
   int fin = 0;
   if (int r = radix_sort_pairs(t->keys, t->idx, n, D == 3 ? 63 : 64, t->hist, st, &fin)) return r;
   t->sorted_buf = fin;
-  uint32_t* flags = ot_flags(t);
-  if (ot_one_pass(t)) {  // one pass over the sorted keys: 4 launches whatever the depth
-    const uint32_t nblk = n / kLcpB + 1;  // positions 0 ... n
-    hipLaunchKernelGGL((ot_lcp_kernel<D>), dim3(nblk), dim3(kLcpB), 0, st, t->keys[fin], n, t->lcp, t->plocal, t->bsum, t->bhist);
+  const ot_tree<T, D> tree = ot_view<T, D>(t);
+  uint32_t* flags          = ot_flags(t);
+  if (p.one_pass) {  // one pass over the sorted keys: 4 launches whatever the depth
+    hipLaunchKernelGGL((ot_lcp_kernel<D>), dim3(p.lcp_blocks), dim3(kLcpB), 0, st, t->keys[fin], n, t->lcp, t->plocal, t->bsum, t->bhist);
     NB_HIP(hipGetLastError());
-    hipLaunchKernelGGL((ot_lcp_finish_kernel<T, D>), dim3(1), dim3(1024), 0, st, n, nblk, t->bsum, t->bhist,
-                       static_cast<const T*>(s->m), static_cast<const T*>(s->x), tree, t->lvl_count);
+    hipLaunchKernelGGL((ot_lcp_finish_kernel<T, D>), dim3(1), dim3(1024), 0, st, n, p.lcp_blocks, t->bsum, t->bhist, m, x, tree,
+                       t->lvl_count);
     NB_HIP(hipGetLastError());
-    hipLaunchKernelGGL((ot_lcp_scatter_kernel<D>), dim3((n + kOB - 1) / kOB), dim3(kOB), 0, st, n, t->lcp, t->plocal, t->bsum, t->rankpos,
-                       t->max_cells);
+    hipLaunchKernelGGL((ot_lcp_scatter_kernel<D>), dim3(p.scatter_grid), dim3(kOB), 0, st, n, t->lcp, t->plocal, t->bsum, t->rankpos,
+                       p.max_cells);
     NB_HIP(hipGetLastError());
-    {
-      const ot_lcp_args<T, D> args{t->keys[fin], t->idx[fin], n, t->lcp, t->plocal, t->bsum, t->rankpos, static_cast<const T*>(s->m),
-                                   static_cast<const T*>(s->x), tree, t->cells, t->tops, t->lvl_count, flags, t->capacity, t->max_cells};
-      const uint32_t blocks = uint32_t((uint64_t(t->max_cells) * NCH + kLcpBuildB - 1) / kLcpBuildB);
-      hipLaunchKernelGGL((ot_build_lcp_kernel<T, D>), dim3(blocks), dim3(kLcpBuildB), 0, st, args);
+    hipLaunchKernelGGL((ot_build_lcp_kernel<T, D>), dim3(p.build_lcp_grid), dim3(kLcpBuildB), 0, st, ot_lcp_view<T, D>(t, s, fin));
+    NB_HIP(hipGetLastError());
+  } else {  // breadth first: every level its own launch (the experiments' forms 2 and 4: the levels from own_levels on in one)
+    hipLaunchKernelGGL((ot_build_init_kernel<T, D>), dim3(1), dim3(64), 0, st, n, m, x, tree, t->cells, t->lvl_count);
+    NB_HIP(hipGetLastError());
+    for (int l = 0; l < p.own_levels; ++l) {
+      hipLaunchKernelGGL((ot_build_level_kernel<T, D>), dim3(p.build_level_grid[l]), dim3(kOBuild), 0, st, l, t->keys[fin], t->idx[fin],
+                         m, x, tree, t->cells, t->lvl_count, flags, p.capacity, p.max_cells);
       NB_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL((ot_build_deep_kernel<T, D>), dim3(64), dim3(64), 0, st, t->idx[fin], t->idx[1 - fin],
-                       static_cast<const T*>(s->m), static_cast<const T*>(s->x), static_cast<const T*>(t->root), tree, t->cells,
-                       t->tops, t->lvl_count, flags, t->capacity);
-    NB_HIP(hipGetLastError());
-    return NBODY_OK;
+    if (int r = ot_exp_build_rest<T, D>(t, s, st)) return r;
   }
-  hipLaunchKernelGGL((ot_build_init_kernel<T, D>), dim3(1), dim3(64), 0, st, n, static_cast<const T*>(s->m),
-                     static_cast<const T*>(s->x), tree, t->cells, t->lvl_count);
-  NB_HIP(hipGetLastError());
-  // Levels [0, own) get a launch each; the levels behind them — empty unless the tree has grown deeper than the last
-  // nbody_octree_info saw it (+ 2) — share ONE launch that walks them with a grid barrier and normally returns at once.  (All levels
-  // behind grid barriers, nbody_octree_set_build(t, 2), is slower on this chip: an agent-scope barrier has to write back and
-  // invalidate the per-XCD L2s and costs ~12 us, a dependent launch 4.6 us — N = 10^5: 0.87 against 0.55 ms per step.)
-#ifdef NBODY_EXPERIMENTS
-  const int own = t->build == 2 ? 0 : (t->depth_hint < kMaxLevels<D> ? t->depth_hint : kMaxLevels<D>);
-#else
-  constexpr int own = kMaxLevels<D>;  // build form 1: every level its own launch
-#endif
-  {
-    uint64_t width = 1;  // a level has at most min(n/2, 2^(D*level)) cells to split
-    for (int l = 0; l < own; ++l) {
-      const uint64_t cap_l = width < uint64_t(n / 2 + 1) ? width : uint64_t(n / 2 + 1);
-      hipLaunchKernelGGL((ot_build_level_kernel<T, D>), dim3(uint32_t((cap_l * NCH + kOBuild - 1) / kOBuild)), dim3(kOBuild), 0, st, l,
-                         t->keys[fin], t->idx[fin], static_cast<const T*>(s->m), static_cast<const T*>(s->x), tree, t->cells,
-                         t->lvl_count, flags, t->capacity, t->max_cells);
-      NB_HIP(hipGetLastError());
-      if (width < (uint64_t(1) << 40)) width *= NCH;
-    }
-  }
-#ifdef NBODY_EXPERIMENTS
-  if (own < kMaxLevels<D>) {  // at most one block per CU, and no more blocks than the widest level can use
-    const uint64_t widest = uint64_t(n / 2 + 1) * NCH;
-    uint32_t grid         = uint32_t((widest + kOBuild - 1) / kOBuild);
-    if (grid > uint32_t(t->ncu)) grid = uint32_t(t->ncu);
-    hipLaunchKernelGGL((ot_build_all_levels_kernel<T, D>), dim3(grid), dim3(kOBuild), 0, st, t->keys[fin], t->idx[fin],
-                       static_cast<const T*>(s->m), static_cast<const T*>(s->x), tree, t->cells, t->lvl_count, flags, t->capacity,
-                       t->max_cells, own);
-    NB_HIP(hipGetLastError());
-  }
-#endif
   // cells still holding >= 2 bodies at the key depth (none in a typical step: the kernel then returns at once)
-  hipLaunchKernelGGL((ot_build_deep_kernel<T, D>), dim3(64), dim3(64), 0, st, t->idx[fin], t->idx[1 - fin],
-                     static_cast<const T*>(s->m), static_cast<const T*>(s->x), static_cast<const T*>(t->root), tree, t->cells,
-                     static_cast<const ot_cell*>(nullptr), t->lvl_count, flags, t->capacity);
+  hipLaunchKernelGGL((ot_build_deep_kernel<T, D>), dim3(64), dim3(64), 0, st, t->idx[fin], t->idx[1 - fin], m, x, root, tree, t->cells,
+                     p.one_pass ? t->tops : static_cast<const ot_cell*>(nullptr), t->lvl_count, flags, p.capacity);
   NB_HIP(hipGetLastError());
   return NBODY_OK;
 }
 
 template <typename T, int D>
 static int ot_tree_run(nbody_octree* t, hipStream_t st) {
-  constexpr uint32_t NCH = 1u << D;
-  const ot_tree<T, D> tree{static_cast<ot_group<T, D>*>(t->groups), static_cast<ot_node<T>*>(t->rootrec)};
-  const uint32_t max_chunks = (t->max_cells + kMpChunk - 1) / kMpChunk;
-  if (ot_one_pass(t) && max_chunks > kMpMaxBlocks) {  // beyond 4.2 * 10^6 bodies: one launch per level over all ranks
-    for (int l = kMaxLevels<D> - 1; l >= 0; --l) {
-      hipLaunchKernelGGL((ot_multipole_ranks_level_kernel<T, D>), dim3((t->max_cells + kOB - 1) / kOB), dim3(kOB), 0, st, l, tree,
-                         t->cells, t->lvl_count, t->capacity, t->max_cells);
+  const ot_plan& p         = t->plan;
+  const ot_tree<T, D> tree = ot_view<T, D>(t);
+  switch (p.route) {
+    case ot_mp_route::ranks_per_level:
+      for (int l = kMaxLevels<D> - 1; l >= 0; --l) {
+        hipLaunchKernelGGL((ot_multipole_ranks_level_kernel<T, D>), dim3(p.ranks_grid), dim3(kOB), 0, st, l, tree, t->cells,
+                           t->lvl_count, p.capacity, p.max_cells);
+        NB_HIP(hipGetLastError());
+      }
+      break;
+    case ot_mp_route::small_block:
+      hipLaunchKernelGGL((ot_multipole_small_kernel<T, D>), dim3(1), dim3(p.small_threads), 0, st, tree, t->cells, t->lvl_count,
+                         t->later, t->later_mask, p.capacity, p.max_cells, p.chunks);
       NB_HIP(hipGetLastError());
-    }
-    return NBODY_OK;
-  }
-  // one block for the whole tree where that is one chunk's work: a single chunk of kMpChunk ranks, or — in float — of 1024 (more cells
-  // than that, rare: chunk after chunk, then the crown).  Double trees of two or three chunks take the two launches below: their
-  // chunks side by side on two CUs + the crown are 22 us, one after the other in one block 30 (n = 1000)
-  if (ot_one_pass(t) && (max_chunks == 1 || (sizeof(T) == 4 && max_chunks <= kSmallChunks))) {
-    hipLaunchKernelGGL((ot_multipole_small_kernel<T, D>), dim3(1), dim3((kSmallMpThreads<T, D>)), 0, st, tree, t->cells, t->lvl_count, t->later,
-                       t->later_mask, t->capacity, t->max_cells, max_chunks);
-    NB_HIP(hipGetLastError());
-    return NBODY_OK;
-  }
-  if (ot_one_pass(t)) {  // rank chunks, then the cells that span chunk boundaries: in one block, or in two rounds
-    hipLaunchKernelGGL((ot_multipole_chunks_kernel<T, D>), dim3(max_chunks), dim3(kMpChunk), 0, st, tree, t->cells, t->lvl_count,
-                       t->later, t->later_mask, t->capacity, t->max_cells);
-    NB_HIP(hipGetLastError());
-    const bool rounds = max_chunks > uint32_t(kMpCrown);  // (decided by the size the tree was created for: the launches are recorded)
-    if (rounds) {
-      const uint32_t blocks = (max_chunks * uint32_t(kMaxLevels<D>) + kMpCrown - 1) / kMpCrown;
-      hipLaunchKernelGGL((ot_multipole_round_kernel<T, D>), dim3(blocks), dim3(kMpCrown), 0, st, tree, t->cells, t->lvl_count, t->later,
-                         t->later_mask, t->later2, t->later2_mask, t->max_cells);
+      break;
+    case ot_mp_route::chunks_crown:
+    case ot_mp_route::chunks_round_crown:
+      hipLaunchKernelGGL((ot_multipole_chunks_kernel<T, D>), dim3(p.chunks), dim3(kMpChunk), 0, st, tree, t->cells, t->lvl_count,
+                         t->later, t->later_mask, p.capacity, p.max_cells);
       NB_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL((ot_multipole_crown_kernel<T, D>), dim3(1), dim3(kMpCrown), 0, st, tree, t->cells, t->lvl_count,
-                       rounds ? t->later2 : t->later, rounds ? t->later2_mask : t->later_mask, t->max_cells, rounds ? 1 : 0);
-    NB_HIP(hipGetLastError());
-    return NBODY_OK;
-  }
-#ifdef NBODY_EXPERIMENTS
-  const int own = t->build == 2 ? 0 : (t->depth_hint < kMaxLevels<D> ? t->depth_hint : kMaxLevels<D>);
-  if (own < kMaxLevels<D>) {  // the levels below `own`, deepest first, in one launch (see ot_insert_run)
-    uint32_t grid = (t->n / 2 + 1 + kOB - 1) / kOB;
-    if (grid > uint32_t(t->ncu)) grid = uint32_t(t->ncu);
-    hipLaunchKernelGGL((ot_multipole_all_levels_kernel<T, D>), dim3(grid), dim3(kOB), 0, st, tree, t->cells, t->lvl_count,
-                       t->lvl_count + (kMaxLevels<D> + 4), t->lvl_count + (kMaxLevels<D> + 2), own, t->max_cells);
-    NB_HIP(hipGetLastError());
-  }
-#else
-  constexpr int own = kMaxLevels<D>;
-#endif
-  for (int l = own - 1; l >= 0; --l) {
-    uint64_t width = 1;
-    for (int j = 0; j < l && width < (uint64_t(1) << 40); ++j) width *= NCH;
-    const uint64_t cap_l = width < uint64_t(t->n / 2 + 1) ? width : uint64_t(t->n / 2 + 1);
-    hipLaunchKernelGGL((ot_multipole_level_kernel<T, D>), dim3(uint32_t((cap_l + kOB - 1) / kOB)), dim3(kOB), 0, st, l,
-                       tree, t->cells, t->lvl_count, t->max_cells);
-    NB_HIP(hipGetLastError());
+      if (p.route == ot_mp_route::chunks_round_crown) {
+        hipLaunchKernelGGL((ot_multipole_round_kernel<T, D>), dim3(p.round_blocks), dim3(kMpCrown), 0, st, tree, t->cells, t->lvl_count,
+                           t->later, t->later_mask, t->later2, t->later2_mask, p.max_cells);
+        NB_HIP(hipGetLastError());
+      }
+      hipLaunchKernelGGL((ot_multipole_crown_kernel<T, D>), dim3(1), dim3(kMpCrown), 0, st, tree, t->cells, t->lvl_count,
+                         p.crown_reads_later2 ? t->later2 : t->later, p.crown_reads_later2 ? t->later2_mask : t->later_mask,
+                         p.max_cells, p.crown_reads_later2 ? 1 : 0);
+      NB_HIP(hipGetLastError());
+      break;
+    case ot_mp_route::levels:  // deepest first
+      if (int r = ot_exp_multipole_rest<T, D>(t, st)) return r;
+      for (int l = p.own_levels - 1; l >= 0; --l) {
+        hipLaunchKernelGGL((ot_multipole_level_kernel<T, D>), dim3(p.level_grid[l]), dim3(kOB), 0, st, l, tree, t->cells, t->lvl_count,
+                           p.max_cells);
+        NB_HIP(hipGetLastError());
+      }
+      break;
   }
   return NBODY_OK;
 }
@@ -2998,7 +2987,7 @@ static int ot_walk_list(nbody_octree* t, const nbody_state* s, hipStream_t st, c
   const uint32_t* list = t->idx[t->sorted_buf];  // whole system: the sorted body indices themselves
   if (s->count < s->sz) {                        // shard window: compact the owned ones (scratch: the sort's other buffers)
     uint32_t* owned       = t->idx[1 - t->sorted_buf];
-    const uint32_t nblk   = (s->sz + kOC - 1) / kOC;
+    const uint32_t nblk   = ot_owned_blocks(s->sz);
     hipLaunchKernelGGL(ot_owned_count_kernel, dim3(nblk), dim3(kOC), 0, st, list, s->sz, s->first, s->count, t->hist);
     NB_HIP(hipGetLastError());
     hipLaunchKernelGGL(ot_owned_scan_kernel, dim3(1), dim3(kOC), 0, st, t->hist, nblk);
@@ -3011,20 +3000,18 @@ static int ot_walk_list(nbody_octree* t, const nbody_state* s, hipStream_t st, c
   return NBODY_OK;
 }
 
-// The refusal of a walk that exists in the compiler-scheduled form only ("softened": also the block steps', which take that walk —
-// octree_block.inc; "quadrupole"; "potential") after nbody_octree_set_walk(t, 2).
-static int ot_form1_only(const nbody_octree* t, const char* walk) {
-  if (t->walk == 2) {
-    set_error("octree walk: the %s walk exists in the compiler-scheduled form only (walk form 1 or 0 = auto), not as the ISA "
-              "visit round set by nbody_octree_set_walk(t, 2)", walk);
-    return NBODY_ERR_ARG;
-  }
-  return NBODY_OK;
+// The plan's refusal of a walk: the plain force walk (walk == nullptr) as the ISA round on a tree too large for it, or a walk that
+// exists in the compiler-scheduled form only ("softened": also the block steps', which take that walk — octree_block.inc;
+// "quadrupole"; "potential") after nbody_octree_set_walk(t, 2).
+static int ot_walk_refused(const nbody_octree* t, const char* walk) {
+  const char* why = walk ? t->plan.other_refusal : t->plan.mono_refusal;
+  if (!why) return NBODY_OK;
+  set_error(why, walk);
+  return NBODY_ERR_ARG;
 }
 
 // One launch for every walk kernel: `plain` and `counting` are its two COUNT instantiations (the tree's counters choose), out / scale
-// are a / c or phi / scale, `extra` is what the kernel takes behind the common arguments (e2, quad or nothing).  One block per wave
-// of 2^(6 - D) bodies; a well-formed tree is left after < capacity rounds.
+// are a / c or phi / scale, `extra` is what the kernel takes behind the common arguments (e2, quad or nothing).
 template <typename T, int D, typename... Extra>
 using ot_walk_kernel = void (*)(const ot_node<T>*, const ot_group<T, D>*, const uint32_t*, uint32_t, const T*, T*, T, uint32_t, T, uint32_t,
                                 const T*, uint32_t*, uint32_t*, Extra...);
@@ -3032,11 +3019,10 @@ template <typename T, int D, typename... Extra>
 static int ot_walk_launch(const nbody_octree* t, ot_walk_kernel<T, D, Extra...> plain, ot_walk_kernel<T, D, Extra...> counting,
                           const uint32_t* list, uint32_t nlist, const T* x, T* out, T scale, uint32_t first, double theta,
                           hipStream_t st, Extra... extra) {
-  const uint32_t per_wave = 64u >> D;
-  hipLaunchKernelGGL(t->counters_on ? counting : plain, dim3((nlist + per_wave - 1) / per_wave), dim3(64), 0, st,
+  hipLaunchKernelGGL(t->counters_on ? counting : plain, dim3(ot_walk_grid(D, nlist)), dim3(64), 0, st,
                      static_cast<const ot_node<T>*>(t->rootrec), static_cast<const ot_group<T, D>*>(t->groups), list, nlist, x, out,
-                     scale, first, static_cast<T>(theta), t->step_budget ? t->step_budget : t->capacity,
-                     static_cast<const T*>(t->root), ot_flags(t), t->counters, extra...);
+                     scale, first, static_cast<T>(theta), t->plan.budget, static_cast<const T*>(t->root), ot_flags(t), t->counters,
+                     extra...);
   NB_HIP(hipGetLastError());
   return NBODY_OK;
 }
@@ -3045,7 +3031,7 @@ static int ot_walk_launch(const nbody_octree* t, ot_walk_kernel<T, D, Extra...> 
 template <typename T, int D>
 static int ot_force_run(nbody_octree* t, const nbody_state* s, double theta, hipStream_t st, ot_kind kind = kOtMono, T e2 = T(0)) {
   if (kind != kOtMono)
-    if (int r = ot_form1_only(t, kind == kOtSoft ? "softened" : "quadrupole")) return r;
+    if (int r = ot_walk_refused(t, kind == kOtSoft ? "softened" : "quadrupole")) return r;
   if (s->count == 0) return NBODY_OK;
   const uint32_t* list = nullptr;
   if (int r = ot_walk_list(t, s, st, &list)) return r;
@@ -3056,19 +3042,8 @@ static int ot_force_run(nbody_octree* t, const nbody_state* s, double theta, hip
   if (kind == kOtSoft) return launch(ot_force_softened_kernel<T, D, false>, ot_force_softened_kernel<T, D, true>, e2);
   if (kind == kOtQuad)
     return launch(ot_force_quadrupole_kernel<T, D, false>, ot_force_quadrupole_kernel<T, D, true>, static_cast<const T*>(t->quad));
-  // the visit round written as ISA (ot_force_isa_kernel, ot_force_isa_f32_kernel; 2D and 3D), while 24-bit group numbers times the group
-  // size stay inside 32-bit offsets; nbody_octree_set_walk(t, 1) keeps the compiler-scheduled kernel (tests compare the two bitwise)
-  bool isa = false;
-  {
-    const char* fe = experiment_env("NBODY_OT_FORM");  // -DNBODY_EXPERIMENTS builds only
-    isa = t->walk != 1 && !(fe && fe[0] == '1') &&
-          uint64_t(t->max_cells) * sizeof(ot_group<T, D>) < (1ull << 32) && t->max_cells < (1u << 24);
-  }
-  if (t->walk == 2 && !isa) {
-    set_error("octree walk: the ISA visit round needs the tree within 24-bit group numbers and 32-bit group offsets");
-    return NBODY_ERR_ARG;
-  }
-  if (isa) {
+  if (int r = ot_walk_refused(t, nullptr)) return r;
+  if (t->plan.isa) {  // ot_force_isa_kernel, ot_force_isa_f32_kernel
     if constexpr (sizeof(T) == 8) return launch(ot_force_isa_kernel<D, false>, ot_force_isa_kernel<D, true>);
     else return launch(ot_force_isa_f32_kernel<D, false>, ot_force_isa_f32_kernel<D, true>);
   }
@@ -3079,7 +3054,7 @@ static int ot_force_run(nbody_octree* t, const nbody_state* s, double theta, hip
 // only; shard windows through the force walk's owned list.
 template <typename T, int D>
 static int ot_potential_run(nbody_octree* t, const nbody_state* s, double theta, hipStream_t st, ot_kind kind, T e2, T* phi, T scale) {
-  if (int r = ot_form1_only(t, "potential")) return r;
+  if (int r = ot_walk_refused(t, "potential")) return r;
   if (s->count == 0) return NBODY_OK;
   const uint32_t* list = nullptr;
   if (int r = ot_walk_list(t, s, st, &list)) return r;
@@ -3099,24 +3074,20 @@ static int ot_potential_run(nbody_octree* t, const nbody_state* s, double theta,
 // root that holds one body (or none) has Q = 0 and no launch writes it.
 template <typename T, int D>
 static int ot_quad_run(nbody_octree* t, hipStream_t st) {
-  constexpr uint32_t NCH = 1u << D;
-  const ot_tree<T, D> tree{static_cast<ot_group<T, D>*>(t->groups), static_cast<ot_node<T>*>(t->rootrec)};
-  T* quad              = static_cast<T*>(t->quad);
-  const bool one_pass  = ot_one_pass(t);
+  const ot_plan& p         = t->plan;
+  const ot_tree<T, D> tree = ot_view<T, D>(t);
+  T* quad                  = static_cast<T*>(t->quad);
   NB_HIP(hipMemsetAsync(quad, 0, sizeof(T) * kOtQS<D>, st));
   hipLaunchKernelGGL((ot_quadrupole_deep_kernel<T, D>), dim3(64), dim3(64), 0, st, tree, quad, t->cells,
-                     one_pass ? t->tops : static_cast<const ot_cell*>(nullptr), t->lvl_count, t->capacity);
+                     p.one_pass ? t->tops : static_cast<const ot_cell*>(nullptr), t->lvl_count, p.capacity);
   NB_HIP(hipGetLastError());
   for (int l = kMaxLevels<D> - 1; l >= 0; --l) {
-    if (one_pass) {
-      hipLaunchKernelGGL((ot_quadrupole_ranks_level_kernel<T, D>), dim3((t->max_cells + kOB - 1) / kOB), dim3(kOB), 0, st, l, tree, quad,
-                         t->cells, t->lvl_count, t->capacity, t->max_cells);
+    if (p.one_pass) {
+      hipLaunchKernelGGL((ot_quadrupole_ranks_level_kernel<T, D>), dim3(p.ranks_grid), dim3(kOB), 0, st, l, tree, quad, t->cells,
+                         t->lvl_count, p.capacity, p.max_cells);
     } else {
-      uint64_t width = 1;
-      for (int j = 0; j < l && width < (uint64_t(1) << 40); ++j) width *= NCH;
-      const uint64_t cap_l = width < uint64_t(t->n / 2 + 1) ? width : uint64_t(t->n / 2 + 1);
-      hipLaunchKernelGGL((ot_quadrupole_level_kernel<T, D>), dim3(uint32_t((cap_l + kOB - 1) / kOB)), dim3(kOB), 0, st, l, tree, quad,
-                         t->cells, t->lvl_count, t->max_cells);
+      hipLaunchKernelGGL((ot_quadrupole_level_kernel<T, D>), dim3(p.level_grid[l]), dim3(kOB), 0, st, l, tree, quad, t->cells,
+                         t->lvl_count, p.max_cells);
     }
     NB_HIP(hipGetLastError());
   }
@@ -3133,39 +3104,23 @@ extern "C" int nbody_octree_set_walk(nbody_octree* t, int mode) {
   NB_ARG(t != nullptr, "nbody_octree is NULL");
   NB_ARG(mode >= 0 && mode <= 2, "walk form must be 0 (auto), 1 (compiler-scheduled) or 2 (visit round as ISA), got %d", mode);
   t->walk = mode;
+  ot_replan(t);
   return NBODY_OK;
 }
 
 extern "C" int nbody_octree_set_build(nbody_octree* t, int mode) {
   NB_ARG(t != nullptr, "nbody_octree is NULL");
-#ifdef NBODY_EXPERIMENTS
-  NB_ARG(mode >= 0 && mode <= 4,
-         "build form must be 0 (auto), 1 (one launch per level), 2 (all levels in one launch), 3 (one pass over the sorted keys) or 4 "
-         "(one launch per level the last tree used, one for the rest), got %d", mode);
-#else
-  NB_ARG(mode == 0 || mode == 1 || mode == 3, "build form must be 0 (auto), 1 (breadth-first, one launch per level) or 3 (one pass over the sorted keys), got %d%s",
-         mode, mode == 2 || mode == 4 ? " — that form exists only in the -DNBODY_EXPERIMENTS build (make experiments)" : "");
-#endif
-  if (mode != t->build) t->inserted = t->have_tree = t->have_quad = false;  // the forms lay the cell list out differently: a tree inserted by one
-                                                             // is not the other's to finish (insert again after a change)
+  if (int r = ot_check_build_form(t, mode)) return r;
+  if (mode != t->build) t->phase.build_form_changed();
   t->build = mode;
-  if (mode != 4) t->depth_hint = 64;  // 1: every level its own launch, whatever earlier trees looked like
+  ot_replan(t);
   return NBODY_OK;
 }
-
-#ifdef NBODY_EXPERIMENTS
-// wall_clock64() stamps (100 MHz) of the last ot_insert_small_kernel launch on the current device: entry, keys, sort, numbering,
-// cells, deep cells (tools/time_small_insert_phases.py)
-extern "C" int nbody_exp_octree_small_stamps(uint64_t* out8) {
-  NB_HIP(hipDeviceSynchronize());
-  NB_HIP(hipMemcpyFromSymbol(out8, HIP_SYMBOL(nbody::ot_small_stamps), sizeof(uint64_t) * 8));
-  return NBODY_OK;
-}
-#endif
 
 extern "C" int nbody_octree_set_step_budget(nbody_octree* t, uint32_t steps) {
   NB_ARG(t != nullptr, "nbody_octree is NULL");
   t->step_budget = steps;
+  ot_replan(t);
   return NBODY_OK;
 }
 
@@ -3179,53 +3134,22 @@ extern "C" int nbody_octree_create_on(nbody_octree** out, int dtype, int dim, ui
   t->dim   = dim;
   t->n     = n;
   t->tsz   = dtype == NBODY_F32 ? 4 : 8;
-  const uint32_t nch = 1u << dim;
-  const uint64_t cap = uint64_t(nch) * n < 1000 ? 1000 : uint64_t(nch) * n;  // System::max_tree_node_size (src/system.h:30)
-  t->capacity        = uint32_t(cap);
-  t->max_cells       = t->capacity / nch + 1;
-  t->bounds_blocks   = uint32_t((uint64_t(n) * dim + kOB * 8 - 1) / (kOB * 8));
-  if (t->bounds_blocks > 1024) t->bounds_blocks = 1024;
-  const int maxl = dim == 3 ? kMaxLevels<3> : kMaxLevels<2>;
-  t->mem.alloc(&t->root, t->tsz * (dim + 1));
-  t->mem.alloc(&t->partials, t->tsz * 2 * t->bounds_blocks);
-  t->mem.alloc(&t->keys[0], sizeof(uint64_t) * size_t(n));
-  t->mem.alloc(&t->keys[1], sizeof(uint64_t) * size_t(n));
-  t->mem.alloc(&t->idx[0], sizeof(uint32_t) * size_t(n));
-  t->mem.alloc(&t->idx[1], sizeof(uint32_t) * size_t(n));
-  t->mem.alloc(&t->hist, sizeof(uint32_t) * radix_sort_scratch_words(n));
-  t->mem.alloc(&t->rootrec, 64);
-  t->group_bytes = dtype == NBODY_F32 ? (dim == 3 ? sizeof(ot_group<float, 3>) : sizeof(ot_group<float, 2>))
-                                      : (dim == 3 ? sizeof(ot_group<double, 3>) : sizeof(ot_group<double, 2>));
-  t->mem.alloc(&t->groups, t->group_bytes * size_t(t->max_cells));
-  t->mem.alloc(&t->cells, sizeof(ot_cell) * size_t(t->max_cells));
-  t->mem.alloc(&t->lvl_count, sizeof(uint32_t) * size_t(maxl + 8));  // level counts, deep groups, flags, two grid-barrier counters, ...
-  {
-    const size_t nblk = size_t(n) / kLcpB + 1;
-    t->mem.alloc(&t->tops, sizeof(ot_cell) * (size_t(n) / 2 + 2));
-    t->mem.alloc(&t->lcp, size_t(n) + 2);
-    t->mem.alloc(&t->plocal, sizeof(uint32_t) * (size_t(n) + 1));
-    t->mem.alloc(&t->bsum, sizeof(uint32_t) * nblk);
-    t->mem.alloc(&t->bhist, sizeof(uint32_t) * nblk * size_t(maxl + 1));
-    t->mem.alloc(&t->rankpos, sizeof(uint32_t) * size_t(t->max_cells));
-    t->mem.alloc(&t->later, sizeof(uint32_t) * (size_t(t->max_cells) / kMpChunk + 2) * size_t(maxl));
-    t->mem.alloc(&t->later_mask, sizeof(uint32_t) * (size_t(t->max_cells) / kMpChunk + 2));
-    {
-      const size_t blocks2 = ((size_t(t->max_cells) / kMpChunk + 2) * size_t(maxl) + kMpCrown - 1) / kMpCrown + 1;
-      t->mem.alloc(&t->later2, sizeof(uint32_t) * blocks2 * size_t(maxl));
-      t->mem.alloc(&t->later2_mask, sizeof(uint32_t) * blocks2);
-    }
+  const char* what = "hipGetDeviceProperties";
+  hipError_t e     = ot_exp_create(t);
+  ot_replan(t);
+  void** const buffers[kOtCreateBuffers] = {
+      &t->root, &t->partials, (void**)&t->keys[0], (void**)&t->keys[1], (void**)&t->idx[0], (void**)&t->idx[1], (void**)&t->hist,
+      &t->rootrec, &t->groups, (void**)&t->cells, (void**)&t->lvl_count, (void**)&t->tops, (void**)&t->lcp, (void**)&t->plocal,
+      (void**)&t->bsum, (void**)&t->bhist, (void**)&t->rankpos, (void**)&t->later, (void**)&t->later_mask, (void**)&t->later2,
+      (void**)&t->later2_mask};  // in ot_buffer's order
+  if (e == hipSuccess) {
+    what = "nbody_octree_create allocation";
+    for (int b = 0; b < kOtCreateBuffers; ++b) t->mem.alloc(buffers[b], t->plan.bytes[b]);
+    e = t->mem.error();
   }
-  hipError_t e     = t->mem.error();
-  const char* what = "nbody_octree_create allocation";
   if (e == hipSuccess) {
     what = "hipMemset";
-    e    = hipMemset(t->lvl_count, 0, sizeof(uint32_t) * size_t(maxl + 8));
-  }
-  if (e == hipSuccess) {
-    what = "hipGetDeviceProperties";
-    hipDeviceProp_t prop;
-    e      = hipGetDeviceProperties(&prop, device);
-    t->ncu = e == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 1;
+    e    = hipMemset(t->lvl_count, 0, t->plan.bytes[kBufLvlCount]);
   }
   return create_finish(out, t, nbody_octree_destroy, e, what);
 }
@@ -3237,12 +3161,8 @@ extern "C" void nbody_octree_destroy(nbody_octree* t) {
 }
 
 extern "C" int nbody_octree_clear(nbody_octree* t, void* stream) {
-  NB_ARG(t != nullptr, "nbody_octree is NULL");
-  if (int r = check_same_device(t->device, as_stream(stream), "nbody_octree")) return r;
-  // every node the build allocates is fully rewritten by it: nothing to reset but the phase flags
-  t->inserted  = false;
-  t->have_tree = false;
-  t->have_quad = false;
+  if (int r = ot_check_handle(t, stream)) return r;
+  t->phase.cleared();
   return NBODY_OK;
 }
 
@@ -3253,50 +3173,40 @@ extern "C" int nbody_octree_compute_bounds(nbody_octree* t, const nbody_state* s
     using TG = decltype(tg);
     return ot_bounds_run<typename TG::type, TG::dim>(t, s, as_stream(stream));
   });
-  if (r == NBODY_OK) t->have_bounds = true;
+  if (r == NBODY_OK) t->phase.bounds_done();
   return r;
 }
 
 extern "C" int nbody_octree_insert(nbody_octree* t, const nbody_state* s, void* stream) {
   if (int r = ot_check(t, s, stream)) return r;
   device_guard guard(t->device);
-  if (!t->have_bounds) {
-    set_error("nbody_octree_insert before nbody_octree_compute_bounds");
-    return NBODY_ERR_STATE;
-  }
+  if (int r = ot_need(t, ot_phase::bounds, "nbody_octree_insert")) return r;
   int r = dispatch(s->dtype, s->dim, [&](auto tg) {
     using TG = decltype(tg);
     return ot_insert_run<typename TG::type, TG::dim>(t, s, as_stream(stream));
   });
-  t->have_quad = false;  // (also when the insert failed: the tree is no longer the one the quadrupoles describe)
-  if (r == NBODY_OK) t->inserted = true;
+  if (r == NBODY_OK) t->phase.insert_done();
+  else t->phase.insert_failed();
   return r;
 }
 
 extern "C" int nbody_octree_compute_tree(nbody_octree* t, void* stream) {
-  NB_ARG(t != nullptr, "nbody_octree is NULL");
-  if (int r = check_same_device(t->device, as_stream(stream), "nbody_octree")) return r;
+  if (int r = ot_check_handle(t, stream)) return r;
   device_guard guard(t->device);
-  if (!t->inserted) {
-    set_error("nbody_octree_compute_tree before nbody_octree_insert");
-    return NBODY_ERR_STATE;
-  }
+  if (int r = ot_need(t, ot_phase::inserted, "nbody_octree_compute_tree")) return r;
   int r = dispatch(t->dtype, t->dim, [&](auto tg) {
     using TG = decltype(tg);
     return ot_tree_run<typename TG::type, TG::dim>(t, as_stream(stream));
   });
-  t->have_quad = false;
-  if (r == NBODY_OK) t->have_tree = true;
+  if (r == NBODY_OK) t->phase.tree_done();
+  else t->phase.tree_failed();
   return r;
 }
 
 extern "C" int nbody_octree_compute_force(nbody_octree* t, const nbody_state* s, double theta, void* stream) {
   if (int r = ot_check(t, s, stream)) return r;
   device_guard guard(t->device);
-  if (!t->have_tree) {
-    set_error("nbody_octree_compute_force before nbody_octree_compute_tree");
-    return NBODY_ERR_STATE;
-  }
+  if (int r = ot_need(t, ot_phase::tree, "nbody_octree_compute_force")) return r;
   return dispatch(s->dtype, s->dim, [&](auto tg) {
     using TG = decltype(tg);
     return ot_force_run<typename TG::type, TG::dim>(t, s, theta, as_stream(stream));
@@ -3306,45 +3216,32 @@ extern "C" int nbody_octree_compute_force(nbody_octree* t, const nbody_state* s,
 extern "C" int nbody_octree_compute_softened_force(nbody_octree* t, const nbody_state* s, double theta, double eps, void* stream) {
   NB_ARG(t != nullptr, "nbody_octree is NULL");
   if (int r = check_state(s)) return r;
-  int r = dispatch(s->dtype, s->dim, [&](auto tg) {
-    using T = typename decltype(tg)::type;
-    T e2;
-    return check_softening<T>(eps, &e2);
-  });
-  if (r) return r;
-  if (int r2 = ot_check(t, s, stream)) return r2;
+  double e2 = 0.0;
+  if (int r = ot_softening(s, eps, &e2)) return r;
+  if (int r = ot_check(t, s, stream)) return r;
   device_guard guard(t->device);
-  if (!t->have_tree) {
-    set_error("nbody_octree_compute_softened_force before nbody_octree_compute_tree");
-    return NBODY_ERR_STATE;
-  }
+  if (int r = ot_need(t, ot_phase::tree, "nbody_octree_compute_softened_force")) return r;
   return dispatch(s->dtype, s->dim, [&](auto tg) {
     using TG = decltype(tg);
     using T  = typename TG::type;
-    T e2;
-    (void)check_softening<T>(eps, &e2);
-    return ot_force_run<T, TG::dim>(t, s, theta, as_stream(stream), kOtSoft, e2);
+    return ot_force_run<T, TG::dim>(t, s, theta, as_stream(stream), kOtSoft, static_cast<T>(e2));
   });
 }
 
 extern "C" int nbody_octree_enable_counters(nbody_octree* t, int on) {
   NB_ARG(t != nullptr, "nbody_octree is NULL");
   device_guard guard(t->device);
-  if (on && !t->counters) NB_HIP(t->mem.alloc_late(&t->counters, sizeof(uint32_t) * 2 * size_t(t->n)));
+  if (on && !t->counters) NB_HIP(t->mem.alloc_late(&t->counters, t->plan.bytes[kBufCounters]));
   t->counters_on = on != 0;
   return NBODY_OK;
 }
 
 extern "C" int nbody_octree_info(nbody_octree* t, uint32_t* tree_size, void* root_mass, void* stream) {
-  NB_ARG(t != nullptr, "nbody_octree is NULL");
-  if (int r = check_same_device(t->device, as_stream(stream), "nbody_octree")) return r;
+  if (int r = ot_check_handle(t, stream)) return r;
   device_guard guard(t->device);
-  if (!t->inserted) {
-    set_error("nbody_octree_info before nbody_octree_insert");
-    return NBODY_ERR_STATE;
-  }
+  if (int r = ot_need(t, ot_phase::inserted, "nbody_octree_info")) return r;
   hipStream_t st = as_stream(stream);
-  const int maxl = t->dim == 3 ? kMaxLevels<3> : kMaxLevels<2>;
+  const int maxl = t->plan.maxl;
   uint32_t lv[40];
   NB_HIP(hipMemcpyAsync(lv, t->lvl_count, sizeof(uint32_t) * (maxl + 3), hipMemcpyDeviceToHost, st));
   char rec[32];
@@ -3358,27 +3255,19 @@ extern "C" int nbody_octree_info(nbody_octree* t, uint32_t* tree_size, void* roo
     return NBODY_ERR_STATE;
   }
   if (flags & kFlagCapacity) {
-    set_error("octree node pool exhausted (capacity %u nodes = System::max_tree_node_size)", t->capacity);
+    set_error("octree node pool exhausted (capacity %u nodes = System::max_tree_node_size)", t->plan.capacity);
     return NBODY_ERR_STATE;
   }
-  if (flags & kFlagBarrier) {
-    set_error("octree build: a grid barrier of the all-level kernels timed out (the blocks of one launch were not all running "
-              "within seconds: is the GPU shared?); nbody_octree_set_build(t, 1) builds with one launch per level");
-    return NBODY_ERR_STATE;
-  }
+  if (int r = ot_exp_info(t, flags, lv)) return r;
   if (flags & kFlagStack) {
     set_error("octree walk: more pending nodes than the per-body stack holds (a tree far deeper than %d levels)", maxl);
     return NBODY_ERR_STATE;
   }
   if (flags & kFlagWalk) {
-    set_error("octree walk: a body was still walking after %u visit rounds (%s)", t->step_budget ? t->step_budget : t->capacity,
-              t->step_budget ? "the budget set with nbody_octree_set_step_budget" : "more than the tree has nodes: the tree is damaged");
+    set_error("octree walk: a body was still walking after %u visit rounds (%s)", t->plan.budget,
+              t->plan.budget_set ? "the budget set with nbody_octree_set_step_budget" : "more than the tree has nodes: the tree is damaged");
     return NBODY_ERR_STATE;
   }
-  int deepest = -1;
-  for (int l = 0; l < maxl; ++l)
-    if (lv[l] != 0) deepest = l;
-  if (t->build == 4) t->depth_hint = deepest + 3 < maxl ? deepest + 3 : maxl;  // the levels the next builds launch one by one
   uint64_t cells = 0;
   for (int l = 0; l <= maxl + 1; ++l) cells += lv[l];  // breadth-first levels, then the groups of the deep build
   if (tree_size) *tree_size = uint32_t(1 + cells * (1u << t->dim));  // next_free_child_group (src/octree.h:152)
@@ -3391,30 +3280,16 @@ extern "C" int nbody_octree_read_counters(nbody_octree* t, uint32_t* host_out, s
   NB_ARG(t->counters != nullptr, "counters were never enabled");
   if (int r = check_same_device(t->device, as_stream(stream), "nbody_octree")) return r;
   device_guard guard(t->device);
-  NB_ARG(bytes == sizeof(uint32_t) * 2 * size_t(t->n), "expected %zu bytes", sizeof(uint32_t) * 2 * size_t(t->n));
+  NB_ARG(bytes == t->plan.bytes[kBufCounters], "expected %zu bytes", t->plan.bytes[kBufCounters]);
   NB_HIP(hipMemcpyAsync(host_out, t->counters, bytes, hipMemcpyDeviceToHost, as_stream(stream)));
   NB_HIP(hipStreamSynchronize(as_stream(stream)));
   return NBODY_OK;
 }
 
-// Host-side phase tracking in call order: a recorded step replays its calls in the order they were recorded, so the checks hold
-// for graphs too.
-static int ot_quad_ready(nbody_octree* t, const char* what) {
-  if (!t->have_quad) {
-    set_error("%s before nbody_octree_compute_quadrupoles (which must follow the latest clear / insert / compute_tree / set_build)", what);
-    return NBODY_ERR_STATE;
-  }
-  return NBODY_OK;
-}
-
 extern "C" int nbody_octree_compute_quadrupoles(nbody_octree* t, void* stream) {
-  NB_ARG(t != nullptr, "nbody_octree is NULL");
-  if (int r = check_same_device(t->device, as_stream(stream), "nbody_octree")) return r;
+  if (int r = ot_check_handle(t, stream)) return r;
   device_guard guard(t->device);
-  if (!t->have_tree) {
-    set_error("nbody_octree_compute_quadrupoles before nbody_octree_compute_tree");
-    return NBODY_ERR_STATE;
-  }
+  if (int r = ot_need(t, ot_phase::tree, "nbody_octree_compute_quadrupoles")) return r;
   hipStream_t st = as_stream(stream);
   if (!t->quad) {
     if (capture_id(st) != 0) {
@@ -3422,14 +3297,13 @@ extern "C" int nbody_octree_compute_quadrupoles(nbody_octree* t, void* stream) {
                 "(outside nbody_graph_begin/end)");
       return NBODY_ERR_STATE;
     }
-    const size_t qs = (t->dim == 3 ? 6 : 3) + size_t(t->dim);  // kOtQS: every node the groups can hold, and the root
-    NB_HIP(t->mem.alloc_late(&t->quad, t->tsz * qs * (size_t(t->max_cells) * (size_t(1) << t->dim) + 1)));
+    NB_HIP(t->mem.alloc_late(&t->quad, t->plan.bytes[kBufQuad]));
   }
   int r = dispatch(t->dtype, t->dim, [&](auto tg) {
     using TG = decltype(tg);
     return ot_quad_run<typename TG::type, TG::dim>(t, st);
   });
-  if (r == NBODY_OK) t->have_quad = true;
+  if (r == NBODY_OK) t->phase.quadrupoles_done();
   return r;
 }
 
@@ -3437,7 +3311,7 @@ extern "C" int nbody_octree_compute_quadrupole_force(nbody_octree* t, const nbod
   if (int r = check_state(s)) return r;  // (before the tree: a bad state is reported as such whatever the tree)
   if (int r = ot_check(t, s, stream)) return r;
   device_guard guard(t->device);
-  if (int r = ot_quad_ready(t, "nbody_octree_compute_quadrupole_force")) return r;
+  if (int r = ot_need(t, ot_phase::quadrupoles, "nbody_octree_compute_quadrupole_force")) return r;
   return dispatch(s->dtype, s->dim, [&](auto tg) {
     using TG = decltype(tg);
     using T  = typename TG::type;
@@ -3449,8 +3323,8 @@ extern "C" int nbody_octree_read_root_quadrupole(nbody_octree* t, void* host_out
   NB_ARG(t != nullptr && host_out != nullptr, "NULL argument");
   if (int r = check_same_device(t->device, as_stream(stream), "nbody_octree")) return r;
   device_guard guard(t->device);
-  if (int r = ot_quad_ready(t, "nbody_octree_read_root_quadrupole")) return r;
-  const size_t nq = t->dim == 3 ? 6 : 3;
+  if (int r = ot_need(t, ot_phase::quadrupoles, "nbody_octree_read_root_quadrupole")) return r;
+  const size_t nq = t->dim == 3 ? kOtNQ<3> : kOtNQ<2>;
   NB_HIP(hipMemcpyAsync(host_out, t->quad, t->tsz * nq, hipMemcpyDeviceToHost, as_stream(stream)));
   NB_HIP(hipStreamSynchronize(as_stream(stream)));
   return NBODY_OK;
@@ -3464,10 +3338,7 @@ static int ot_potential_entry(nbody_octree* t, const nbody_state* s, void* phi, 
   NB_ARG(phi != nullptr, "%s: phi is NULL", what);
   if (int r = ot_check(t, s, stream)) return r;
   device_guard guard(t->device);
-  if (!t->have_tree) {
-    set_error("%s before nbody_octree_compute_tree", what);
-    return NBODY_ERR_STATE;
-  }
+  if (int r = ot_need(t, ot_phase::tree, what)) return r;
   return dispatch(s->dtype, s->dim, [&](auto tg) {
     using TG = decltype(tg);
     return run(tg, static_cast<typename TG::type*>(phi), -static_cast<typename TG::type>(s->c));
@@ -3485,17 +3356,12 @@ extern "C" int nbody_octree_compute_potential(nbody_octree* t, const nbody_state
 extern "C" int nbody_octree_compute_softened_potential(nbody_octree* t, const nbody_state* s, double theta, double eps, void* phi,
                                                        void* stream) {
   if (int r = check_state(s)) return r;
-  if (int r = dispatch(s->dtype, s->dim, [&](auto tg) {
-        typename decltype(tg)::type e2;
-        return check_softening(eps, &e2);
-      }))
-    return r;
+  double e2 = 0.0;
+  if (int r = ot_softening(s, eps, &e2)) return r;
   return ot_potential_entry(t, s, phi, stream, "nbody_octree_compute_softened_potential", [&](auto tg, auto* p, auto scale) {
     using TG = decltype(tg);
     using T  = typename TG::type;
-    T e2;
-    (void)check_softening<T>(eps, &e2);
-    return ot_potential_run<T, TG::dim>(t, s, theta, as_stream(stream), kOtSoft, e2, p, scale);
+    return ot_potential_run<T, TG::dim>(t, s, theta, as_stream(stream), kOtSoft, static_cast<T>(e2), p, scale);
   });
 }
 
@@ -3503,7 +3369,7 @@ extern "C" int nbody_octree_compute_quadrupole_potential(nbody_octree* t, const 
   return ot_potential_entry(t, s, phi, stream, "nbody_octree_compute_quadrupole_potential", [&](auto tg, auto* p, auto scale) {
     using TG = decltype(tg);
     using T  = typename TG::type;
-    if (int r = ot_quad_ready(t, "nbody_octree_compute_quadrupole_potential")) return r;
+    if (int r = ot_need(t, ot_phase::quadrupoles, "nbody_octree_compute_quadrupole_potential")) return r;
     return ot_potential_run<T, TG::dim>(t, s, theta, as_stream(stream), kOtQuad, T(0), p, scale);
   });
 }
@@ -3517,13 +3383,9 @@ extern "C" int nbody_octree_calc_energies(nbody_octree* t, const nbody_state* s,
   NB_ARG(s->first == 0 && s->count == s->sz, "nbody_octree_calc_energies needs the whole system (first=0, count=sz)");
   NB_ARG(eps >= 0.0 && eps <= DBL_MAX, "nbody_octree_calc_energies: eps = %g must be 0 (unsoftened) or a finite softening length > 0", eps);
   NB_ARG(!(quadrupole && eps > 0.0), "nbody_octree_calc_energies: the quadrupole term and softening cannot be combined");
-  if (eps > 0.0) {
-    if (int r = dispatch(s->dtype, s->dim, [&](auto tg) {
-          typename decltype(tg)::type e2;
-          return check_softening(eps, &e2);
-        }))
-      return r;
-  }
+  double e2 = 0.0;
+  if (eps > 0.0)
+    if (int r = ot_softening(s, eps, &e2)) return r;
   if (int r = ot_check(t, s, stream)) return r;
   device_guard guard(t->device);
   hipStream_t st = as_stream(stream);
@@ -3531,27 +3393,22 @@ extern "C" int nbody_octree_calc_energies(nbody_octree* t, const nbody_state* s,
     set_error("nbody_octree_calc_energies is blocking: it cannot be recorded (call it outside nbody_graph_begin/end)");
     return NBODY_ERR_STATE;
   }
-  if (!t->have_tree) {
-    set_error("nbody_octree_calc_energies before nbody_octree_compute_tree");
-    return NBODY_ERR_STATE;
-  }
+  if (int r = ot_need(t, ot_phase::tree, "nbody_octree_calc_energies")) return r;
   if (quadrupole)
-    if (int r = ot_quad_ready(t, "nbody_octree_calc_energies(quadrupole)")) return r;
+    if (int r = ot_need(t, ot_phase::quadrupoles, "nbody_octree_calc_energies(quadrupole)")) return r;
   struct fill_ctx {
     nbody_octree* t;
     const nbody_state* s;
-    double theta, eps;
+    double theta, e2;
     ot_kind kind;
     hipStream_t st;
-  } ctx{t, s, theta, eps, quadrupole ? kOtQuad : eps > 0.0 ? kOtSoft : kOtMono, st};
+  } ctx{t, s, theta, e2, quadrupole ? kOtQuad : eps > 0.0 ? kOtSoft : kOtMono, st};
   auto fill = [](void* sums, void* p) -> int {
     const fill_ctx& c = *static_cast<const fill_ctx*>(p);
     return dispatch(c.s->dtype, c.s->dim, [&](auto tg) {
       using TG = decltype(tg);
       using T  = typename TG::type;
-      T e2     = T(0);
-      if (c.kind == kOtSoft) (void)check_softening<T>(c.eps, &e2);
-      return ot_potential_run<T, TG::dim>(c.t, c.s, c.theta, c.st, c.kind, e2, static_cast<T*>(sums), T(1));
+      return ot_potential_run<T, TG::dim>(c.t, c.s, c.theta, c.st, c.kind, static_cast<T>(c.e2), static_cast<T*>(sums), T(1));
     });
   };
   return energies_from_sums(s, st, fill, &ctx, kinetic_out, potential_out);

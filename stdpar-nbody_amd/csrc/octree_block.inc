@@ -134,7 +134,7 @@ static int otb_check(nbody_octree_block* h, nbody_octree* t, const nbody_state* 
               is_start ? "starts a run of block steps, which are not recordable" : "is blocking (it reads the size of the active set back)");
     return NBODY_ERR_STATE;
   }
-  if (int r = ot_form1_only(t, "softened")) return r;  // after nbody_octree_set_walk(t, 2): the softened walk's refusal
+  if (int r = ot_walk_refused(t, "softened")) return r;  // after nbody_octree_set_walk(t, 2): the softened walk's refusal
   if (!is_start) {
     if (!h->on) {
       set_error("%s before nbody_octree_block_start on this handle", who);
@@ -149,13 +149,13 @@ static int otb_check(nbody_octree_block* h, nbody_octree* t, const nbody_state* 
 // bounds, insert, multipoles on the view `s` (clear has nothing to launch): the tree's phase flags as after the four phase calls
 template <typename T, int D>
 static int otb_build(nbody_octree* t, const nbody_state* s, hipStream_t st) {
-  t->inserted = t->have_tree = t->have_quad = false;
+  t->phase.cleared();
   if (int r = ot_bounds_run<T, D>(t, s, st)) return r;
-  t->have_bounds = true;
+  t->phase.bounds_done();
   if (int r = ot_insert_run<T, D>(t, s, st)) return r;
-  t->inserted = true;
+  t->phase.insert_done();
   if (int r = ot_tree_run<T, D>(t, st)) return r;
-  t->have_tree = true;
+  t->phase.tree_done();
   return NBODY_OK;
 }
 
