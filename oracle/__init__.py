@@ -214,6 +214,38 @@ def bvh_force(s, tr, theta, want_counts=False):
     return counts
 
 
+class BvhWideWalk:
+    """What bvh_walk_wide returns, one row per target: a (nt, D) and scale (nt,) float64; counts (nt, 4) and near_nodes (nt,)
+    uint32."""
+
+
+def bvh_walk_wide(s, tr, theta, targets=None):
+    """The walk of bvh_force on a state `s` that is already in key order and its bvh_build tree `tr` — the same T tree, the opening
+    test bw * bw < theta^2 d2 in T on the reference's unfused d2, the same order of visits — with everything a body accumulates
+    formed and summed in the wider type (double for float, long double for double), for the bodies in `targets` (an index array;
+    None = all).  Over the accepted entries, node monopoles and bodies alike, with d = p - x_i, r2 = |d|^2, r = sqrt(r2) and the
+    reference's eps(T) kept (all_pairs_force_wide's pair form):
+      a = c sum m d / (r2 r + eps(T))                     scale = |c| sum |m| r / (r2 r + eps(T))
+    counts = bvh_force's {internal-node tests, leaf-pair visits, monopole terms, body terms}; near_nodes = the accepted nodes
+    whose d2 (in T) is below 2^-16, where the product's double term changes form."""
+    L = lib()
+    try:
+        fn = L.oracle_bvh_walk_wide
+    except AttributeError:
+        raise RuntimeError(f"{LIB_PATH} has no oracle_bvh_walk_wide: the library is older than oracle/nbody_oracle.c; "
+                           "rebuild it (make -C oracle oracle)") from None
+    t = np.arange(s.n, dtype=np.uint32) if targets is None else np.ascontiguousarray(targets, dtype=np.uint32)
+    assert t.ndim == 1 and (t.size == 0 or int(t.max()) < s.n)
+    w = BvhWideWalk()
+    w.a, w.scale = np.zeros((t.size, s.dim), np.float64), np.zeros(t.size, np.float64)
+    w.counts, w.near_nodes = np.zeros((t.size, 4), np.uint32), np.zeros(t.size, np.uint32)
+    r = fn(s.dtype, s.dim, _p(s.m), _p(s.x), C.c_double(s.c), C.c_uint32(s.n), C.c_double(theta), _p(tr.nm), _p(tr.nbw), _p(t),
+           C.c_uint32(t.size), _p(w.a), _p(w.scale), _p(w.counts), _p(w.near_nodes))
+    if r != 0:
+        raise RuntimeError(f"oracle_bvh_walk_wide failed ({r})")
+    return w
+
+
 def can_approximate(dtype, bw, theta, d2):
     """bvh.h:246-248 on arrays: bw * bw < theta^2 * d2 in T (theta^2 formed in T, bvh.h:252)."""
     t = np_dtype(dtype)

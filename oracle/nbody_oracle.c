@@ -254,6 +254,25 @@ int oracle_bvh_force(int dtype, int dim, const void* m, const void* x, void* a, 
   return 0;
 }
 
+/* The walk of oracle_bvh_force (same T tree, same opening decisions, same order of visits) with everything a body accumulates formed
+ * and summed in the wider type, for the bodies in targets[nt] of a state in key order: see bvh_walk_wide in the .inc.  a[nt * dim],
+ * scale[nt] float64; counts[nt * 4] as oracle_bvh_force's; near_nodes[nt].  Returns -2 for a system of one body, -3 on a target out of
+ * range. */
+int oracle_bvh_walk_wide(int dtype, int dim, const void* m, const void* x, double c, uint32_t sz, double theta, const void* nm,
+                         const void* nbw, const uint32_t* targets, uint32_t nt, double* a, double* scale, uint32_t* counts,
+                         uint32_t* near_nodes) {
+  uint32_t nl = oracle_bvh_nlevels(sz);
+  if (nl == 0) return -2;
+  for (uint32_t t = 0; t < nt; ++t)
+    if (targets[t] >= sz) return -3;
+#define CALL(TT, S)                                                              \
+  bvh_t_##S t = {nl - 1, (1u << nl) - 1u, (TT*)nm, (TT*)0, (TT*)nbw};           \
+  bvh_walk_wide_##S(&t, (const TT*)m, (const TT*)x, (TT)c, sz, (TT)theta, targets, nt, a, scale, counts, near_nodes)
+  DISPATCH(dtype, dim, CALL);
+#undef CALL
+  return 0;
+}
+
 /* bvh.h:246-248 can_approximate on arrays: out[i] = bw[i] * bw[i] < theta^2 * d2[i], in T, with theta^2 = theta * theta in T as
  * compute_force forms it (bvh.h:252).  Used by the tests of the product's one-compare form of this test. */
 int oracle_can_approximate(int dtype, const void* bw, double theta, const void* d2, uint64_t n, uint8_t* out) {

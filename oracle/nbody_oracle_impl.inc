@@ -500,6 +500,96 @@ static void FN(bvh_force)(const FN(bvh_t) * t, const T* m, const T* x, T* a, T c
   }
 }
 
+/* ---- the wide BVH walk: the per-body yardstick of the traversal (K9) of include/nbody_hip.h -----------------------------------------
+ * bvh_force's loop above for the bodies in targets[nt], on the same T tree: the opening test bw * bw < theta2 * dist2 in T with the
+ * reference's unfused dist2, the same order of visits, the same counters.  What a body accumulates from the entries it accepts (node
+ * monopoles and bodies alike) is formed and summed in W, the pair form all_pairs_force_wide's with the reference's eps(T) kept:
+ *   a_i = c sum m d / (r2 * r + eps(T))        scale_i = |c| sum |m| r / (r2 * r + eps(T)),    d = p - x_i, r2 = |d|^2, r = sqrt(r2)
+ * near_nodes[t]: the accepted NODES whose dist2 (in T) is below 2^-16, the distance at which the product's double term changes form.
+ * Written here from the formulas of include/nbody_hip.h; no reference counterpart. */
+static void FN(bvh_walk_wide)(const FN(bvh_t) * t, const T* m, const T* x, T c, uint32_t sz, T theta, const uint32_t* targets,
+                              uint32_t nt, double* a_out, double* scale_out, uint32_t* counts, uint32_t* near_nodes) {
+  const T theta2            = theta * theta;
+  const T near2             = (T)(1.0 / 65536.0);
+  const uint32_t last_level = t->last_level;
+  const W eps               = (W)T_EPS;
+#pragma omp parallel for schedule(dynamic, 64)
+  for (int64_t tt = 0; tt < (int64_t)nt; ++tt) {
+    const uint32_t i = targets[tt];
+    T xs[D];
+    W xw[D], acc[D], sc = 0;
+    for (int k = 0; k < D; ++k) { xs[k] = x[(uint64_t)i * D + k]; xw[k] = (W)xs[k]; acc[k] = 0; }
+    uint32_t tree_index = 0, level = 0;
+    uint32_t leaf_level = last_level + 1, nlevels = last_level + 1;
+    uint64_t covered = 0;
+    uint32_t c_nodes = 0, c_leaf = 0, c_mono = 0, c_body = 0, c_near = 0;
+    while (covered < sz) {
+      uint32_t next_index = 0, next_level = level;
+      const T* p = NULL; /* the accepted entry, if any: D coordinates in T */
+      T mass     = (T)0;
+      if (level == leaf_level) {
+        uint32_t bidx = tree_index - ((1u << leaf_level) - 1u);
+        for (int q = 0; q < 2; ++q) {
+          if (bidx < sz && bidx != i) {
+            const T* pb = &x[(uint64_t)bidx * D];
+            W d[D], r2 = 0;
+            for (int k = 0; k < D; ++k) { d[k] = (W)pb[k] - xw[k]; r2 += d[k] * d[k]; }
+            const W r = W_SQRT(r2), w = (W)m[bidx] / (r2 * r + eps);
+            for (int k = 0; k < D; ++k) acc[k] += w * d[k];
+            sc += W_FABS(w) * r;
+            ++c_body;
+          }
+          ++bidx;
+        }
+        covered += 2;
+        ++c_leaf;
+        next_index = (level == 0) ? 0u : (((1u << (level - 1)) - 1u) + (tree_index - ((1u << level) - 1u)) / 2u);
+        next_index += 1;
+        next_level = level - 1;
+      } else {
+        const T* nm = &t->nm[(uint64_t)tree_index * (D + 1)];
+        T bw        = t->nbw[tree_index];
+        ++c_nodes;
+        const T d2t = FN(dist2)(xs, nm);
+        if (bw * bw < theta2 * d2t) {
+          p    = nm;
+          mass = nm[D];
+          ++c_mono;
+          if (d2t < near2) ++c_near;
+          covered += (uint64_t)(1 << (nlevels - level));
+          if ((tree_index - 1) % 2) {
+            next_index = (level == 0) ? 0u : (((1u << (level - 1)) - 1u) + (tree_index - ((1u << level) - 1u)) / 2u);
+            next_index += 1;
+            next_level = level - 1;
+          } else {
+            next_index = tree_index + 1;
+          }
+        } else {
+          uint32_t f = (1u << level) - 1u, cnt = 1u << level;
+          next_index = (tree_index - f) * 2 + f + cnt;
+          next_level = level + 1;
+        }
+      }
+      if (p) {
+        W d[D], r2 = 0;
+        for (int k = 0; k < D; ++k) { d[k] = (W)p[k] - xw[k]; r2 += d[k] * d[k]; }
+        const W r = W_SQRT(r2), w = (W)mass / (r2 * r + eps);
+        for (int k = 0; k < D; ++k) acc[k] += w * d[k];
+        sc += W_FABS(w) * r;
+      }
+      level      = next_level;
+      tree_index = next_index;
+    }
+    for (int k = 0; k < D; ++k) a_out[(uint64_t)tt * D + k] = (double)((W)c * acc[k]);
+    scale_out[tt] = (double)(W_FABS((W)c) * sc);
+    counts[(uint64_t)tt * 4 + 0] = c_nodes;
+    counts[(uint64_t)tt * 4 + 1] = c_leaf;
+    counts[(uint64_t)tt * 4 + 2] = c_mono;
+    counts[(uint64_t)tt * 4 + 3] = c_body;
+    near_nodes[tt] = c_near;
+  }
+}
+
 /* ---- octree Barnes-Hut (octree.h) ------------------------------------------------------------- */
 /* Serial restatement of the lock-based concurrent tree (what the serial PSTL backend executes: bodies are
  * inserted in index order).  Node numbering depends on insertion order; forces, visit counts, tree size and

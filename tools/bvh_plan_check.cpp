@@ -21,6 +21,8 @@
 //   per-lane LDS       float auto at 2 .. 2048: test_wave_cooperative_equals_per_lane_bitwise, test_traversal_forms_fuzz
 //   sweep, parts = 8   test_traversal_shard_windows_bitwise at 9000 (windows of 1000, 4001, 3999); double auto at 4096, 4097, 20 000
 //   sweep, parts = 4   test_recorded_steps_and_eager_traversals_at_other_angles at 30 000
+//   every form and launch shape of the sweep, float and double, 2D and 3D, counters on and off, per body against the wide walk:
+//                      tests/test_gpu_bvh_wide.py (4099, 20 545 and 41 001 bodies, pinned below)
 //   sweep, items       test_sweep_work_items_and_shard_windows at 200 003 (windows of 70 000, 65 539, 64 464),
 //                      test_config4_n1e6_galaxy_theta05_vs_oracle at 10^6, test_bvh_whole_force_phase_at_2pow21; in float at traversal 5:
 //                      70 000 (tests/test_gpu_cli.py, the long runs of both forms).  Float in auto mode takes the sweep from 180 000
@@ -149,7 +151,7 @@ static int check_pins() {
   const auto d = [](uint32_t count, uint32_t n = 0, int order = 0, int final_buf = 0) {
     return request(8, count, levels_for(n ? n : count), 0, order, true, final_buf);
   };
-  const auto f = [](uint32_t count, int traversal = 0) { return request(4, count, levels_for(count), traversal); };
+  const auto f = [](uint32_t count, int traversal = 0, int order = 0) { return request(4, count, levels_for(count), traversal, order); };
   const k9_form lane = k9_form::lane_global, lds = k9_form::lane_lds, sweep = k9_form::sweep;
   const pin pins[] = {
       {d(4095), lane, 64, 0, 1, 0, 0},
@@ -176,6 +178,17 @@ static int check_pins() {
       {f(179999), lane, 2813, 0, 1, 0, 0},
       {f(180000), sweep, 2992, 0, 1, 374, 0},
       {d((1u << 26) + 1u), lane, 1048577, 0, 1, 0, 0},  // 27 levels in auto mode: per-lane
+      // what tests/test_gpu_bvh_wide.py launches, count -> groups -> shape, double on auto and float at traversal 5: 4099 -> 65 -> 8 lane
+      // ranges; 20545 -> 322 -> 4 ranges; 41001 -> 641 -> 1 range with work items (81 + 5 per list), and in index order without
+      {d(4099), sweep, 520, 65, 8, 0, 0},
+      {d(20545), sweep, 1288, 322, 4, 0, 0},
+      {d(41001), sweep, 688, 641, 1, 86, 0},
+      {d(41001, 0, 1), sweep, 641, 641, 1, 0, 0},
+      {f(4099, 5), sweep, 520, 65, 8, 0, 0},
+      {f(20545, 5), sweep, 1288, 322, 4, 0, 0},
+      {f(41001, 5), sweep, 688, 641, 1, 86, 0},
+      {f(41001, 5, 1), sweep, 641, 641, 1, 0, 0},
+      {f(4099), lane, 65, 65, 1, 0, 0},  // float on auto above 2048 bodies: per-lane over global memory
   };
   for (const pin& q : pins) {
     k9_plan p;
