@@ -96,7 +96,9 @@ typedef struct nbody_state {
  *      centre, nbody_knn_create, nbody_knn_create_on, nbody_knn_destroy, nbody_knn_compute, nbody_knn_read,
  *      nbody_knn_density_centre; nbody_knn_create_method and nbody_knn_method (the tree-pruned method of the same handle).
  *      Additive, same version: friends-of-friends groups on the same tree, nbody_fof_create, nbody_fof_create_on,
- *      nbody_fof_destroy, nbody_fof_compute, nbody_fof_read, nbody_fof_summary. */
+ *      nbody_fof_destroy, nbody_fof_compute, nbody_fof_read, nbody_fof_summary.  Additive, same version: exact fixed-radius
+ *      neighbour lists on the same tree, nbody_nlist_create, nbody_nlist_create_on, nbody_nlist_destroy, nbody_nlist_set_radii,
+ *      nbody_nlist_compute, nbody_nlist_read, nbody_nlist_summary. */
 #define NBODY_HIP_ABI_VERSION 2004
 int nbody_abi_version(void);
 
@@ -724,6 +726,67 @@ int  nbody_fof_compute(nbody_fof* h, const nbody_state* s, double b, void* strea
 int  nbody_fof_read(nbody_fof* h, int what, void* host_out, size_t bytes, void* stream);
 /* Blocking.  out4: the summary of the last compute. */
 int  nbody_fof_summary(nbody_fof* h, uint32_t* out4, void* stream);
+
+/* ---- exact fixed-radius neighbour lists on the same tree (no reference counterpart) ----------------------------------------------
+ * Every neighbour of every body within a radius, as a variable-length list per body.  T the state's type, D its dimension:
+ *   neighbour  j is a neighbour of i iff j != i and d2_ij <= r2_i, d2 the unsoftened squared distance of the kNN section (one FMA
+ *              chain in component order, bitwise symmetric in (i, j)).
+ *   radius     scalar (the default): r2_i = T(r) * T(r), rounded once in T on the host; r is compute's argument, r = 0 is legal and
+ *              finds the bodies whose computed d2 is 0.  The relation is then symmetric.  Per-body radii (nbody_nlist_set_radii):
+ *              r2_i = v_i * v_i, one multiply in T, or r2_i = v_i with squared = 1.  That is a gather: i's own radius decides, so i
+ *              may list j without j listing i.
+ *   count      uint32_t[n]: the number of neighbours of every body, in the state's body order.
+ *   offset     uint64_t[n + 1]: the exclusive prefix sum of count in body order; offset[n] is the total.
+ *   list       uint32_t[total]: the neighbours of i are list[offset[i] .. offset[i + 1]), in ascending index.
+ *   summary    uint64_t[4]: the total, the largest count, the lowest index that has it, status.
+ *   status     NBODY_NLIST_OVER_CAPACITY: total > capacity; NBODY_NLIST_OVER_PER_BODY: the largest count exceeds
+ *              NBODY_NLIST_MAX_PER_BODY.  Either means that the list was NOT produced by this compute (nbody_nlist_read of the list
+ *              returns NBODY_ERR_STATE); count, offset and summary are always valid, and a later compute that fits clears the status.
+ *   capacity   the number of list entries the handle can hold, 0 .. 2^32, fixed at create.  capacity = 0 makes a counts-only handle:
+ *              it skips the two passes that produce the list.
+ * The lists are sets with one correct answer: they do not depend on the order of the bodies in the state beyond the renaming, on
+ * scheduling, or on how the tree was built.  The search is exact: the tree of the kNN section's TREE method prunes with a bound that
+ * needs no tolerance, and a body at exactly r2_i is listed.  No atomics anywhere: two computes of the same state give the same bits
+ * for every output, and so do an eager call and a replayed recorded one, and a handle destroyed and made again.  No loop of any kernel
+ * waits for another lane, wave or block.  Non-finite positions are outside the contract (the call stays memory-safe; a NaN distance is
+ * within no radius).
+ *  - create allocates everything (packed and sorted records, boxes, keys, the sort's scratch, the radii, count, offset, the scan's
+ *    strips, two arrays of capacity entries, the summary) and frees everything again if one allocation fails.  Argument errors in
+ *    this order: out NULL, dtype, dim, n = 0 or n > 2^28, capacity > 2^32 (all NBODY_ERR_ARG).  create(_on) between
+ *    nbody_graph_begin and nbody_graph_end: NBODY_ERR_STATE.
+ *  - set_radii is blocking.  host_values: T[n] on the host, bytes = n * sizeof(T); NULL with bytes = 0 returns the handle to the
+ *    scalar radius.  Every r2_i must be finite and >= 0 and every v_i >= 0: checked on the host before anything is copied; a bad
+ *    value is NBODY_ERR_ARG with a message that names the first offending index, and the handle keeps the radii it had.  Order: h
+ *    NULL, host_values NULL, bytes, squared not 0 or 1 (NBODY_ERR_ARG); the stream's device; between nbody_graph_begin and
+ *    nbody_graph_end NBODY_ERR_STATE; then the values.  It may be called before the first compute.
+ *  - compute reads s->m and s->x only: s->v, s->a and s->ao may be NULL or garbage.  Asynchronous, allocates nothing, reads nothing
+ *    back, may be recorded into a step graph (a recording keeps the radius, or the use of the per-body radii, it was made with); the
+ *    number of launches is fixed at create (it follows from n, and from whether capacity is 0).  Whole system only.
+ *  - Argument errors of compute are found before the device is touched, in this order: s NULL; the state's dtype, dim, window,
+ *    tuning; the whole-system rule; h NULL; h made for another dtype, dim or n; and when the handle holds no radii: r negative, NaN
+ *    or infinite; r2 not finite in T (all NBODY_ERR_ARG).  With radii set r is ignored.  Then a stream of another device
+ *    (NBODY_ERR_ARG).
+ *  - read and summary are blocking; NBODY_ERR_STATE before the first compute on that handle and between nbody_graph_begin and
+ *    nbody_graph_end (the capture stays usable).  Every entry switches to the handle's device and restores the caller's. */
+#define NBODY_NLIST_MAX_PER_BODY 4096
+#define NBODY_NLIST_OVER_CAPACITY 1u
+#define NBODY_NLIST_OVER_PER_BODY 2u
+typedef struct nbody_nlist nbody_nlist;
+int  nbody_nlist_create(nbody_nlist** out, int dtype, int dim, uint32_t n, uint64_t capacity);                /* on the current device */
+int  nbody_nlist_create_on(nbody_nlist** out, int dtype, int dim, uint32_t n, uint64_t capacity, int device); /* device < 0: the current one */
+void nbody_nlist_destroy(nbody_nlist* h);                                                                     /* NULL: no-op */
+/* Blocking.  Per-body radii (squared = 0) or squared radii (squared = 1) for every later compute; NULL, 0: the scalar radius again. */
+int  nbody_nlist_set_radii(nbody_nlist* h, const void* host_values, size_t bytes, int squared, void* stream);
+/* count, offset, the summary and (if it fits) the list at (s->m, s->x) for the radius r, into the handle.  Asynchronous, recordable. */
+int  nbody_nlist_compute(nbody_nlist* h, const nbody_state* s, double r, void* stream);
+/* Blocking.  what: 0 count uint32[n]: bytes must be n * 4 | 1 offset uint64[n + 1]: bytes must be (n + 1) * 8 | 2 list uint32[total]:
+ * bytes must be total * 4; the call reads the total back itself, so nbody_nlist_summary need not have been called (total = 0: bytes =
+ * 0, nothing is written, host_out may be NULL).  A list read after a compute whose status is not 0 returns NBODY_ERR_STATE with a
+ * message that says which limit was hit: the needed total and the capacity, or the largest count.  Order of the argument errors:
+ * what, h NULL, then for 0 / 1 host_out NULL and bytes; the state rules; then for 2 the status, bytes and host_out NULL. */
+int  nbody_nlist_read(nbody_nlist* h, int what, void* host_out, size_t bytes, void* stream);
+/* Blocking.  out4: the summary of the last compute. */
+int  nbody_nlist_summary(nbody_nlist* h, uint64_t* out4, void* stream);
 
 /* ---- owning context (device mirrors of a host System), used by the C++ CLI host ------------------ */
 

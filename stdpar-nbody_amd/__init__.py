@@ -73,6 +73,8 @@ ABI_SYMBOLS = [
     "nbody_knn_create", "nbody_knn_create_on", "nbody_knn_destroy", "nbody_knn_compute", "nbody_knn_read", "nbody_knn_density_centre",
     "nbody_knn_create_method", "nbody_knn_method",
     "nbody_fof_create", "nbody_fof_create_on", "nbody_fof_destroy", "nbody_fof_compute", "nbody_fof_read", "nbody_fof_summary",
+    "nbody_nlist_create", "nbody_nlist_create_on", "nbody_nlist_destroy", "nbody_nlist_set_radii", "nbody_nlist_compute",
+    "nbody_nlist_read", "nbody_nlist_summary",
 ]
 ABI_MAJOR = 2
 COMM_ID_BYTES = 128
@@ -152,6 +154,14 @@ def lib():
         L.nbody_fof_compute.argtypes = [vp, vp, d, vp]
         L.nbody_fof_read.argtypes = [vp, C.c_int, vp, C.c_size_t, vp]
         L.nbody_fof_summary.argtypes = [vp, vp, vp]
+        L.nbody_nlist_create.argtypes = [vp, C.c_int, C.c_int, C.c_uint32, C.c_uint64]
+        L.nbody_nlist_create_on.argtypes = [vp, C.c_int, C.c_int, C.c_uint32, C.c_uint64, C.c_int]
+        L.nbody_nlist_destroy.restype = None
+        L.nbody_nlist_destroy.argtypes = [vp]
+        L.nbody_nlist_set_radii.argtypes = [vp, vp, C.c_size_t, C.c_int, vp]
+        L.nbody_nlist_compute.argtypes = [vp, vp, d, vp]
+        L.nbody_nlist_read.argtypes = [vp, C.c_int, vp, C.c_size_t, vp]
+        L.nbody_nlist_summary.argtypes = [vp, vp, vp]
         _lib = L
     return _lib
 
@@ -692,6 +702,61 @@ class Fof(_Handle):
         return {name: self.read(what, stream) for what, name in ((2, "label"), (3, "size"), (4, "mass"), (5, "com"))}
 
 
+class NeighbourLists(_Handle):
+    """Exact fixed-radius neighbour lists (nbody_nlist_*): every j != i with d2_ij <= r2_i, as count (n,), offset (n + 1,) and a list
+    in ascending index per body.  On the tree of the kNN "tree" method.  capacity (fixed here, 0 .. 2^32) is the number of list
+    entries the handle can hold; 0 makes a counts-only handle."""
+
+    _destroy = "nbody_nlist_destroy"
+
+    MAX_PER_BODY = 4096
+    OVER_CAPACITY, OVER_PER_BODY = 1, 2  # the summary's status bits: no list was produced by that compute
+
+    def __init__(self, dtype, dim, n, capacity, device=-1):
+        """device: where the handle's buffers live (-1: the calling thread's current device)."""
+        self.h = C.c_void_p()
+        self.dtype, self.dim, self.n, self.capacity = dtype, dim, n, int(capacity)
+        _check(lib().nbody_nlist_create_on(C.byref(self.h), dtype, dim, C.c_uint32(n), C.c_uint64(self.capacity), device))
+
+    def set_radii(self, values, squared=False, stream=None):
+        """Per-body radii (n,), or squared radii with squared=True, for every later compute: r2_i = v_i * v_i (or v_i), each >= 0 and
+        finite (blocking)."""
+        v = np.ascontiguousarray(values, np_dtype(self.dtype))
+        _check(lib().nbody_nlist_set_radii(self.h, _p(v), v.nbytes, 1 if squared else 0, stream))
+
+    def clear_radii(self, stream=None):
+        """Back to the scalar radius of compute."""
+        _check(lib().nbody_nlist_set_radii(self.h, None, 0, 0, stream))
+
+    def compute(self, st, r=0.0, stream=None):
+        """count, offset, the summary and (if it fits) the list at (st.m, st.x) for the radius r >= 0 (ignored once radii are set),
+        into the handle.  Asynchronous, recordable."""
+        _check(lib().nbody_nlist_compute(self.h, C.byref(st), C.c_double(r), stream))
+
+    def summary(self, stream=None):
+        """(total, largest count, lowest index that has it, status) of the last compute, uint64 (4,) (blocking)."""
+        out = np.zeros(4, np.uint64)
+        _check(lib().nbody_nlist_summary(self.h, _p(out), stream))
+        return out
+
+    def read(self, what, stream=None):
+        """0 count (n,) uint32, 1 offset (n + 1,) uint64, 2 list (total,) uint32 of the last compute (blocking).  The list of a compute
+        whose status is not 0 does not exist: NbodyError."""
+        if what == 0:
+            out = np.zeros(self.n, np.uint32)
+        elif what == 1:
+            out = np.zeros(self.n + 1, np.uint64)
+        else:
+            total, _, _, status = self.summary(stream)
+            out = np.zeros(int(total) if status == 0 else 0, np.uint32)  # no list: the call below says which limit was hit
+        _check(lib().nbody_nlist_read(self.h, what, _p(out) if out.size else None, out.nbytes, stream))
+        return out
+
+    def lists(self, stream=None):
+        """(count, offset, idx) of the last compute (blocking)."""
+        return self.read(0, stream), self.read(1, stream), self.read(2, stream)
+
+
 class OctreeBlock(_Handle):
     """Block (individual) time steps for the octree leapfrog (nbody_octree_block_*): owns the levels, tau, the active lists, the
     predicted positions and the scratch of the active set's forces; the tree is the caller's Octree."""
@@ -747,6 +812,7 @@ class DeviceSystem(_Handle):
         self._knn = {}
         self._knn_other = {}
         self._fof = {}
+        self._nlist = {}
 
     @classmethod
     def from_host(cls, hs, device=0):
@@ -756,7 +822,7 @@ class DeviceSystem(_Handle):
 
     def close(self):
         cached = [getattr(self, a) for a in self._CACHED] + list(self._knn.values()) + list(self._knn_other.values())
-        cached += list(self._fof.values())
+        cached += list(self._fof.values()) + list(self._nlist.values())
         for h in cached:
             if h is not None:
                 h.close()
@@ -765,6 +831,7 @@ class DeviceSystem(_Handle):
         self._knn = {}
         self._knn_other = {}
         self._fof = {}
+        self._nlist = {}
         super().close()  # the context last
 
     def upload(self, hs):
@@ -1015,6 +1082,48 @@ class DeviceSystem(_Handle):
         h = self.fof_handle(min_members)
         h.compute(self.state(), b, self.stream)
         return h.catalogue(self.stream), h.summary(self.stream)
+
+    # exact fixed-radius neighbour lists (no reference counterpart)
+    def nlist_handle(self, capacity=0):
+        """The NeighbourLists handle of this system for `capacity` list entries (0: counts only), made at the first use and closed
+        with the system."""
+        capacity = int(capacity)
+        if capacity not in self._nlist:
+            self._nlist[capacity] = NeighbourLists(self.dtype, self.dim, self.n, capacity, self.device)
+        return self._nlist[capacity]
+
+    def nlist_compute(self, r, capacity=0):
+        """nbody_nlist_compute on the state as it is; a StepGraph may record it (the handle for `capacity` is made before the
+        recording).  The radius is r unless that handle holds per-body radii (nlist_handle(capacity).set_radii)."""
+        self.nlist_handle(capacity).compute(self.state(), r, self.stream)
+
+    def _nlist_run(self, h, r, radii, squared):
+        if (r is None) == (radii is None):
+            raise ValueError("give either a radius r or per-body radii")
+        if radii is None:
+            h.clear_radii(self.stream)
+        else:
+            h.set_radii(radii, squared, self.stream)
+        h.compute(self.state(), 0.0 if r is None else r, self.stream)
+
+    def radius_counts(self, r=None, radii=None, squared=False):
+        """count (n,) uint32: the number of bodies j != i with d2_ij <= r2_i, for one radius r or per-body radii (squared=True: the
+        values are r2_i) (blocking)."""
+        h = self.nlist_handle(0)
+        self._nlist_run(h, r, radii, squared)
+        return h.read(0, self.stream)
+
+    def radius_neighbours(self, r=None, radii=None, squared=False, capacity=None):
+        """(offset (n + 1,) uint64, idx (total,) uint32): the neighbours of body i within its radius are idx[offset[i]:offset[i + 1]],
+        ascending (blocking).  capacity=None: the counts-only handle gives the total and a handle of exactly that capacity the list;
+        with a capacity that turns out too small, or a body with more than NeighbourLists.MAX_PER_BODY neighbours, NbodyError."""
+        if capacity is None:
+            h0 = self.nlist_handle(0)
+            self._nlist_run(h0, r, radii, squared)
+            capacity = int(h0.summary(self.stream)[0])
+        h = self.nlist_handle(capacity)
+        self._nlist_run(h, r, radii, squared)
+        return h.read(1, self.stream), h.read(2, self.stream)
 
     def calc_energies(self, softening=0.0):
         """(kinetic, potential) as in System::calc_energies (src/system.h:62-79); blocking.  softening > 0: the potential of the

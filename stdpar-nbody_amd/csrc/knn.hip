@@ -47,6 +47,7 @@
 #include "pair_sweep.hpp"
 #include "radix_sort.hpp"
 #include "fof_union.hpp"
+#include "nlist_plan.hpp"
 
 #pragma clang fp contract(off)
 
@@ -307,6 +308,7 @@ __global__ __launch_bounds__(kKnnSumBlock) void knn_summary_kernel(const T* __re
 
 #include "nntree.inc"
 #include "fof.inc"
+#include "nlist.inc"
 
 }  // namespace nbody
 
@@ -636,6 +638,215 @@ extern "C" int nbody_fof_summary(nbody_fof* h, uint32_t* out4, void* stream) {
   device_guard guard(h->device);
   uint32_t sum[4];
   if (int r = fof_read_summary(h, sum, st)) return r;
+  memcpy(out4, sum, sizeof sum);
+  return NBODY_OK;
+}
+
+// ---- fixed-radius neighbour lists (nlist.inc) ----------------------------------------------------------------------------------
+// recs: pair_rec<T>[padded], original order (the structure's input); st: the structure nbody_knn's tree method and nbody_fof build
+// too.  np: every launch shape, from (n, capacity) (nlist_plan.hpp).  started: nbody_nlist_compute has run.
+struct nbody_nlist : hermite_handle {
+  nlist_plan np{};
+  bool has_radii = false;  // r2 holds per-body values (nbody_nlist_set_radii); else the scalar r of compute
+  nntree_structure st{};
+  void* r2          = nullptr;  // T[n]: r2_i in body order
+  uint32_t* count   = nullptr;  // [n], body order
+  uint64_t* offset  = nullptr;  // [n + 1]
+  uint64_t* ssum    = nullptr;  // [strips]: the strips' sums, then their exclusive scan
+  uint64_t* smax    = nullptr;  // [strips]: the strips' max of (count << 32) | ~index
+  uint32_t* scratch = nullptr;  // [capacity]: the segments in ascending sorted position
+  uint32_t* list    = nullptr;  // [capacity]: ... in ascending index
+  uint64_t* summary = nullptr;  // [4]
+};
+
+namespace nbody {
+
+// the structure, count walk, strip sums, scan (+ summary and status), offsets, and with a list: fill walk, segment order.
+template <typename T, int D>
+static int nlist_launch(nbody_nlist* h, const nbody_state* s, T r2, hipStream_t st) {
+  const nlist_plan& p = h->np;
+  auto* recs          = static_cast<pair_rec<T>*>(h->recs);
+  const void* sorted  = h->st.sorted;  // untyped on purpose, see the head of fof.inc
+  const void* boxes   = h->st.boxes;
+  const T* radii      = h->has_radii ? static_cast<const T*>(h->r2) : nullptr;
+  const uint32_t n = h->n, levels = h->st.tree.levels;
+  const dim3 block(kNtBlock);
+  if (int r = nntree_structure_launch<T, D>(&h->st, s, recs, n, h->padded, st)) return r;
+  hipLaunchKernelGGL((nlist_count_kernel<T, D>), dim3(p.walk_blocks), block, 0, st, sorted, boxes, radii, r2, n, levels, h->count);
+  NB_HIP(hipGetLastError());
+  hipLaunchKernelGGL(nlist_strip_kernel, dim3(p.strips), block, 0, st, h->count, n, h->ssum, h->smax);
+  NB_HIP(hipGetLastError());
+  hipLaunchKernelGGL(nlist_scan_kernel, dim3(1), dim3(kNlScanBlock), 0, st, h->ssum, h->smax, p.strips, p.scan_trips, p.capacity, h->offset + n,
+                     h->summary);
+  NB_HIP(hipGetLastError());
+  hipLaunchKernelGGL(nlist_offsets_kernel, dim3(p.strips), block, 0, st, h->count, h->ssum, n, h->offset);
+  NB_HIP(hipGetLastError());
+  if (!p.lists) return NBODY_OK;  // a counts-only handle
+  hipLaunchKernelGGL((nlist_fill_kernel<T, D>), dim3(p.walk_blocks), block, 0, st, sorted, boxes, radii, r2, n, levels, h->offset, h->summary,
+                     h->scratch, p.capacity);
+  NB_HIP(hipGetLastError());
+  hipLaunchKernelGGL(nlist_order_kernel, dim3(p.order_blocks), dim3(kNlWave), 0, st, h->count, h->offset, h->summary, h->scratch, h->list,
+                     p.capacity);
+  NB_HIP(hipGetLastError());
+  return NBODY_OK;
+}
+
+// r2_i of set_radii's values into out, checked: returns the first bad index, or n
+template <typename T>
+static uint32_t nlist_radii_r2(const T* v, uint32_t n, bool squared, T* out) {
+  for (uint32_t i = 0; i < n; ++i) {
+    const T r2 = squared ? v[i] : v[i] * v[i];  // one multiply in T
+    if (!(v[i] >= T(0)) || !(r2 <= (sizeof(T) == 4 ? T(FLT_MAX) : T(DBL_MAX)))) return i;
+    out[i] = r2;
+  }
+  return n;
+}
+
+}  // namespace nbody
+
+extern "C" int nbody_nlist_create(nbody_nlist** out, int dtype, int dim, uint32_t n, uint64_t capacity) {
+  return nbody_nlist_create_on(out, dtype, dim, n, capacity, -1);
+}
+
+extern "C" int nbody_nlist_create_on(nbody_nlist** out, int dtype, int dim, uint32_t n, uint64_t capacity, int device) {
+  if (int r = create_check_args(out, dtype, dim, n, 1, kNlMaxN, "nlist needs 1 <= n <= 2^28 (got %u)")) return r;
+  NB_ARG(capacity <= kNlMaxCapacity, "nlist needs capacity <= 2^32 list entries (got %llu)", static_cast<unsigned long long>(capacity));
+  if (int r = create_check_device(&device, "nlist", true)) return r;
+  device_guard guard(device);
+  auto* h = new nbody_nlist;
+  // nothing is cleared: every compute writes all it later reads
+  pair_handle_alloc(h, dtype, dim, n, device, knn_plan_for(n));
+  nlist_plan_for(n, capacity, &h->np);  // in range: checked above
+  nntree_structure_alloc(&h->st, h->mem, h->tsz, n, h->padded);
+  h->mem.alloc(&h->r2, h->tsz * size_t(n));
+  h->mem.alloc(&h->count, sizeof(uint32_t) * size_t(n));
+  h->mem.alloc(&h->offset, sizeof(uint64_t) * (size_t(n) + 1));
+  h->mem.alloc(&h->ssum, sizeof(uint64_t) * size_t(h->np.strips));
+  h->mem.alloc(&h->smax, sizeof(uint64_t) * size_t(h->np.strips));
+  if (h->np.lists) {
+    h->mem.alloc(&h->scratch, sizeof(uint32_t) * size_t(capacity));
+    h->mem.alloc(&h->list, sizeof(uint32_t) * size_t(capacity));
+  }
+  h->mem.alloc(&h->summary, sizeof(uint64_t) * 4);
+  return create_finish(out, h, nbody_nlist_destroy, h->mem.error(), "nbody_nlist_create allocation");
+}
+
+extern "C" void nbody_nlist_destroy(nbody_nlist* h) {
+  if (!h) return;
+  device_guard guard(h->device);
+  delete h;
+}
+
+extern "C" int nbody_nlist_set_radii(nbody_nlist* h, const void* host_values, size_t bytes, int squared, void* stream) {
+  NB_ARG(h != nullptr, "nbody_nlist is NULL");
+  const bool clear = host_values == nullptr && bytes == 0;
+  if (!clear) {
+    NB_ARG(host_values != nullptr, "host_values is NULL");
+    NB_ARG(bytes == h->tsz * size_t(h->n), "nbody_nlist_set_radii needs %zu bytes (n values of the handle's type), got %zu", h->tsz * size_t(h->n), bytes);
+    NB_ARG(squared == 0 || squared == 1, "squared must be 0 or 1, got %d", squared);
+  }
+  const hipStream_t st = as_stream(stream);
+  if (int r = check_same_device(h->device, st, "nbody_nlist")) return r;
+  if (capture_id(st) != 0) {
+    set_error("nbody_nlist_set_radii is blocking: it cannot be recorded (call it outside nbody_graph_begin/end)");
+    return NBODY_ERR_STATE;
+  }
+  if (clear) {
+    h->has_radii = false;
+    return NBODY_OK;
+  }
+  // every r2_i on the host, checked before anything is copied
+  std::vector<unsigned char> r2(bytes);
+  const uint32_t bad = h->dtype == NBODY_F32 ? nlist_radii_r2(static_cast<const float*>(host_values), h->n, squared != 0, reinterpret_cast<float*>(r2.data()))
+                                             : nlist_radii_r2(static_cast<const double*>(host_values), h->n, squared != 0, reinterpret_cast<double*>(r2.data()));
+  if (bad != h->n) {
+    const double v = h->dtype == NBODY_F32 ? double(static_cast<const float*>(host_values)[bad]) : static_cast<const double*>(host_values)[bad];
+    NB_ARG(false, "nbody_nlist_set_radii: value %g at index %u: every radius must be >= 0 and its square finite in the handle's type", v, bad);
+  }
+  device_guard guard(h->device);
+  NB_HIP(hipMemcpyAsync(h->r2, r2.data(), bytes, hipMemcpyHostToDevice, st));
+  NB_HIP(hipStreamSynchronize(st));
+  h->has_radii = true;
+  return NBODY_OK;
+}
+
+extern "C" int nbody_nlist_compute(nbody_nlist* h, const nbody_state* s, double r, void* stream) {
+  if (int rc = pair_check_state(s, "nbody_nlist_compute")) return rc;
+  NB_ARG(h != nullptr, "nbody_nlist is NULL");
+  NB_ARG(h->dtype == s->dtype && h->dim == s->dim && h->n == s->sz,
+         "nbody_nlist was created for (dtype %d, dim %d, n %u), the state is (dtype %d, dim %d, sz %u)", h->dtype, h->dim, h->n, s->dtype,
+         s->dim, s->sz);
+  if (!h->has_radii) NB_ARG(r >= 0.0 && r <= DBL_MAX, "radius r = %g must be finite and >= 0", r);
+  const hipStream_t st = as_stream(stream);
+  return dispatch(s->dtype, s->dim, [&](auto tg) {
+    using T         = typename decltype(tg)::type;
+    constexpr int D = decltype(tg)::dim;
+    T r2 = T(0);
+    if (!h->has_radii) {
+      // r is compared in double BEFORE it is converted: a finite double beyond T's range has no defined conversion to T
+      NB_ARG(r <= double(sizeof(T) == 4 ? T(FLT_MAX) : T(DBL_MAX)), "radius r = %g: r^2 is not finite in the state's type", r);
+      const T rt = T(r);
+      r2         = rt * rt;  // rounded once in T
+      NB_ARG(r2 <= (sizeof(T) == 4 ? T(FLT_MAX) : T(DBL_MAX)), "radius r = %g: r^2 is not finite in the state's type", r);
+    }
+    if (int rc = check_same_device(h->device, st, "nbody_nlist")) return rc;
+    device_guard guard(h->device);
+    const int rc = nlist_launch<T, D>(h, s, r2, st);
+    if (rc == NBODY_OK) h->started = true;
+    return rc;
+  });
+}
+
+// the summary of the last compute, blocking (the callers have checked pair_read_ready)
+static int nlist_read_summary(nbody_nlist* h, uint64_t (&out)[4], hipStream_t st) {
+  NB_HIP(hipMemcpyAsync(out, h->summary, sizeof out, hipMemcpyDeviceToHost, st));
+  NB_HIP(hipStreamSynchronize(st));
+  return NBODY_OK;
+}
+
+extern "C" int nbody_nlist_read(nbody_nlist* h, int what, void* host_out, size_t bytes, void* stream) {
+  NB_ARG(what >= 0 && what <= 2, "what must be 0 (count), 1 (offset) or 2 (list), got %d", what);
+  NB_ARG(h != nullptr, "nbody_nlist is NULL");
+  if (what <= 1) {
+    const size_t need = what == 0 ? sizeof(uint32_t) * size_t(h->n) : sizeof(uint64_t) * (size_t(h->n) + 1);
+    NB_ARG(host_out != nullptr, "host_out is NULL");
+    NB_ARG(bytes == need, "nbody_nlist_read(what = %d) needs %zu bytes, got %zu", what, need, bytes);
+  }
+  const hipStream_t st = as_stream(stream);
+  if (int r = pair_read_ready(h, "nbody_nlist", "nbody_nlist_read", "nbody_nlist_compute", st)) return r;
+  device_guard guard(h->device);
+  const void* src = what == 0 ? static_cast<const void*>(h->count) : static_cast<const void*>(h->offset);
+  if (what == 2) {  // total entries: the total is read back here (a replayed recorded compute changes it without a host call)
+    uint64_t sum[4];
+    if (int r = nlist_read_summary(h, sum, st)) return r;
+    if (sum[3] != 0) {
+      if (sum[3] & kNlStatusPerBody)
+        set_error("nbody_nlist_read: no list was produced: the largest count %llu (body %llu) exceeds NBODY_NLIST_MAX_PER_BODY = %u",
+                  static_cast<unsigned long long>(sum[1]), static_cast<unsigned long long>(sum[2]), kNlMaxPerBody);
+      else
+        set_error("nbody_nlist_read: no list was produced: it needs %llu entries, the handle's capacity is %llu",
+                  static_cast<unsigned long long>(sum[0]), static_cast<unsigned long long>(h->np.capacity));
+      return NBODY_ERR_STATE;
+    }
+    NB_ARG(bytes == sizeof(uint32_t) * size_t(sum[0]), "nbody_nlist_read(what = 2) needs %zu bytes (%llu entries), got %zu",
+           sizeof(uint32_t) * size_t(sum[0]), static_cast<unsigned long long>(sum[0]), bytes);
+    if (bytes == 0) return NBODY_OK;
+    NB_ARG(host_out != nullptr, "host_out is NULL");
+    src = h->list;
+  }
+  NB_HIP(hipMemcpyAsync(host_out, src, bytes, hipMemcpyDeviceToHost, st));
+  NB_HIP(hipStreamSynchronize(st));
+  return NBODY_OK;
+}
+
+extern "C" int nbody_nlist_summary(nbody_nlist* h, uint64_t* out4, void* stream) {
+  NB_ARG(h != nullptr, "nbody_nlist is NULL");
+  NB_ARG(out4 != nullptr, "out4 is NULL");
+  const hipStream_t st = as_stream(stream);
+  if (int r = pair_read_ready(h, "nbody_nlist", "nbody_nlist_summary", "nbody_nlist_compute", st)) return r;
+  device_guard guard(h->device);
+  uint64_t sum[4];
+  if (int r = nlist_read_summary(h, sum, st)) return r;
   memcpy(out4, sum, sizeof sum);
   return NBODY_OK;
 }

@@ -48,6 +48,7 @@ class Device {
     if (neighbours_) nbody_neighbours_destroy(neighbours_);
     if (knn_) nbody_knn_destroy(knn_);
     if (fof_) nbody_fof_destroy(fof_);
+    if (nlist_) nbody_nlist_destroy(nlist_);
     if (hermite_) nbody_hermite_destroy(hermite_);
     if (hermite6_) nbody_hermite6_destroy(hermite6_);
     if (octree_block_) nbody_octree_block_destroy(octree_block_);
@@ -193,6 +194,19 @@ class Device {
     backend_check(nbody_fof_read(fof_, 5, cat_com.data(), c * D * sizeof(T), stream()), "nbody_fof_read");
   }
 
+  // --save-lists R: the exact fixed-radius neighbour lists of the current x for the radius r (nbody_nlist_*; the reads are blocking):
+  // the summary, the count of every body and, when the summary's status is 0, the lists (else `list` comes back empty)
+  void lists(double r, std::uint64_t capacity, std::uint64_t (&summary)[4], std::vector<std::uint32_t>& count, std::vector<std::uint32_t>& list) {
+    single("--save-lists");
+    if (!nlist_) backend_check(nbody_nlist_create_on(&nlist_, dtype, D, host_.n, capacity, 0), "nbody_nlist_create_on");
+    backend_check(nbody_nlist_compute(nlist_, &view_[0], r, stream()), "nbody_nlist_compute");
+    backend_check(nbody_nlist_summary(nlist_, summary, stream()), "nbody_nlist_summary");
+    count.resize(host_.n);
+    backend_check(nbody_nlist_read(nlist_, 0, count.data(), count.size() * sizeof(std::uint32_t), stream()), "nbody_nlist_read");
+    list.resize(summary[3] == 0 ? std::size_t(summary[0]) : 0);
+    if (summary[3] == 0) backend_check(nbody_nlist_read(nlist_, 2, list.data(), list.size() * sizeof(std::uint32_t), stream()), "nbody_nlist_read");
+  }
+
   // Record the phase calls issued by `step` once and return a replayable graph of them (one submission per step).
   template <typename F>
   nbody_graph* record(F&& step) {
@@ -296,6 +310,7 @@ class Device {
   nbody_neighbours* neighbours_ = nullptr;
   nbody_knn* knn_               = nullptr;
   nbody_fof* fof_               = nullptr;
+  nbody_nlist* nlist_           = nullptr;
 };
 
 }  // namespace nb

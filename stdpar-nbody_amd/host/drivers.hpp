@@ -33,7 +33,7 @@ inline std::string fixed2(double v) {
 }
 
 inline void csv_total_guard(Options const& o) {  // src/all_pairs.h:58-62, src/bvh.h:334-339
-  if (o.csv_total && (o.print_state || o.print_info || o.save_pos || o.save_energy || o.save_neighbours || o.save_density != 0 || o.save_groups)) std::abort();
+  if (o.csv_total && (o.print_state || o.print_info || o.save_pos || o.save_energy || o.save_neighbours || o.save_density != 0 || o.save_groups || o.save_lists)) std::abort();
 }
 
 template <typename T, int D>

@@ -81,6 +81,14 @@ struct Options {
   double groups_b      = 0.0;
   long groups_min      = 20;
   bool groups_min_given = false;
+  // not in the reference either (nor in --help): --save-lists R (a radius, finite and >= 0), at every frame the run's Saver records,
+  // the exact fixed-radius neighbour lists of the positions (nbody_nlist_*: summary, counts and, if they fit, the lists) are
+  // appended to lists.bin; --lists-capacity C (0 .. 2^32, default 64 n): the list entries a frame may hold; independent of --save and
+  // of the algorithm; one GPU
+  bool save_lists            = false;
+  double lists_r             = 0.0;
+  unsigned long long lists_capacity = 0;
+  bool lists_capacity_given  = false;
 };
 
 namespace detail {
@@ -244,6 +252,26 @@ inline Options parse_options(std::vector<std::string> const& argv) {
       }
       o.groups_min       = v;
       o.groups_min_given = true;
+    } else if (f == "--save-lists") {
+      std::string const l = k + 1 < argv.size() ? argv[++k] : std::string();
+      char* end           = nullptr;
+      double const v      = std::strtod(l.c_str(), &end);
+      if (l.empty() || end != l.c_str() + l.size() || !(v >= 0.0) || !(v <= std::numeric_limits<double>::max())) {
+        std::cerr << "--save-lists needs a radius R, finite and >= 0." << std::endl;
+        std::exit(EXIT_FAILURE);
+      }
+      o.save_lists = true;
+      o.lists_r    = v;
+    } else if (f == "--lists-capacity") {
+      std::string const l = k + 1 < argv.size() ? argv[++k] : std::string();
+      char* end           = nullptr;
+      unsigned long long const v = std::strtoull(l.c_str(), &end, 10);
+      if (l.empty() || l[0] < '0' || l[0] > '9' || end != l.c_str() + l.size() || v > (1ull << 32)) {
+        std::cerr << "--lists-capacity needs an entry count C in 0 .. 2^32." << std::endl;
+        std::exit(EXIT_FAILURE);
+      }
+      o.lists_capacity       = v;
+      o.lists_capacity_given = true;
     } else if (f == "--print-state") {
       o.print_state = true;
     } else if (f == "--print-info") {
@@ -297,6 +325,16 @@ inline Options parse_options(std::vector<std::string> const& argv) {
     std::cerr << "--groups-min M must not exceed the number of bodies (M = " << o.groups_min << ")." << std::endl;
     std::exit(EXIT_FAILURE);
   }
+  if (o.lists_capacity_given && !o.save_lists) {
+    std::cerr << "--lists-capacity needs --save-lists R." << std::endl;
+    std::exit(EXIT_FAILURE);
+  }
+  if (o.save_lists && o.gpus_given) {
+    std::cerr << "--save-lists runs on one GPU: it cannot be combined with --gpus." << std::endl;
+    std::exit(EXIT_FAILURE);
+  }
+  if (o.save_lists && !o.lists_capacity_given) o.lists_capacity = 64ull * o.size;
+  if (o.save_lists && o.lists_capacity > (1ull << 32)) o.lists_capacity = 1ull << 32;
   if (o.block_levels_given && !(o.block_eta > 0.0)) {
     std::cerr << "--block-levels needs --block-eta ETA." << std::endl;
     std::exit(EXIT_FAILURE);

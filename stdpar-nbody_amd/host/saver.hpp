@@ -9,6 +9,9 @@
 //   groups.bin:     u32 nbodies, u32 steps, u32 sizeof(T), u32 dim, f64 b, u32 min_members, then per save_all the u32[4] summary
 //                   (groups, catalogued groups c, largest size, its label), label u32[n], size u32[n], then c entries of
 //                   {u32 label, u32 size, T mass, T com[dim]}
+// and, with --save-lists R (--lists-capacity C),
+//   lists.bin:      u32 nbodies, u32 steps, u32 sizeof(T), u32 dim, f64 r, u64 capacity, then per save_all the u64[4] summary (total,
+//                   largest count, the lowest index that has it, status), count u32[n], then list u32[total] if the status is 0
 #pragma once
 #include <cstdint>
 #include <cstdlib>
@@ -27,7 +30,7 @@ class Saver {
   explicit Saver(Options const& o)
    : pos_(o.save_pos), energy_(o.save_energy), tree_energy_(o.tree_energy), quadrupole_(o.quadrupole), softening_(o.softening),
      neighbours_(o.save_neighbours), density_k_(o.save_density), density_tree_(o.density_tree), groups_(o.save_groups), groups_b_(o.groups_b),
-     groups_min_(std::uint32_t(o.groups_min)), theta_(o.theta), nbodies_(std::uint32_t(o.size)), nsteps_(std::uint32_t(o.steps)) {
+     groups_min_(std::uint32_t(o.groups_min)), lists_(o.save_lists), lists_r_(o.lists_r), lists_capacity_(o.lists_capacity), theta_(o.theta), nbodies_(std::uint32_t(o.size)), nsteps_(std::uint32_t(o.steps)) {
     std::uint32_t const tsz = sizeof(T), dim = D;
     if (pos_) {
       pos_file_.open("positions.bin", std::ios::out | std::ios::binary);
@@ -66,9 +69,18 @@ class Saver {
       put(groups_file_, groups_b_);
       put(groups_file_, groups_min_);
     }
+    if (lists_) {
+      lists_file_.open("lists.bin", std::ios::out | std::ios::binary);
+      put(lists_file_, nbodies_);
+      put(lists_file_, nsteps_);
+      put(lists_file_, tsz);
+      put(lists_file_, dim);
+      put(lists_file_, lists_r_);
+      put(lists_file_, lists_capacity_);
+    }
   }
 
-  bool active() const { return pos_ || energy_ || neighbours_ || density_k_ != 0 || groups_; }
+  bool active() const { return pos_ || energy_ || neighbours_ || density_k_ != 0 || groups_ || lists_; }
 
   // one frame; the device copy is authoritative, so positions are pulled first
   void save_all(System<T, D>& sys, Device<T, D>& dev) {
@@ -106,6 +118,13 @@ class Saver {
         groups_file_.write(reinterpret_cast<char const*>(&cat_com_[e * D]), std::streamsize(sizeof(T) * D));
       }
     }
+    if (lists_) {
+      std::uint64_t summary[4];
+      dev.lists(lists_r_, lists_capacity_, summary, count_, list_);  // list_ is empty when the status is not 0
+      lists_file_.write(reinterpret_cast<char const*>(summary), std::streamsize(sizeof summary));
+      lists_file_.write(reinterpret_cast<char const*>(count_.data()), std::streamsize(count_.size() * sizeof(std::uint32_t)));
+      lists_file_.write(reinterpret_cast<char const*>(list_.data()), std::streamsize(list_.size() * sizeof(std::uint32_t)));
+    }
   }
 
  private:
@@ -122,11 +141,14 @@ class Saver {
   bool groups_;                    // --save-groups B: the friends-of-friends groups of every recorded frame
   double groups_b_;                // ... its linking length
   std::uint32_t groups_min_;       // --groups-min M: the smallest group the catalogue lists
+  bool lists_;                     // --save-lists R: the fixed-radius neighbour lists of every recorded frame
+  double lists_r_;                 // ... its radius
+  std::uint64_t lists_capacity_;   // --lists-capacity C: the list entries a frame may hold
   double theta_;
   std::uint32_t nbodies_, nsteps_;
-  std::ofstream pos_file_, energy_file_, neighbours_file_, density_file_, groups_file_;
+  std::ofstream pos_file_, energy_file_, neighbours_file_, density_file_, groups_file_, lists_file_;
   std::vector<T> phi_, nnd2_, rho_;
-  std::vector<std::uint32_t> nn_, label_, size_, cat_label_, cat_size_;
+  std::vector<std::uint32_t> nn_, label_, size_, cat_label_, cat_size_, count_, list_;
   std::vector<T> cat_mass_, cat_com_;
 };
 
